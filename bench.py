@@ -12,16 +12,22 @@ Workloads (`--workload`), all with the same JSON schema:
   am-cs16   configs[4], AM half: 256 hybrid-AM MA1 cs16 streams @46511.71875 S/s, 61 s each
   am-cu8    configs[4], AM half through the 5-stage 32:1 decimator: 128 MA1 cu8 streams @1.488375 MS/s
   mixed     configs[4]: 128 FM cu8 + 64 AM cs16 + 64 AM cu8 streams in one engine
-The default fm line also carries: configs[1] (one FM stream, `single_stream`), the in-order (reference event timing) figure of
-the same batch (`in_order`), compact configs[4] legs (`config4`: am-cs16 and mixed, 3 passes each) and the DROP-IN as a user of
-`nrsc5 -r` sees it (`dropin`: the reference's public pipe API on libnrsc5_hipdropin.so vs the plain reference).
+A plain run sets up, warms up, times `--steps` passes and prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = wall time of one timed pass) and the `roofline` of those passes.  `--dump-outputs DIR`
+writes what the last timed pass handed its caller (records, counts, decoded frames) as .npy files; the inputs are seeded, so two
+builds run with the same arguments can be compared file by file.
 
-Parity is enforced, not reported: every stream that lost sync in the last pass plus `--oracle-streams` others is compared with
-the UNMODIFIED reference (oracle/_ref, its own L2) -- complete ordered log, frames bit-exact -- and the process exits non-zero
-when any compared log differs or a checker leg raises (the JSON line is still printed, with the failure in it).
+`--full` adds everything else, after the timed passes: the truth check of the decoded frames, the L2 index property check, the CPU
+baseline (`cpu_baseline`) and, for the default fm line, configs[1] (one FM stream, `single_stream`), the in-order (reference event
+timing) figure of the same batch (`in_order`), compact configs[4] legs (`config4`: am-cs16 and mixed, 3 passes each) and the DROP-IN
+as a user of `nrsc5 -r` sees it (`dropin`: the reference's public pipe API on libnrsc5_hipdropin.so vs the plain reference).
+
+With `--full`, parity is enforced, not reported: every stream that lost sync in the last pass plus `--oracle-streams` others is
+compared with the UNMODIFIED reference (oracle/_ref, its own L2) -- complete ordered log, frames bit-exact -- and the process exits
+non-zero when any compared log differs or a checker leg raises (the JSON line is still printed, with the failure in it).
 
 `python bench.py --gpus N` starts its N ranks itself (one process per GPU, torch.distributed over RCCL) unless it already
-runs under torchrun.  Prints ONE JSON line on rank 0 with `roofline` and `cpu_baseline`.
+runs under torchrun.
 """
 from __future__ import annotations
 
@@ -61,6 +67,9 @@ def parse(argv=None):
     ap.add_argument("--workload", default="fm", choices=["fm", "am-cs16", "am-cu8", "mixed"])
     ap.add_argument("--steps", type=int, default=10, help="timed passes (SURVEY 8d: median of >= 10 next to the mean)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="after the timed passes also run every check and side measurement: truth check, parity vs the reference, "
+                    "L2 index property, CPU baseline, single-stream / in-order / drop-in / configs[4] legs (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed pass returned (records, counts, sampled frames) to DIR/<name>.npy")
     ap.add_argument("--streams", type=int, default=0, help="streams per GPU (default: 256; am-cu8: 128)")
     ap.add_argument("--stream-base", type=int, default=0, help="first global stream id (a stream's CFO / offset / noise / channel are seeded by its id: another base = another batch)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak", help="--gpus N: weak = --streams per GPU; strong = --total-streams split over the ranks (configs[3]: 2048)")
@@ -969,9 +978,9 @@ def dropin_leg(iq: np.ndarray, fs: float):
     import ctypes
     from oracle import ref
     from tests import common
-    paths = {"dropin": os.path.join(ROOT, "integration", "_build", "libnrsc5_hipdropin.so"), "plain": os.path.join(ROOT, "oracle", "_ref", "libnrsc5_plain.so")}
+    paths = {"dropin": os.path.join(ROOT, "oracle", "_ref", "libnrsc5_hipdropin.so"), "plain": os.path.join(ROOT, "oracle", "_ref", "libnrsc5_plain.so")}
     if not all(os.path.exists(p) for p in paths.values()):
-        return {"skipped": "integration/_build/libnrsc5_hipdropin.so or oracle/_ref/libnrsc5_plain.so not prebuilt (need /root/reference in the build container)"}
+        return {"skipped": "oracle/_ref/libnrsc5_hipdropin.so or oracle/_ref/libnrsc5_plain.so not built (oracle/Makefile needs the reference sources)"}
     out, logs = {"feed": "nrsc5_pipe_samples_cu8, 32768-byte calls (src/main.c:1095-1121)", "seconds_of_signal": round(iq.size / 2 / fs, 2)}, {}
     from nrsc5_amd import engine as eng
     hip = eng.load_library()                                 # the same loaded libnrsc5hip.so the drop-in is linked with
@@ -1154,6 +1163,74 @@ def compact_leg(name, args, dev, local, steps=3):
     return out
 
 
+DUMP_BYTES = 64 << 20                    # --dump-outputs: upper bound of all files of one run (all ranks together)
+DUMP_FRAME_SHARE = 3 / 8                 # of that bound: the sampled frames; the rest: counts and records
+DUMP_FRAME_STREAMS = 16                  # streams whose decoded frames are written (a fixed, seeded sample)
+
+
+def dump_outputs(W, recs, counts, frames, out_dir, rank=0, world=1):
+    """--dump-outputs: what the last timed pass handed its caller, in capture-row order, as .npy files (integers as float64, exact;
+    float32 record fields as float32):
+      counts.npy               records delivered per stream
+      rec_streams.npy          the stream rows whose records follow: all of them, or -- when they would not fit their share of
+                               DUMP_BYTES -- a fixed, seeded sample (numpy seed 1), in row order
+      rec_<field>.npy          every delivered record of those streams, concatenated in row order, one file per RECORD_DTYPE field
+      frame_index.npy          [n, 4]: stream row, record index within the stream, first word in frame_words.npy, words
+      frame_words.npy          the 32-bit words of every frame a record announces (FM P1; AM P1 block / P3), for a fixed sample of
+                               streams (numpy seed 0, DUMP_FRAME_STREAMS of them); bits past the frame's length are cleared
+    With --gpus N every rank writes its own streams to DIR/rank<r>/ within its share of DUMP_BYTES."""
+    eng = W.eng
+    out = out_dir if world == 1 else os.path.join(out_dir, f"rank{rank}")
+    os.makedirs(out, exist_ok=True)
+    budget = DUMP_BYTES // world - (64 << 10)                          # .npy headers
+    frame_budget = int(budget * DUMP_FRAME_SHARE)
+    S = len(counts)
+    counts = np.asarray(counts).astype(np.int64)
+    rec_bytes = sum((4 if recs.dtype[n].base.kind == "f" else 8) * max(1, int(np.prod(recs.dtype[n].shape))) for n in recs.dtype.names)
+    fixed = 2 * 8 * S                                                  # counts.npy + rec_streams.npy at their largest
+    rows = np.arange(S)
+    if fixed + int(counts.sum()) * rec_bytes > budget - frame_budget:
+        room, keep = budget - frame_budget - fixed, []
+        for k in np.random.default_rng(1).permutation(S):
+            if int(counts[k]) * rec_bytes <= room:
+                keep.append(int(k))
+                room -= int(counts[k]) * rec_bytes
+        rows = np.sort(np.array(keep, dtype=np.int64))
+    valid = np.concatenate([np.asarray(recs[k, :counts[k]]) for k in rows]) if len(rows) else np.zeros(0, recs.dtype)
+    files = {"counts": counts.astype(np.float64), "rec_streams": rows.astype(np.float64)}
+    for name in valid.dtype.names:
+        col = valid[name]
+        files["rec_" + name] = col.astype(np.float32 if col.dtype.kind == "f" else np.float64)
+    sample = np.sort(np.random.default_rng(0).choice(S, size=min(DUMP_FRAME_STREAMS, S), replace=False)) if S else []
+    index, words, off, used = [], [], 0, 0
+    for k in sample:
+        am = W.is_am(int(k))
+        for j, r in enumerate(np.asarray(recs[k, :counts[k]])):
+            fl, slot = int(r["flags"]), int(r["p1_slot"])
+            spans = []
+            if fl & eng.REC_P1:
+                spans.append((int(r["bc_decoded"]) * eng.AM_P1_WORDS, eng.AM_P1_BITS) if am else (0, eng.P1_BITS))
+            if am and fl & eng.REC_P3:
+                spans.append((eng.AM_P3_WORD0, 30000 if int(r["psmi"]) == 2 else 24000))
+            for w0, nbits in spans:
+                nw = (nbits + 31) // 32
+                if used + (nw + 4) * 8 > frame_budget:
+                    continue
+                w = np.array(frames[k, slot, w0:w0 + nw], dtype=np.uint64)
+                if nbits % 32:
+                    w[-1] &= (1 << (nbits % 32)) - 1
+                index.append([k, j, off, nw])
+                words.append(w.astype(np.float64))
+                off += nw
+                used += (nw + 4) * 8
+    files["frame_index"] = np.array(index, dtype=np.float64).reshape(-1, 4)
+    files["frame_words"] = np.concatenate(words) if words else np.zeros(0, np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out, name + ".npy"), a)
+    return {"dir": out, "files": len(files), "bytes": int(sum(a.nbytes for a in files.values())), "frames": len(index),
+            "streams_with_records": int(len(rows))}
+
+
 def main():
     args = parse()
     from nrsc5_amd import shard
@@ -1214,20 +1291,24 @@ def main():
     tb_checked, tb_rewalked = E.tb_stats() if hasattr(E, "tb_stats") else (0, 0)
     dt = shard.max_over_ranks(dt, cdev)
     per_rank_ms = [round(x / args.steps * 1e3, 3) for x in shard.gather_floats(dt_rank, cdev)]
-    tot = shard.sum_over_ranks([W.samples, W.signal_seconds, 1.0], cdev)
+    tot = shard.sum_over_ranks([W.samples, W.signal_seconds, 1.0, float(len(my_streams))], cdev)
     total_samples, total_seconds, ranks_seen = float(tot[0]), float(tot[1]), int(tot[2])     # ranks_seen: counted through the collective itself
+    total_streams = int(tot[3])
 
     if hasattr(W, "unpermute"):
         recs, counts, frames = W.unpermute(recs, counts, frames)
-    rows = W.verify(recs, counts, frames)
-    allrows = shard.gather_summaries(np.array(rows, dtype=np.int64), cdev)
-    # Parity against the unmodified reference, on EVERY rank for its own streams (untimed): with --gpus N each rank fans its checker out
-    # over its share of the host cores and the verdicts are gathered, so that one multi-GPU run proves all N x 256 streams, not rank 0's.
-    checker = not args.no_cpu_baseline
+    dumped = dump_outputs(W, recs, counts, frames, args.dump_outputs, rank, world) if args.dump_outputs else None
+    # Everything below the headline runs with --full only (untimed)
+    checker = args.full and not args.no_cpu_baseline
     n_fail0 = len(FAILURES)
-    parity = checked_parity(W, recs, counts, frames, allrows if rank == 0 else np.array(rows, dtype=np.int64), checker)
-    per_rank_parity = None
-    if world > 1:
+    parity, per_rank_parity = None, None
+    if args.full:
+        rows = W.verify(recs, counts, frames)
+        allrows = shard.gather_summaries(np.array(rows, dtype=np.int64), cdev)
+        # Parity against the unmodified reference, on EVERY rank for its own streams (untimed): with --gpus N each rank fans its checker out
+        # over its share of the host cores and the verdicts are gathered, so that one multi-GPU run proves all N x 256 streams, not rank 0's.
+        parity = checked_parity(W, recs, counts, frames, allrows if rank == 0 else np.array(rows, dtype=np.int64), checker)
+    if args.full and world > 1:
         re_ = parity.get("reference_equality_rank0") or {}
         subs = [re_] if "streams_compared" in re_ else [v for v in re_.values() if isinstance(v, dict) and "streams_compared" in v]
         tot = lambda key: float(sum(x.get(key, 0) for x in subs))
@@ -1262,7 +1343,7 @@ def main():
             if r["parity_failures"] or (checker and r["streams_compared"] != r["streams"]):
                 FAILURES.append(f"rank {r['rank']}: {r['parity_failures']} parity failure(s), {r['streams_compared']} of {r['streams']} streams compared: {r['failures'][:3]}")
     checker = checker and world == 1     # the host-core legs below (CPU baseline, drop-in, configs[4]) belong to the single-GPU line
-    if args.workload == "fm" and not args.no_l2_index:
+    if args.full and args.workload == "fm" and not args.no_l2_index:
         try:
             parity["l2_index_rank0"] = W.l2_property()
         except Exception as ex:
@@ -1343,7 +1424,7 @@ def main():
                 cpu = {"error": repr(ex)}
                 FAILURES.append(f"cpu baseline leg raised {ex!r}")
     extra = {}
-    if args.workload == "fm" and world == 1 and not args.no_extra_legs:
+    if args.full and args.workload == "fm" and world == 1 and not args.no_extra_legs:
         try:
             sample = W.stream_iq(0)
             extra = W.extra_legs(local)
@@ -1357,7 +1438,7 @@ def main():
     config = W.describe(block_steps)
     if world > 1:
         config["parallelism"] = f"{world} ranks x {len(my_streams)} streams ({args.scaling} scaling), no data-path collective"
-        config["total_streams"] = int(allrows.shape[0])
+        config["total_streams"] = total_streams
     line = {
         "metric": "IQ MS/s demod+decoded", "value": round(value, 2), "unit": "IQ MS/s",
         "x_realtime": round(total_seconds * args.steps / dt, 1), "n_gpus": world, "ranks_in_process_group": ranks_seen, "steps": args.steps, "warmup": args.warmup,
@@ -1365,7 +1446,7 @@ def main():
         "ms_per_step_min_max": [round(min(pass_ms), 3), round(max(pass_ms), 3)], "per_rank_ms_per_step": per_rank_ms, "higher_is_better": True, "scaling": args.scaling,
         "vs_baseline": None, "dtype": W.dtype, "data": "synthetic",
         "config": config, "roofline": roofline, "cpu_baseline": cpu, "parity": parity,
-        "gen_seconds": round(t_gen, 1),
+        "gen_seconds": round(t_gen, 1), "full": args.full, "dumped_outputs": dumped,
         "traceback_walk": {"chunk_boundaries_checked": tb_checked, "chunks_rewalked": tb_rewalked,
                            "what": "single-path traceback: every 64-step chunk walked once after a 64-step run-in through the chunk above (speculative), the chain of chunk boundaries verified, wrong chunks re-walked (viterbi_v3.h); counts since the engine was created, rank 0"},
         "forward_pass_segments": {"boundaries_checked": fwd_checked, "segments_repaired": fwd_repaired,

@@ -4,6 +4,8 @@ The CPU-emulated twin used by the `-m "not gpu"` logic tests is built by `build_
 tests/simt/ -- test infrastructure, never loaded by the package itself."""
 from __future__ import annotations
 
+import contextlib
+import fcntl
 import os
 import subprocess
 import sys
@@ -29,6 +31,30 @@ def _deps():
     return d
 
 
+@contextlib.contextmanager
+def _build_lock(target: str):
+    """Serialises builds of one output across processes (pytest-xdist workers start together on a clean checkout): the caller checks
+    again, under the lock, whether the output is still stale, since another process may have built it meanwhile."""
+    fd = os.open(os.path.dirname(target), os.O_RDONLY)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX)
+        yield
+    finally:
+        os.close(fd)
+
+
+def _compile_to(target: str, cmd_for) -> None:
+    """Runs cmd_for(path) with a temporary path next to target, then replaces target in one rename: a process that has the old library
+    mapped, or opens it meanwhile, never sees a half-written file."""
+    tmp = "%s.tmp%d" % (target, os.getpid())
+    try:
+        subprocess.check_call(cmd_for(tmp))
+        os.replace(tmp, target)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+
+
 def source_sha() -> str:
     """Fingerprint of the device sources: measurements stored under profiles/ carry it, so that bench.py can tell whether a PMC
     figure was collected from THIS tree."""
@@ -43,13 +69,18 @@ def source_sha() -> str:
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     """Cross-compiles on a GPU-less host too (hipcc --offload-arch=gfx950)."""
     if force or _stale(LIB, _deps()):
-        srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES if os.path.exists(os.path.join(CSRC, f))]
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-               '-DNRSC5HIP_SOURCE_SHA="%s"' % source_sha(),        # nrsc5hip_source_sha(): callers can tell a stale build from the tree they run in
-               "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", LIB] + srcs
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
+        with _build_lock(LIB):
+            if force or _stale(LIB, _deps()):                   # not built by another process while this one waited
+                srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES if os.path.exists(os.path.join(CSRC, f))]
+
+                def cmd(out):
+                    c = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
+                         '-DNRSC5HIP_SOURCE_SHA="%s"' % source_sha(),        # nrsc5hip_source_sha(): callers can tell a stale build from the tree they run in
+                         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", out] + srcs
+                    if verbose:
+                        print(" ".join(c))
+                    return c
+                _compile_to(LIB, cmd)
     return LIB
 
 
@@ -76,15 +107,20 @@ def build_emu(force: bool = False) -> str:
     simt = os.path.join(ROOT, "tests", "simt")
     deps = _deps() + [os.path.join(simt, "hipemu.h"), os.path.join(simt, "hipemu.cpp")]
     if force or _stale(EMU_LIB, deps):
-        srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES if os.path.exists(os.path.join(CSRC, f))]
-        # -mfma (where the host has it): __builtin_fma of ref_sincosf becomes the instruction instead of a libm call; -ffp-contract=off keeps every other a * b + c unfused
-        fma = ["-mfma"] if _host_has_fma() else []
-        cmd = ["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-w"] + fma + ['-DNRSC5HIP_SOURCE_SHA="%s"' % source_sha(),
-               "-I" + simt, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", EMU_LIB,
-               os.path.join(simt, "hipemu.cpp")]
-        for s in srcs:
-            cmd += ["-x", "c++", s]
-        subprocess.check_call(cmd)
+        with _build_lock(EMU_LIB):
+            if force or _stale(EMU_LIB, deps):                  # not built by another process while this one waited
+                srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES if os.path.exists(os.path.join(CSRC, f))]
+                # -mfma (where the host has it): __builtin_fma of ref_sincosf becomes the instruction instead of a libm call; -ffp-contract=off keeps every other a * b + c unfused
+                fma = ["-mfma"] if _host_has_fma() else []
+
+                def cmd(out):
+                    c = ["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-w"] + fma + ['-DNRSC5HIP_SOURCE_SHA="%s"' % source_sha(),
+                         "-I" + simt, "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-o", out,
+                         os.path.join(simt, "hipemu.cpp")]
+                    for s in srcs:
+                        c += ["-x", "c++", s]
+                    return c
+                _compile_to(EMU_LIB, cmd)
     return EMU_LIB
 
 

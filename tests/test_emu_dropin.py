@@ -1,7 +1,8 @@
 """CPU (`-m "not gpu"`): the drop-in translation unit (integration/input_hip.c) under the reference's untouched L4 / L2 code, over
 the CPU-EMULATED twin of the library (tests/simt: same .hip sources compiled with g++) -- the shim's control flow (block-exact
 pieces, deliver-before-step order, polling, the zero-length flush) against the plain reference build through the public pipe API.
-Needs /root/reference (build container); the `-m gpu` twin with the real library is tests/test_gpu_dropin.py."""
+Both libraries are built into oracle/_ref/ by build() where the reference sources are present (oracle/Makefile); the `-m gpu` twin
+with the real library is tests/test_gpu_dropin.py."""
 import ctypes
 import os
 import subprocess
@@ -12,17 +13,18 @@ import pytest
 from tests import common
 from oracle import ref
 
-INTEG = os.path.join(common.ROOT, "integration")
+REF_BUILD = os.path.join(common.ROOT, "oracle", "_ref")
 
 
 @pytest.fixture(scope="module")
 def emu_dropin(emu_lib):
-    if not os.path.isdir("/root/reference/src"):
-        pytest.skip("needs /root/reference")
-    if not os.path.exists(os.path.join(common.ROOT, "oracle", "_ref", "libnrsc5_plain.so")):
-        pytest.skip("oracle/_ref/libnrsc5_plain.so not built")
-    subprocess.check_call(["make", "-C", INTEG, "emu"], stdout=subprocess.DEVNULL)
-    return os.path.join(INTEG, "_build", "libnrsc5_emudropin.so")
+    from nrsc5_amd import build
+    with build._build_lock(REF_BUILD):                        # a lock on oracle/: one xdist worker relinks, the others wait
+        subprocess.check_call(["make", "-C", os.path.dirname(REF_BUILD), "emu-dropin"], stdout=subprocess.DEVNULL)
+    for lib in ("libnrsc5_plain.so", "libnrsc5_emudropin.so"):
+        if not os.path.exists(os.path.join(REF_BUILD, lib)):
+            pytest.skip(f"oracle/_ref/{lib} not built (oracle/Makefile needs the reference sources)")
+    return os.path.join(REF_BUILD, "libnrsc5_emudropin.so")
 
 
 def _run(path, iq, chunk=32768, mode=0):

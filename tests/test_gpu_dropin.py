@@ -1,7 +1,7 @@
 """`-m gpu`: the DROP-IN seen from the reference's own public API (nrsc5.h): the reference's L4/L2/L1' code,
 unmodified, linked with integration/input_hip.c + libnrsc5hip.so, against the plain reference library.
 Both are driven only through nrsc5_open_pipe / nrsc5_set_mode / nrsc5_set_callback / nrsc5_pipe_samples_cu8.
-The libraries are prebuilt in the build container (integration/Makefile / oracle/Makefile need /root/reference)."""
+Both libraries are built into oracle/_ref/ by build() where the reference sources are present (oracle/Makefile)."""
 import ctypes
 import os
 
@@ -12,13 +12,13 @@ from tests import common
 from oracle import ref
 
 pytestmark = pytest.mark.gpu
-BUILD = {"libnrsc5_hipdropin.so": os.path.join(common.ROOT, "integration", "_build"), "libnrsc5_plain.so": os.path.join(common.ROOT, "oracle", "_ref")}
+BUILD = {"libnrsc5_hipdropin.so": os.path.join(common.ROOT, "oracle", "_ref"), "libnrsc5_plain.so": os.path.join(common.ROOT, "oracle", "_ref")}
 
 
 def _run(libname, iq, chunk=32768, mode=0):
     path = os.path.join(BUILD[libname], libname)
     if not os.path.exists(path):
-        pytest.skip(f"{libname} not prebuilt (integration/Makefile / oracle/Makefile need /root/reference)")
+        pytest.skip(f"oracle/_ref/{libname} not built (oracle/Makefile needs the reference sources)")
     lib = ctypes.CDLL(path)
     lib.pipe_run.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
     lib.pipe_run.restype = ctypes.c_size_t
@@ -83,7 +83,10 @@ def test_two_dropin_sessions_in_one_process(captures):
     32768-byte calls: each delivers exactly the events it delivers alone (= the plain reference's)."""
     a = np.ascontiguousarray(captures("fm_cu8_cfo137").iq)
     b = np.ascontiguousarray(captures("fm_cu8_cfo-2400").iq)
-    lib = ctypes.CDLL(os.path.join(BUILD["libnrsc5_hipdropin.so"], "libnrsc5_hipdropin.so"))
+    path = os.path.join(BUILD["libnrsc5_hipdropin.so"], "libnrsc5_hipdropin.so")
+    if not os.path.exists(path):
+        pytest.skip("oracle/_ref/libnrsc5_hipdropin.so not built (oracle/Makefile needs the reference sources)")
+    lib = ctypes.CDLL(path)
     if not hasattr(lib, "pipe_run_pair"):
         pytest.skip("drop-in not prebuilt with pipe_run_pair")
     vp, sz = ctypes.c_void_p, ctypes.c_size_t
@@ -173,5 +176,5 @@ def test_dropin_set_mode_on_a_live_session():
     from tests import test_emu_dropin as emu
     path = os.path.join(BUILD["libnrsc5_hipdropin.so"], "libnrsc5_hipdropin.so")
     if not os.path.exists(path) or not os.path.exists(os.path.join(BUILD["libnrsc5_plain.so"], "libnrsc5_plain.so")):
-        pytest.skip("drop-in / plain reference libraries not prebuilt (need /root/reference)")
+        pytest.skip("drop-in / plain reference libraries not built in oracle/_ref (oracle/Makefile needs the reference sources)")
     emu.check_dropin_set_mode_on_a_live_session(path)

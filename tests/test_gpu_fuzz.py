@@ -40,7 +40,7 @@ def test_gpu_fuzz_fm_cfo_search_batch(hip_lib):
 
 
 def _bench(args, timeout=600):
-    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--full"] + args, capture_output=True, text=True, timeout=timeout)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, (json.loads(lines[-1]) if lines else None)
 

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 def _run(tmp_path, streams, extra_env=None):
     env = dict(os.environ, NRSC5_BENCH_SHARE_GPU="1", NRSC5_SHARD_BACKEND="gloo", NRSC5_BENCH_VERDICT_DIR=str(tmp_path))
     env.update(extra_env or {})
-    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--streams", str(streams), "--seconds", "5", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--full", "--gpus", "2", "--streams", str(streams), "--seconds", "5", "--steps", "2", "--warmup", "1",
                         "--cpu-baseline-seconds", "1", "--parity-processes", "8"], env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     files = {}

@@ -19,8 +19,8 @@ if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 60000
     build.build_emu()
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "integration"), "emu"], stdout=subprocess.DEVNULL)
-    dropin = os.path.join(ROOT, "integration", "_build", "libnrsc5_emudropin.so")
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "_ref/libnrsc5_emudropin.so"], stdout=subprocess.DEVNULL)
+    dropin = os.path.join(ROOT, "oracle", "_ref", "libnrsc5_emudropin.so")
     plain = os.path.join(ROOT, "oracle", "_ref", "libnrsc5_plain.so")
     bad = after_reset_only = events = 0
     for i in range(n):

@@ -6,5 +6,5 @@ sys.path.insert(0, ROOT)
 from nrsc5_amd import engine as _eng
 _eng.DEFAULT_LIB = os.path.join(ROOT, "nrsc5_amd", "libnrsc5hip_r3arith.so")
 import bench
-sys.argv = ["bench.py", "--no-extra-legs", "--oracle-streams", "256", "--oracle-lost-max", "256", "--steps", "2", "--warmup", "1", "--cpu-baseline-seconds", "2"]
+sys.argv = ["bench.py", "--full", "--no-extra-legs", "--oracle-streams", "256", "--oracle-lost-max", "256", "--steps", "2", "--warmup", "1", "--cpu-baseline-seconds", "2"]
 bench.main()

@@ -1,10 +1,10 @@
 #!/bin/bash
 # the bench's own batches on further stream bases (other CFO / offset / noise / channel draws), every stream against the unmodified reference, all three workloads
-cd "${GRAFT_REPO_ROOT:-.}"; export TMPDIR=/tmp; mkdir -p gpurun_out; TAG=${1:-r06m}
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp; mkdir -p bench_logs; TAG=${1:-r06m}
 for SPEC in "fm 1024" "fm 1280" "fm 1536" "fm 1792" "am-cs16 1024" "am-cs16 1280" "am-cu8 1024" "mixed 1024" "mixed 1280"; do
   set -- $SPEC; WL=$1; B=$2
-  ( timeout 600 python bench.py --workload $WL --stream-base $B --no-extra-legs --steps 2 --warmup 1 --cpu-baseline-seconds 2 ) > gpurun_out/${TAG}_${WL}_base$B.log 2>gpurun_out/${TAG}_${WL}_base$B.err; rc=$?
-  python - $WL $B $rc gpurun_out/${TAG}_${WL}_base$B.log <<'PY'
+  ( timeout 600 python bench.py --full --workload $WL --stream-base $B --no-extra-legs --steps 2 --warmup 1 --cpu-baseline-seconds 2 ) > bench_logs/${TAG}_${WL}_base$B.log 2>bench_logs/${TAG}_${WL}_base$B.err; rc=$?
+  python - $WL $B $rc bench_logs/${TAG}_${WL}_base$B.log <<'PY'
 import json, sys
 wl, b, rc, path = sys.argv[1:5]
 try:
