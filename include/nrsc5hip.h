@@ -176,7 +176,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 7   /* 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 8   /* 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -495,6 +495,51 @@ int nrsc5hip_profile(nrsc5hip_engine *e, int enable, double *total_ms, long long
 int nrsc5hip_debug_fetch_q15(nrsc5hip_engine *e, int stream, long long n, int16_t *out /* [n][2] */);
 void *nrsc5hip_debug_alloc_copy(const void *host, size_t nbytes);
 void nrsc5hip_debug_free(void *dev);
+
+/* ---- wideband channelizer (ABI 8): one SDR capture at any rate -> one reference-format cs16 stream per station -------------
+ * Input: complex samples x[n] (n counted from the last create / reset) at Fs_in = rate_num / rate_den S/s, 744 187.5 <= Fs_in
+ * <= 64e6, as cu8 (scaled (b - 127) * 64, U8_Q15 of defines.h:93), cs16 (as is) or cf32 (v * 32768).  Per channel k (1 <= K <= 512):
+ *   mixer      x[n] * exp(-j 2 pi theta_k[n] / 2^32), theta_k[n] = n * s_k mod 2^32, s_k = round(f_k / Fs_in * 2^32): integer phase,
+ *              no drift however long the session; the realised offset s_k * Fs_in / 2^32 is reported by nrsc5hip_chan_info
+ *   resampler  output m at input time t_m = m * P / Q (P / Q = Fs_in / 744 187.5, reduced), floor(t_m) and (m P mod Q) / Q in 64-bit
+ *              integers; y_k[m] = g_k * sum_n mixed[n] * h(t_m - n), h a Kaiser lowpass of support T input samples (passband
+ *              +-0.1 dB to 198.5 kHz, >= 70 dB from 545.8 kHz), stored as a float32 table of L phases x T taps (nearest phase;
+ *              nrsc5hip_chan_taps reads it back); samples before n = 0 are zero
+ *   output     round to nearest, clamp to int16 (clamped samples counted per channel), interleaved cs16 at 744 187.5 S/s: the
+ *              stream a tuner centred at f_k hands to nrsc5_pipe_samples_cs16 (a station at +f_k comes out at 0 Hz, unconjugated)
+ * Output m exists once input floor(t_m) + T/2 has arrived: the output count depends on the total input only, and every output's
+ * arithmetic on absolute indices only, so any chunking of the input (down to 1 sample) gives identical bytes.
+ * The object runs on its own HIP stream on cfg.device (switched to and restored by every entry point, as for an engine); it is not
+ * re-entrant.  nrsc5hip_chan_create rejects (NRSC5HIP_EINVAL) a rate out of range, a rate whose reduced ratio P / Q has a term of 2^31
+ * or more (rate_den above ~1442 with terms prime to 1488375 * 2), |f_k| > Fs_in / 2 - 198.5 kHz, nchan outside 1..512 and an unknown
+ * format. */
+enum { NRSC5HIP_IQ_CU8 = 0, NRSC5HIP_IQ_CS16 = 1, NRSC5HIP_IQ_CF32 = 2 };
+typedef struct nrsc5hip_chan_config {
+    int device, format, nchan;
+    long long rate_num, rate_den;        /* Fs_in = rate_num / rate_den S/s */
+    const double *offset_hz;             /* [nchan] centre of each channel relative to the capture centre */
+    const float *gain;                   /* [nchan] or NULL (1) */
+} nrsc5hip_chan_config;
+typedef struct nrsc5hip_chan nrsc5hip_chan;
+int  nrsc5hip_chan_create(const nrsc5hip_chan_config *cfg, nrsc5hip_chan **out);
+void nrsc5hip_chan_destroy(nrsc5hip_chan *c);
+int  nrsc5hip_chan_reset(nrsc5hip_chan *c);                                    /* == a freshly created object */
+/* realised_offset_hz[nchan] (may be NULL), taps = T, phases = L */
+int  nrsc5hip_chan_info(nrsc5hip_chan *c, double *realised_offset_hz, int *taps, int *phases);
+int  nrsc5hip_chan_taps(nrsc5hip_chan *c, float *table /* [phases][taps] */);
+/* outputs per channel the next push of n_in samples yields (negative: error) */
+long long nrsc5hip_chan_outputs_for(nrsc5hip_chan *c, long long n_in);
+/* dev_in: device buffer of n_in complex samples of cfg.format; channel k's new outputs go to dev_out + k * out_stride_elems (int16
+ * elements, >= 2 * out_capacity when nchan > 1).  NRSC5HIP_EOVERFLOW when they exceed out_capacity (samples per channel): the object is
+ * then untouched.  Returns when the outputs are complete and dev_in is no longer read (a wait on the channelizer's own stream). */
+int  nrsc5hip_chan_process(nrsc5hip_chan *c, const void *dev_in, long long n_in, int16_t *dev_out, long long out_stride_elems,
+                           long long out_capacity, long long *n_out);
+int  nrsc5hip_chan_clip_counts(nrsc5hip_chan *c, long long *counts /* [nchan], since create / reset */);
+/* channelize and append channel k's new outputs to stream stream_ids[k] of an engine on the same device -- what
+ * nrsc5hip_batch_append_cs16 of those outputs does; follow with nrsc5hip_batch_process.  The engine's stream waits for the channelizer
+ * through an event (no device-wide sync), and the channelizer's next write to its staging buffer waits for the engine's append. When the
+ * engine refuses the append (a stream id, q15_capacity: its error code is returned) the channelizer is left as before the call. */
+int  nrsc5hip_chan_feed(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, const void *dev_in, long long n_in);
 
 #ifdef __cplusplus
 }

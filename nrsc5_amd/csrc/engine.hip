@@ -47,6 +47,7 @@ extern "C" void nrsc5hip_debug_seam_counts(double out[6], int reset)
     for (int k = 0; k < 6; k++) { if (out) out[k] = g_seam[8 + k]; if (reset) g_seam[8 + k] = 0; }
 }
 extern "C" const char *nrsc5hip_last_error(void) { return g_err; }
+namespace nrsc5 { void set_last_error(const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); } }   // other translation units (k_channelize)
 #ifndef NRSC5HIP_SOURCE_SHA
 #define NRSC5HIP_SOURCE_SHA "unknown"
 #endif

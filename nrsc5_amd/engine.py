@@ -66,6 +66,17 @@ class L2Job(ctypes.Structure):
                 ("nbits", ctypes.c_int32)]
 
 
+class _ChanConfig(ctypes.Structure):
+    """nrsc5hip_chan_config"""
+    _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("nchan", ctypes.c_int), ("rate_num", ctypes.c_longlong),
+                ("rate_den", ctypes.c_longlong), ("offset_hz", ctypes.c_void_p), ("gain", ctypes.c_void_p)]
+
+
+IQ_CU8, IQ_CS16, IQ_CF32 = 0, 1, 2
+IQ_FORMATS = {"cu8": IQ_CU8, "cs16": IQ_CS16, "cf32": IQ_CF32}
+IQ_DTYPES = {IQ_CU8: np.uint8, IQ_CS16: np.int16, IQ_CF32: np.float32}
+EINVAL, ENOMEM, EHIP, EOVERFLOW = -1, -2, -3, -4
+
 L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
 TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
 L2_STATUS = ("end", "no_audio", "fixed_data", "header_rs", "bad_locators", "too_many_pdus", "hef_overrun", "bad_stream", "bad_length", "audio_end")
@@ -172,6 +183,18 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_hdc_adts.restype = ctypes.c_size_t
     lib.nrsc5hip_hdc_host_bytes.argtypes = [vp]
     lib.nrsc5hip_hdc_host_bytes.restype = ctypes.c_size_t
+    ll = ctypes.c_longlong
+    lib.nrsc5hip_chan_create.argtypes = [ctypes.POINTER(_ChanConfig), ctypes.POINTER(vp)]
+    lib.nrsc5hip_chan_destroy.argtypes = [vp]
+    lib.nrsc5hip_chan_destroy.restype = None
+    lib.nrsc5hip_chan_reset.argtypes = [vp]
+    lib.nrsc5hip_chan_info.argtypes = [vp, vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.nrsc5hip_chan_taps.argtypes = [vp, vp]
+    lib.nrsc5hip_chan_outputs_for.argtypes = [vp, ll]
+    lib.nrsc5hip_chan_outputs_for.restype = ll
+    lib.nrsc5hip_chan_process.argtypes = [vp, vp, ll, vp, ll, ll, ctypes.POINTER(ll)]
+    lib.nrsc5hip_chan_clip_counts.argtypes = [vp, vp]
+    lib.nrsc5hip_chan_feed.argtypes = [vp, vp, vp, vp, ll]
     return lib
 
 
@@ -186,7 +209,9 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
     "nrsc5hip_hdc_create", "nrsc5hip_hdc_destroy", "nrsc5hip_hdc_reset", "nrsc5hip_hdc_push_frame", "nrsc5hip_hdc_advance",
-    "nrsc5hip_hdc_adts", "nrsc5hip_hdc_host_bytes", "nrsc5hip_hdc_fixed_audio_end", "nrsc5hip_l2_apply_audio_end", "nrsc5hip_hdc_frame_reset"]
+    "nrsc5hip_hdc_adts", "nrsc5hip_hdc_host_bytes", "nrsc5hip_hdc_fixed_audio_end", "nrsc5hip_l2_apply_audio_end", "nrsc5hip_hdc_frame_reset",
+    "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
+    "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -582,6 +607,93 @@ class Engine:
         bins = np.zeros((32, 534), dtype=np.complex64)
         self._check(self.lib.nrsc5hip_debug_fetch(self._h, stream, pm.ctypes.data, bins.ctypes.data))
         return pm, bins
+
+
+class Channelizer:
+    """Wideband channelizer (nrsc5hip_chan_*): one capture at rate = rate_num / rate_den S/s in `fmt` (IQ_CU8 / IQ_CS16 / IQ_CF32)
+    -> one reference-format cs16 stream at 744 187.5 S/s per entry of offsets_hz.  Input and output buffers are device pointers
+    (ints) or torch tensors on the channelizer's device."""
+
+    OUT_RATE = 744187.5
+
+    def __init__(self, rate, fmt: int, offsets_hz, gains=None, device: int = 0, lib_path: str | None = None):
+        from fractions import Fraction
+        self.lib = load_library(lib_path)
+        r = Fraction(rate).limit_denominator(1 << 20) if isinstance(rate, float) else Fraction(rate)
+        self.rate_num, self.rate_den = r.numerator, r.denominator
+        self.fmt, self.device = int(fmt), device
+        self.offsets = np.ascontiguousarray(offsets_hz, dtype=np.float64).reshape(-1)
+        self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), self.offsets.shape))
+        self.nchan = int(self.offsets.size)
+        self.cfg = _ChanConfig(device, self.fmt, self.nchan, self.rate_num, self.rate_den, self.offsets.ctypes.data,
+                               None if self.gains is None else self.gains.ctypes.data)
+        self._h = ctypes.c_void_p()
+        self._check(self.lib.nrsc5hip_chan_create(ctypes.byref(self.cfg), ctypes.byref(self._h)))
+        T, L = ctypes.c_int(), ctypes.c_int()
+        self.realised = np.zeros(self.nchan, dtype=np.float64)
+        self._check(self.lib.nrsc5hip_chan_info(self._h, self.realised.ctypes.data, ctypes.byref(T), ctypes.byref(L)))
+        self.taps, self.phases = T.value, L.value
+
+    def _check(self, rc: int):
+        if rc != 0:
+            err = Nrsc5HipError(f"libnrsc5hip error {rc}: {self.lib.nrsc5hip_last_error().decode()}")
+            err.code = rc
+            raise err
+
+    def close(self):
+        if self._h:
+            self.lib.nrsc5hip_chan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._check(self.lib.nrsc5hip_chan_reset(self._h))
+
+    def table(self) -> np.ndarray:
+        """the prototype as stored: float32 [phases][taps]"""
+        t = np.zeros((self.phases, self.taps), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_chan_taps(self._h, t.ctypes.data))
+        return t
+
+    def outputs_for(self, n_in: int) -> int:
+        n = int(self.lib.nrsc5hip_chan_outputs_for(self._h, n_in))
+        if n < 0:
+            self._check(n)
+        return n
+
+    def clip_counts(self) -> np.ndarray:
+        out = np.zeros(self.nchan, dtype=np.int64)
+        self._check(self.lib.nrsc5hip_chan_clip_counts(self._h, out.ctypes.data))
+        return out
+
+    def process(self, dev_in: int, n_in: int, dev_out: int, stride_elems: int, capacity: int) -> int:
+        """raw form: n_in samples at device pointer dev_in; channel k's outputs at dev_out + k * stride_elems (int16); -> outputs per channel"""
+        n = ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_chan_process(self._h, dev_in, n_in, dev_out, stride_elems, capacity, ctypes.byref(n)))
+        return n.value
+
+    def process_tensor(self, x):
+        """torch device tensor of interleaved samples (uint8 / int16 / float32 by format) -> int16 tensor [nchan, n_out, 2]"""
+        import torch
+        n_in = x.numel() // 2
+        n_out = self.outputs_for(n_in)
+        out = torch.empty((self.nchan, max(n_out, 1), 2), dtype=torch.int16, device=x.device)
+        x = x.contiguous()
+        torch.cuda.current_stream(x.device).synchronize()          # the producer of x has finished: the channelizer runs on its own stream
+        got = self.process(x.data_ptr(), n_in, out.data_ptr(), 2 * out.shape[1], out.shape[1])
+        assert got == n_out
+        return out[:, :n_out]
+
+    def feed(self, engine: "Engine", stream_ids, dev_in: int, n_in: int):
+        """channelize and append channel k's outputs to stream_ids[k] of `engine` (follow with engine.batch_process)"""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        assert ids.size == self.nchan
+        self._check(self.lib.nrsc5hip_chan_feed(self._h, engine._h, ids.ctypes.data, dev_in, n_in))
 
 
 class HdcConsumer:
