@@ -17,8 +17,10 @@
  *                                            pids_frame_push (decode.c:471, pids.h:98),
  *                                            frame_push (decode.c:460, frame.h:53)
  *
- * plus an additive batch API (device-resident captures, many independent streams per call) that the
- * reference has no counterpart for.  All functions return 0 on success and a negative NRSC5HIP_E*
+ * plus an additive batch API (device-resident captures, many independent streams per call), a wideband
+ * channelizer (nrsc5hip_chan_*: one SDR capture -> one stream per station) and a band scan
+ * (nrsc5hip_scan_*: the averaged power spectrum of such a capture and the centres of the hybrid-FM
+ * stations in it) that the reference has no counterpart for.  All functions return 0 on success and a negative NRSC5HIP_E*
  * code on failure; nothing throws across the boundary; no C++/torch types appear in signatures.
  * Buffers passed in are borrowed for the duration of the call.  INTEGRATION.md shows the binding a
  * maintainer of the reference would add (src/input.c replacement + CMake lines).
@@ -176,7 +178,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 8   /* 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 9   /* 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -540,6 +542,57 @@ int  nrsc5hip_chan_clip_counts(nrsc5hip_chan *c, long long *counts /* [nchan], s
  * through an event (no device-wide sync), and the channelizer's next write to its staging buffer waits for the engine's append. When the
  * engine refuses the append (a stream id, q15_capacity: its error code is returned) the channelizer is left as before the call. */
 int  nrsc5hip_chan_feed(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, const void *dev_in, long long n_in);
+
+/* ---- band scan (ABI 9): where are the HD stations of a wideband capture? -----------------------------------------------------
+ * Input as for the channelizer: complex samples x[n] (n counted from the last create / reset) at Fs = rate_num / rate_den S/s,
+ * 744 187.5 <= Fs <= 64e6, as cu8 ((b - 127) * 64), cs16 (as is) or cf32 (v * 32768).
+ *   transform  nfft a power of two in 512..8192; cfg.nfft = 0 picks the smallest one >= Fs / 2000 Hz within that range
+ *   segments   segment s covers samples [s H, s H + nfft), H = nfft / 2 (Welch, 50 % overlap), window periodic Hann
+ *              w[j] = 0.5 - 0.5 cos(2 pi j / nfft); X_s[k] = sum_j w[j] x[s H + j] exp(-2 pi i j k / nfft)
+ *   result     PSD[i] = sum_s |X_s[k]|^2 / (S * sum_j w[j]^2), i = (k + nfft/2) mod nfft: bin i lies at (i - nfft/2) * Fs / nfft, S is
+ *              the number of complete segments since create / reset; white noise of variance v per sample gives PSD ~ v in every bin
+ * Pushes may have any length (nfft - 1 samples of history are carried).  The same sequence of pushes gives the same bytes on every run;
+ * another chunking of the same input computes the same segments and may add them in another order (all sums are double, as is the
+ * transform).  The object runs on its own HIP stream on cfg.device (switched to and restored by every entry point); it is not
+ * re-entrant.  nrsc5hip_scan_create rejects (NRSC5HIP_EINVAL) a rate that is not positive or out of range, an unknown format and an
+ * nfft that is neither 0 nor a power of two in 512..8192.
+ * Detector (host, double, deterministic; nrsc5hip_scan_detect_psd needs no device and no scan object):
+ *   floor      the 20th percentile of the PSD: element (int)(0.2 * (nfft - 1)) of the sorted bins
+ *   score(c)   for every bin centre c with |c| <= Fs/2 - 198.5 kHz: each sideband [c - 198 402, c - 129 361] and [c + 129 361,
+ *              c + 198 402] Hz (carriers 356 and 546 of the 363.373 Hz grid) is split into four equal parts; the mean linear power of a
+ *              part is the integral of the PSD, taken as constant across each bin, over the part's width; score = 10 log10(the least of
+ *              the eight means / floor)
+ *   picks      highest score first (ties: lower bin), none below threshold_db, none within +-min_separation_hz of an earlier pick
+ * It is liberal on purpose (no edge or flatness test): two analog-only FM stations 400 kHz apart fill both windows of the slot between
+ * them; nrsc5_amd/wideband.py: scan() confirms a nomination by decoding it. */
+typedef struct nrsc5hip_scan_config {
+    int device, format;
+    long long rate_num, rate_den;        /* Fs = rate_num / rate_den S/s */
+    int nfft;                            /* 0: the default for the rate */
+} nrsc5hip_scan_config;
+typedef struct nrsc5hip_scan_params {
+    double threshold_db;                 /* 6 */
+    double min_separation_hz;            /* 100e3 */
+} nrsc5hip_scan_params;
+typedef struct nrsc5hip_scan_station {
+    double offset_hz;                    /* the bin centre picked, relative to the capture centre */
+    float score_db, lower_db, upper_db;  /* lower / upper: mean power of the whole sideband over the floor */
+    float floor_db;                      /* 10 log10 of the floor, in the PSD's units */
+} nrsc5hip_scan_station;
+typedef struct nrsc5hip_scan nrsc5hip_scan;
+int  nrsc5hip_scan_create(const nrsc5hip_scan_config *cfg, nrsc5hip_scan **out);
+void nrsc5hip_scan_destroy(nrsc5hip_scan *s);
+int  nrsc5hip_scan_reset(nrsc5hip_scan *s);                                    /* == a freshly created object */
+/* dev_in: device buffer of n_in complex samples of cfg.format; returns when it is no longer read */
+int  nrsc5hip_scan_push(nrsc5hip_scan *s, const void *dev_in, long long n_in);
+int  nrsc5hip_scan_info(nrsc5hip_scan *s, int *nfft, long long *segments, double *bin_hz);      /* any pointer may be NULL */
+/* NRSC5HIP_EINVAL while no segment is complete */
+int  nrsc5hip_scan_spectrum(nrsc5hip_scan *s, double *psd /* [nfft] */);
+/* params NULL: the defaults.  Writes the first `max` picks (max >= 0) and sets *n to the number of picks found. */
+int  nrsc5hip_scan_detect_psd(const double *psd, int nfft /* a power of two >= 16 */, double fs, const nrsc5hip_scan_params *params,
+                              nrsc5hip_scan_station *stations_out, int max, int *n);
+/* nrsc5hip_scan_spectrum followed by nrsc5hip_scan_detect_psd */
+int  nrsc5hip_scan_detect(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_station *stations_out, int max, int *n);
 
 #ifdef __cplusplus
 }

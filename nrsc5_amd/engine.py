@@ -72,6 +72,23 @@ class _ChanConfig(ctypes.Structure):
                 ("rate_den", ctypes.c_longlong), ("offset_hz", ctypes.c_void_p), ("gain", ctypes.c_void_p)]
 
 
+class _ScanConfig(ctypes.Structure):
+    """nrsc5hip_scan_config"""
+    _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("rate_num", ctypes.c_longlong), ("rate_den", ctypes.c_longlong),
+                ("nfft", ctypes.c_int)]
+
+
+class ScanParams(ctypes.Structure):
+    """nrsc5hip_scan_params"""
+    _fields_ = [("threshold_db", ctypes.c_double), ("min_separation_hz", ctypes.c_double)]
+
+
+class ScanStation(ctypes.Structure):
+    """nrsc5hip_scan_station"""
+    _fields_ = [("offset_hz", ctypes.c_double), ("score_db", ctypes.c_float), ("lower_db", ctypes.c_float), ("upper_db", ctypes.c_float),
+                ("floor_db", ctypes.c_float)]
+
+
 IQ_CU8, IQ_CS16, IQ_CF32 = 0, 1, 2
 IQ_FORMATS = {"cu8": IQ_CU8, "cs16": IQ_CS16, "cf32": IQ_CF32}
 IQ_DTYPES = {IQ_CU8: np.uint8, IQ_CS16: np.int16, IQ_CF32: np.float32}
@@ -195,6 +212,15 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_chan_process.argtypes = [vp, vp, ll, vp, ll, ll, ctypes.POINTER(ll)]
     lib.nrsc5hip_chan_clip_counts.argtypes = [vp, vp]
     lib.nrsc5hip_chan_feed.argtypes = [vp, vp, vp, vp, ll]
+    lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
+    lib.nrsc5hip_scan_destroy.argtypes = [vp]
+    lib.nrsc5hip_scan_destroy.restype = None
+    lib.nrsc5hip_scan_reset.argtypes = [vp]
+    lib.nrsc5hip_scan_push.argtypes = [vp, vp, ll]
+    lib.nrsc5hip_scan_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ll), ctypes.POINTER(ctypes.c_double)]
+    lib.nrsc5hip_scan_spectrum.argtypes = [vp, vp]
+    lib.nrsc5hip_scan_detect.argtypes = [vp, ctypes.POINTER(ScanParams), vp, ci, ctypes.POINTER(ci)]
+    lib.nrsc5hip_scan_detect_psd.argtypes = [vp, ci, ctypes.c_double, ctypes.POINTER(ScanParams), vp, ci, ctypes.POINTER(ci)]
     return lib
 
 
@@ -211,7 +237,9 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_hdc_create", "nrsc5hip_hdc_destroy", "nrsc5hip_hdc_reset", "nrsc5hip_hdc_push_frame", "nrsc5hip_hdc_advance",
     "nrsc5hip_hdc_adts", "nrsc5hip_hdc_host_bytes", "nrsc5hip_hdc_fixed_audio_end", "nrsc5hip_l2_apply_audio_end", "nrsc5hip_hdc_frame_reset",
     "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
-    "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed"]
+    "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed",
+    "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",
+    "nrsc5hip_scan_spectrum", "nrsc5hip_scan_detect", "nrsc5hip_scan_detect_psd"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -694,6 +722,99 @@ class Channelizer:
         ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
         assert ids.size == self.nchan
         self._check(self.lib.nrsc5hip_chan_feed(self._h, engine._h, ids.ctypes.data, dev_in, n_in))
+
+
+def _stations(out, n: int) -> list:
+    return [{"offset_hz": float(s.offset_hz), "score_db": float(s.score_db), "lower_db": float(s.lower_db), "upper_db": float(s.upper_db),
+             "floor_db": float(s.floor_db)} for s in out[:n]]
+
+
+def detect_psd(psd, fs: float, threshold_db: float = 6.0, min_separation_hz: float = 100e3, max_stations: int = 512,
+               lib: ctypes.CDLL | None = None, lib_path: str | None = None) -> list:
+    """nrsc5hip_scan_detect_psd: the library's host detector on any spectrum (psd[i] at (i - nfft/2) * fs / nfft); no device, no scan
+    object.  -> [{"offset_hz", "score_db", "lower_db", "upper_db", "floor_db"}, ...], highest score first"""
+    lib = lib or load_library(lib_path)
+    psd = np.ascontiguousarray(psd, dtype=np.float64)
+    out = (ScanStation * max(max_stations, 1))()
+    n = ctypes.c_int()
+    rc = lib.nrsc5hip_scan_detect_psd(psd.ctypes.data, psd.size, float(fs), ctypes.byref(ScanParams(threshold_db, min_separation_hz)),
+                                      ctypes.addressof(out), max_stations, ctypes.byref(n))
+    if rc != 0:
+        err = Nrsc5HipError(f"libnrsc5hip error {rc}: {lib.nrsc5hip_last_error().decode()}")
+        err.code = rc
+        raise err
+    return _stations(out, min(n.value, max_stations))
+
+
+class Scanner:
+    """Band scan (nrsc5hip_scan_*): the averaged power spectrum of one capture at rate = rate_num / rate_den S/s in `fmt` (IQ_CU8 /
+    IQ_CS16 / IQ_CF32) and the hybrid-FM stations in it.  nfft: a power of two in 512..8192, or 0 for the rate's default.  Input
+    buffers are device pointers (ints) or torch tensors on the scanner's device."""
+
+    def __init__(self, rate, fmt: int, nfft: int = 0, device: int = 0, lib_path: str | None = None):
+        from fractions import Fraction
+        self.lib = load_library(lib_path)
+        r = Fraction(rate).limit_denominator(1 << 20) if isinstance(rate, float) else Fraction(rate)
+        self.rate_num, self.rate_den = r.numerator, r.denominator
+        self.rate = self.rate_num / self.rate_den
+        self.fmt, self.device = int(fmt), device
+        self._h = ctypes.c_void_p()
+        cfg = _ScanConfig(device, self.fmt, self.rate_num, self.rate_den, int(nfft))
+        self._check(self.lib.nrsc5hip_scan_create(ctypes.byref(cfg), ctypes.byref(self._h)))
+        n, seg, bw = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_double()
+        self._check(self.lib.nrsc5hip_scan_info(self._h, ctypes.byref(n), ctypes.byref(seg), ctypes.byref(bw)))
+        self.nfft, self.bin_hz = n.value, bw.value
+
+    def _check(self, rc: int):
+        if rc != 0:
+            err = Nrsc5HipError(f"libnrsc5hip error {rc}: {self.lib.nrsc5hip_last_error().decode()}")
+            err.code = rc
+            raise err
+
+    def close(self):
+        if self._h:
+            self.lib.nrsc5hip_scan_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._check(self.lib.nrsc5hip_scan_reset(self._h))
+
+    @property
+    def segments(self) -> int:
+        seg = ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_scan_info(self._h, None, ctypes.byref(seg), None))
+        return seg.value
+
+    def push(self, dev_in: int, n_in: int):
+        """raw form: n_in samples at device pointer dev_in"""
+        self._check(self.lib.nrsc5hip_scan_push(self._h, dev_in, n_in))
+
+    def push_tensor(self, x):
+        """torch device tensor of interleaved samples (uint8 / int16 / float32 by format)"""
+        import torch
+        x = x.contiguous()
+        torch.cuda.current_stream(x.device).synchronize()          # the producer of x has finished: the scanner runs on its own stream
+        self.push(x.data_ptr(), x.numel() // 2)
+
+    def spectrum(self):
+        """-> (freqs_hz [nfft], psd [nfft]), float64; bin i at (i - nfft/2) * bin_hz"""
+        psd = np.zeros(self.nfft, dtype=np.float64)
+        self._check(self.lib.nrsc5hip_scan_spectrum(self._h, psd.ctypes.data))
+        return (np.arange(self.nfft) - self.nfft // 2) * self.bin_hz, psd
+
+    def detect(self, threshold_db: float = 6.0, min_separation_hz: float = 100e3, max_stations: int = 512) -> list:
+        """-> [{"offset_hz", "score_db", "lower_db", "upper_db", "floor_db"}, ...], highest score first"""
+        out = (ScanStation * max(max_stations, 1))()
+        n = ctypes.c_int()
+        self._check(self.lib.nrsc5hip_scan_detect(self._h, ctypes.byref(ScanParams(threshold_db, min_separation_hz)), ctypes.addressof(out),
+                                                  max_stations, ctypes.byref(n)))
+        return _stations(out, min(n.value, max_stations))
 
 
 class HdcConsumer:

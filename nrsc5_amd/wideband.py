@@ -3,11 +3,17 @@ and the batch engine decodes them (p1_async, l2_feedback).
 
     python -m nrsc5_amd.wideband FILE --format cs16 --rate 20000000 --offsets -800e3,0,400e3
 
-prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC)."""
+prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  Without --offsets the stations are found
+first (scan(): the band scan nrsc5hip_scan_* nominates centres from the capture's power spectrum, a short decode confirms them):
+
+    python -m nrsc5_amd.wideband FILE --format cs16 --rate 20000000 [--scan-only] [--spectrum band.csv]
+
+prints one `found` line per station, then decodes the whole file at the centres found."""
 from __future__ import annotations
 
 import argparse
 import sys
+from dataclasses import dataclass
 from fractions import Fraction
 
 import numpy as np
@@ -65,6 +71,111 @@ class WidebandReceiver:
         self.chan.close()
 
 
+CONFIRM_SECONDS = 1.0       # twice the largest first-PIDS time measured on the synthetic scenes, and not below 1 s
+CONFIRM_MAX = 64            # nominations decoded by one confirmation pass, highest score first
+
+
+@dataclass
+class FoundStation:
+    offset_hz: float                     # centre relative to the capture centre (a bin centre of the survey)
+    score_db: float
+    lower_db: float
+    upper_db: float
+    floor_db: float = 0.0
+    freq_offset_hz: float | None = None  # confirmed stations: what the engine's SYNC reports at that centre
+    psmi: int | None = None
+    pids_ok: int | None = None           # PIDS frames with a good CRC-12 inside the confirmation window
+    first_pids_s: float | None = None    # capture time at the end of the push that delivered the first of them
+
+
+def _device_samples(raw, fmt: int, device: int):
+    import torch
+    dtype = eng.IQ_DTYPES[fmt]
+    if isinstance(raw, np.ndarray):
+        raw = torch.from_numpy(np.ascontiguousarray(raw, dtype=dtype)).to(torch.device("cuda", device))
+    return raw.contiguous()
+
+
+def survey(raw, rate, fmt: str, *, seconds: float | None = None, nfft: int = 0, threshold_db: float = 6.0, device: int = 0,
+           lib_path: str | None = None):
+    """power spectrum of the first `seconds` of the capture (all of it when None) and the detector's nominations
+    -> (freqs_hz, psd, [FoundStation, ...] by ascending offset)"""
+    code = eng.IQ_FORMATS[fmt]
+    x = _device_samples(raw, code, device)
+    n = x.numel() // 2
+    if seconds is not None:
+        n = min(n, int(seconds * float(Fraction(rate) if not isinstance(rate, float) else rate)))
+    sc = eng.Scanner(Fraction(rate) if not isinstance(rate, float) else rate, code, nfft=nfft, device=device, lib_path=lib_path)
+    try:
+        sc.push_tensor(x[:2 * n])
+        freqs, psd = sc.spectrum()
+        picks = sc.detect(threshold_db=threshold_db)
+    finally:
+        sc.close()
+    found = [FoundStation(p["offset_hz"], p["score_db"], p["lower_db"], p["upper_db"], p["floor_db"]) for p in picks]
+    return freqs, psd, sorted(found, key=lambda s: s.offset_hz)
+
+
+def confirm_stations(raw, rate, fmt: str, found, *, confirm_seconds: float = CONFIRM_SECONDS, chunk: int = 1 << 22, device: int = 0,
+                     lib_path: str | None = None) -> list:
+    """decode the nominated centres (the CONFIRM_MAX best scores) over the first confirm_seconds of the capture in one engine; keep
+    those whose stream reaches fine sync and delivers at least one PIDS frame with a good CRC-12"""
+    cands = sorted(found, key=lambda s: -s.score_db)[:CONFIRM_MAX]
+    if not cands:
+        return []
+    fs = float(Fraction(rate) if not isinstance(rate, float) else rate)
+    code = eng.IQ_FORMATS[fmt]
+    x = _device_samples(raw, code, device)
+    n = min(x.numel() // 2, int(confirm_seconds * fs))
+    q15 = int(n / fs * 744187.5) + 4 * 71280
+    rx = WidebandReceiver(rate, fmt, [s.offset_hz for s in cands], device=device, q15_capacity=q15, lib_path=lib_path)
+    try:
+        for p in range(0, n, chunk):
+            end = min(n, p + chunk)
+            rx.push(x[2 * p:2 * end])
+            for k, s in enumerate(cands):
+                if s.first_pids_s is None and rx.records[k]:
+                    fl = rx.records[k][-1]["flags"]
+                    if np.any(((fl & eng.REC_PIDS) != 0) & ((fl & eng.REC_PIDS_CRC) != 0)):
+                        s.first_pids_s = end / fs
+        kept = []
+        for k, s in enumerate(cands):
+            recs = rx.station_records(k)
+            fl = recs["flags"]
+            fine = np.nonzero(fl & eng.REC_TO_FINE)[0]
+            good = int(np.sum(((fl & eng.REC_PIDS) != 0) & ((fl & eng.REC_PIDS_CRC) != 0)))
+            if fine.size and good:
+                s.freq_offset_hz, s.psmi, s.pids_ok = float(recs["freq_offset"][fine[0]]), int(recs["psmi"][fine[0]]), good
+                kept.append(s)
+    finally:
+        rx.close()
+    return sorted(kept, key=lambda s: s.offset_hz)
+
+
+def scan(raw, rate, fmt: str, *, seconds: float | None = None, confirm: bool = True, confirm_seconds: float = CONFIRM_SECONDS,
+         threshold_db: float = 6.0, device: int = 0, lib_path: str | None = None) -> list:
+    """Find the HD stations of a capture.  raw: interleaved samples (numpy array, or torch tensor on the device) in `fmt` at `rate` S/s.
+    The spectrum is taken over the first `seconds` (None: everything); confirm=False returns the detector's nominations, confirm=True
+    only those that decode (fine sync and a PIDS frame with a good CRC) within the first confirm_seconds.  -> [FoundStation, ...] by
+    ascending offset."""
+    _, _, found = survey(raw, rate, fmt, seconds=seconds, threshold_db=threshold_db, device=device, lib_path=lib_path)
+    if not confirm:
+        return found
+    return confirm_stations(raw, rate, fmt, found, confirm_seconds=confirm_seconds, device=device, lib_path=lib_path)
+
+
+def format_found(s: FoundStation) -> str:
+    line = f"found {s.offset_hz / 1e3:+.1f} kHz score {s.score_db:.1f} dB lower {s.lower_db:.1f} upper {s.upper_db:.1f}"
+    return line + (f" psmi {s.psmi}" if s.psmi is not None else "")
+
+
+def write_spectrum_csv(path: str, freqs, psd):
+    with open(path, "w") as f:
+        f.write("freq_hz,power_db\n")
+        for fr, p in zip(freqs, psd):
+            f.write(f"{fr:.3f},{10 * np.log10(max(p, 1e-30)):.3f}\n")
+
+
 def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None:
     head = f"station {s} ({rx.offsets[s] / 1e3:+.1f} kHz):"
     if kind == "sync":
@@ -83,7 +194,12 @@ def main(argv=None) -> int:
     ap.add_argument("file")
     ap.add_argument("--format", choices=sorted(eng.IQ_FORMATS), default="cs16")
     ap.add_argument("--rate", required=True, help="S/s, an integer or a fraction num/den")
-    ap.add_argument("--offsets", required=True, help="comma-separated station centres in Hz relative to the capture centre")
+    ap.add_argument("--offsets", default=None, help="comma-separated station centres in Hz relative to the capture centre (default: --scan)")
+    ap.add_argument("--scan", action="store_true", help="find the stations first and print them (implied without --offsets)")
+    ap.add_argument("--scan-only", action="store_true", help="stop after the list of stations")
+    ap.add_argument("--scan-seconds", type=float, default=CONFIRM_SECONDS, help="how much of the file the scan looks at")
+    ap.add_argument("--threshold-db", type=float, default=6.0, help="least detector score of a nomination")
+    ap.add_argument("--spectrum", metavar="FILE.csv", default=None, help="write the scan's power spectrum: freq_hz,power_db per bin")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=1 << 22, help="samples per push")
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -93,11 +209,30 @@ def main(argv=None) -> int:
             break
     a = ap.parse_args(argv)
     rate = Fraction(a.rate)
-    offsets = [float(x) for x in a.offsets.split(",") if x]
+    offsets = None if a.offsets is None else [float(x) for x in a.offsets.split(",") if x]
     fmt = eng.IQ_FORMATS[a.format]
     dtype = eng.IQ_DTYPES[fmt]
     import os
     total = os.path.getsize(a.file) // (2 * np.dtype(dtype).itemsize)
+    do_scan = a.scan or a.scan_only or offsets is None
+    if do_scan or a.spectrum:
+        head = np.fromfile(a.file, dtype=dtype, count=2 * min(total, int(a.scan_seconds * float(rate))))
+        head = _device_samples(head, fmt, a.device)
+        freqs, psd, found = survey(head, rate, a.format, threshold_db=a.threshold_db, device=a.device)
+        if a.spectrum:
+            write_spectrum_csv(a.spectrum, freqs, psd)
+        if do_scan:
+            found = confirm_stations(head, rate, a.format, found, confirm_seconds=a.scan_seconds, device=a.device)
+            for s in found:
+                print(format_found(s), flush=True)
+            if a.scan_only:
+                return 0
+            if offsets is None:
+                offsets = [s.offset_hz for s in found]
+                if not offsets:
+                    print("no station found", file=sys.stderr)
+                    return 1
+        del head
     q15 = int(total / float(rate) * 744187.5) + 4 * 71280
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=q15)
     with open(a.file, "rb") as f:
