@@ -100,7 +100,8 @@ typedef struct nrsc5hip_config {
     int device;                /* HIP device ordinal */
     int max_streams;           /* independent IQ streams resident in this engine */
     long long q15_capacity;    /* decimated (744187.5 S/s) samples of FIFO per stream; >= 2 * 71280.
-                                  Batch use: capture length / 2 + 64. */
+                                  Batch use: capture length / 2 + 64 for a capture appended whole; a session of any length that
+                                  trims (nrsc5hip_batch_trim) needs NRSC5HIP_TRIM_RETAIN_MAX + its largest append. */
     int record_capacity;       /* block records retained per stream between drains (>= 64) */
     int p1_slots;              /* decoded P1 frames retained per stream between drains (>= 2) */
     int p1_async;              /* 0: decode each P1 frame before the next block of any stream (exact
@@ -112,8 +113,10 @@ typedef struct nrsc5hip_config {
                                   before its next block, as in the reference.  With p1_async = 1 (FM and AM) the verdict of a deferred
                                   decode arrives windows later: the stream is then rewound to the end of the block that delivered the
                                   frame and re-run from there, so the delivered records and frames are the reference's all the same
-                                  (needs the samples since that block still in the FIFO: batch use, or pushes whose records are
-                                  drained after each call; and record_capacity >= 256).
+                                  (the samples since that block stay in the FIFO: the batch appends never discard any, and
+                                  nrsc5hip_batch_trim gives back only what lies in front of every checkpoint a verdict may still
+                                  rewind to, so a batch session may run for any length; streaming pushes: drain the records after
+                                  each call; and record_capacity >= 256).
                                   0: the host does it through nrsc5hip_force_resync (the drop-in shim). */
     int am_enable;             /* allocate the AM buffers (1.4 MB per stream) so that streams may be switched to
                                   NRSC5HIP_MODE_AM */
@@ -178,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 9   /* 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 10   /* 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -236,6 +239,30 @@ int nrsc5hip_batch_append_cu8(nrsc5hip_engine *e, int nstreams, const int *strea
                               const uint8_t *dev_iq, long long stride_bytes, const uint32_t *nbytes);
 int nrsc5hip_batch_append_cs16(nrsc5hip_engine *e, int nstreams, const int *stream_ids,
                                const int16_t *dev_iq, long long stride_elems, const uint32_t *nelems);
+/* An append that does not fit (retained samples + new ones > q15_capacity) fails with NRSC5HIP_EOVERFLOW and leaves every listed stream untouched:
+ * the appends never discard samples by themselves.  Space comes back through nrsc5hip_batch_trim (ABI 10):
+ *
+ * Give back the FIFO space of the listed streams that nothing can read again: everything before min(rd, the oldest checkpoint a pending
+ * first-header verdict may rewind to).  retained[k] (may be NULL) = samples stream k still holds (wr - base) afterwards.
+ * The live samples move to the front of the stream's slab on the engine's stream, behind every block step and rollback submitted so far and ahead of the
+ * next append; results (records, frames) are the same as without the call.  Streams that read a capture in place (batch_zero_copy appends, the pinned
+ * capture of the fast streaming seam) hold nothing in the FIFO: they are left alone and report 0.  A stream id listed twice is NRSC5HIP_EINVAL.  A stream of the streaming seam that is listed here
+ * is, as with every batch entry point, read from the device from then on.
+ *
+ * NRSC5HIP_TRIM_RETAIN_MAX bounds what a trim can retain for a stream whose complete blocks have all been processed (nrsc5hip_batch_process ran until
+ * nothing was left): the oldest checkpoint with an open verdict belongs to a frame at most NWIN = 8 decode windows of 16 blocks old -- the decode of window w
+ * is waited for, and its verdict taken, before window w + 8 reuses its slot; NRSC5HIP_TUNE_VERDICT_LAG is clamped to 8 windows and so adds nothing -- and a
+ * block step advances the read position by at most its 33-symbol window of 71280 samples; the block in progress (the unread tail) is less than one more
+ * window.  (This bound is conservative by design.  With the present scheduler every nrsc5hip_batch_process, also one that stops at max_steps, returns with
+ * every deferred decode finished and every verdict taken, so the floor of a trim between two calls is the read position itself and the checkpoint terms
+ * never apply: the retained span measured after a process call that ran to the end is under one window, 71280 samples.  The bound, and with it a least
+ * capacity of 36.8 MB per station, is what the rule guarantees without relying on that.)  AM streams: windows of 8 blocks of 8910 samples each, NRSC5HIP_TRIM_RETAIN_MAX_AM.  Between two nrsc5hip_batch_process calls that ran to the end every verdict
+ * has been taken, and a trim then retains less than one window.  The smallest q15_capacity that carries a session of any length is therefore
+ * NRSC5HIP_TRIM_RETAIN_MAX (_AM for an AM stream) + the largest single append (in decimated samples); when the retained span leaves less room than that, the append reports
+ * NRSC5HIP_EOVERFLOW with the retained span in its message -- samples are never dropped silently. */
+#define NRSC5HIP_TRIM_RETAIN_MAX    ((8LL * 16 + 1) * 71280)  /* 9 195 120 samples (36.8 MB per stream) */
+#define NRSC5HIP_TRIM_RETAIN_MAX_AM ((8LL * 8 + 1) * 8910)    /*   579 150 samples */
+int nrsc5hip_batch_trim(nrsc5hip_engine *e, int nstreams, const int *stream_ids, long long *retained);
 /* Run block steps (every listed stream advances by at most one block per step) until no listed stream
  * has a complete window or max_steps is reached; *steps_done gets the number of steps that did work. */
 int nrsc5hip_batch_process(nrsc5hip_engine *e, int nstreams, const int *stream_ids, int max_steps, int *steps_done);

@@ -192,6 +192,7 @@ struct nrsc5hip_engine {
     size_t stage_ring_bytes;           // size of each of the NSTAGE staging buffers of the fast seam (a block of either mode fits)
     int *ids_dev; unsigned *nbytes_dev;
     int *all_ids_dev;                  // identity list 0..S-1
+    TrimPlan *trim_plan_dev;           // nrsc5hip_batch_trim: one plan per listed stream (k_trim.hip)
     // chunked K1 running ahead of the block steps on its own stream (fresh batches in the async pipeline)
     hipStream_t dec_stream;
     std::vector<hipEvent_t> dec_events;    // dec_events[c] fires when output samples [0, (c+1)*dec_chunk) of every stream are committed
@@ -657,6 +658,7 @@ extern "C" int nrsc5hip_engine_create(const nrsc5hip_config *cfg, nrsc5hip_engin
         if ((rc = dev_alloc(e, &e->ids_dev, S))) break;
         if ((rc = dev_alloc(e, &e->nbytes_dev, S))) break;
         if ((rc = dev_alloc(e, &e->all_ids_dev, S))) break;
+        if ((rc = dev_alloc(e, &e->trim_plan_dev, S))) break;
         std::vector<StreamState> init(S);
         std::vector<int> ident(S);
         for (size_t s = 0; s < S; s++) { init_state(init[s]); ident[s] = (int)s; }
@@ -1598,6 +1600,13 @@ static int upload_ids(nrsc5hip_engine *e, int n, const int *ids, const uint32_t 
     return 0;
 }
 
+// an append that does not fit is refused whole (nothing is written, no counter moves); the appends never trim by themselves
+static int fifo_overflow(nrsc5hip_engine *e, int s, long long incoming)
+{
+    FAIL(NRSC5HIP_EOVERFLOW, "stream %d: q15_capacity %lld too small for this batch: %lld samples retained + %lld appended (nrsc5hip_batch_trim gives back what nothing can read again)",
+         s, e->db.q15_cap, e->wr_host[s] - e->base_host[s], incoming);
+}
+
 extern "C" int nrsc5hip_batch_append_cu8(nrsc5hip_engine *e, int nstreams, const int *stream_ids,
                                          const uint8_t *dev_iq, long long stride_bytes, const uint32_t *nbytes)
 {
@@ -1615,7 +1624,7 @@ extern "C" int nrsc5hip_batch_append_cu8(nrsc5hip_engine *e, int nstreams, const
                 const int s = stream_ids ? stream_ids[k] : k;
                 if (nbytes[k] % 4) FAIL(NRSC5HIP_EINVAL, "chunk %d: nbytes %% 4 != 0", k);
                 const long long nout = (e->raw_host[s] + nbytes[k] / 2) / 32 - e->raw_host[s] / 32;
-                if (e->wr_host[s] - e->base_host[s] + nout > e->db.q15_cap) FAIL(NRSC5HIP_EOVERFLOW, "stream %d: q15_capacity %lld too small for this batch", s, e->db.q15_cap);
+                if (e->wr_host[s] - e->base_host[s] + nout > e->db.q15_cap) return fifo_overflow(e, s, nout);
                 if (nbytes[k] > mx) mx = nbytes[k];
             }
             { ProfScope p(e, NRSC5HIP_PROF_DECIMATE, e->main); launch_am_decimate_cu8(e->tb, e->db, nstreams, ids_dev, dev_iq, stride_bytes, e->nbytes_dev, mx, e->main); }
@@ -1648,8 +1657,7 @@ extern "C" int nrsc5hip_batch_append_cu8(nrsc5hip_engine *e, int nstreams, const
     for (int k = 0; k < nstreams; k++) {
         const int s = stream_ids ? stream_ids[k] : k;
         if (nbytes[k] % 4) FAIL(NRSC5HIP_EINVAL, "chunk %d: nbytes %% 4 != 0", k);
-        if (e->wr_host[s] - e->base_host[s] + nbytes[k] / 4 > e->db.q15_cap)
-            FAIL(NRSC5HIP_EOVERFLOW, "stream %d: q15_capacity %lld too small for this batch", s, e->db.q15_cap);
+        if (e->wr_host[s] - e->base_host[s] + nbytes[k] / 4 > e->db.q15_cap) return fifo_overflow(e, s, nbytes[k] / 4);
         if (nbytes[k] > mx) mx = nbytes[k];
     }
     bool fresh = e->cfg.p1_async != 0 && stream_ids == nullptr && nstreams == e->cfg.max_streams;
@@ -1706,13 +1714,64 @@ extern "C" int nrsc5hip_batch_append_cs16(nrsc5hip_engine *e, int nstreams, cons
         const int s = stream_ids ? stream_ids[k] : k;
         if (nelems[k] % 2) FAIL(NRSC5HIP_EINVAL, "chunk %d: odd cs16 length", k);
         if (e->attached[s]) FAIL(NRSC5HIP_EINVAL, "stream %d reads a zero-copy capture: reset it before appending samples", s);
-        if (e->wr_host[s] - e->base_host[s] + nelems[k] / 2 > e->db.q15_cap)
-            FAIL(NRSC5HIP_EOVERFLOW, "stream %d: q15_capacity %lld too small for this batch", s, e->db.q15_cap);
+        if (e->wr_host[s] - e->base_host[s] + nelems[k] / 2 > e->db.q15_cap) return fifo_overflow(e, s, nelems[k] / 2);
         if (nelems[k] > mx) mx = nelems[k];
     }
     launch_append_cs16(e->db, nstreams, ids_dev, dev_iq, stride_elems, e->nbytes_dev, mx, e->main);
     for (int k = 0; k < nstreams; k++) e->wr_host[stream_ids ? stream_ids[k] : k] += nelems[k] / 2;
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+
+// Give back the slab space of the listed streams in front of everything that may still be read (k_trim.hip).  On the chain stream, the only consumer of
+// db.q15, behind every block step and rollback submitted so far and ahead of the next append: batch_process returns with all of them done; ON_ENGINE_DEVICE
+// runs settle(), which harvests a block step of the streaming seam that is still in flight and waits for the ingest stream; leave_mirror submits what a push
+// left staged; a chunked append on the decimation stream is waited for here.
+static_assert(NRSC5HIP_TRIM_RETAIN_MAX == (16LL * NWIN + 1) * WIN_N, "include/nrsc5hip.h states the retention bound of the pipeline depth");
+static_assert(NRSC5HIP_TRIM_RETAIN_MAX_AM == (8LL * NWIN + 1) * AM_WIN, "include/nrsc5hip.h states the retention bound of the AM pipeline depth");
+extern "C" int nrsc5hip_batch_trim(nrsc5hip_engine *e, int nstreams, const int *stream_ids, long long *retained)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e) FAIL(NRSC5HIP_EINVAL, "null engine");
+    if (nstreams < 1 || nstreams > e->cfg.max_streams) FAIL(NRSC5HIP_EINVAL, "nstreams %d out of range", nstreams);
+    if (stream_ids) {
+        std::vector<char> seen(e->cfg.max_streams, 0);         // a stream listed twice would be moved by two grid rows at once
+        for (int k = 0; k < nstreams; k++) {
+            if (stream_ids[k] < 0 || stream_ids[k] >= e->cfg.max_streams) FAIL(NRSC5HIP_EINVAL, "stream id %d out of range", stream_ids[k]);
+            if (seen[stream_ids[k]]) FAIL(NRSC5HIP_EINVAL, "stream id %d listed twice", stream_ids[k]);
+            seen[stream_ids[k]] = 1;
+        }
+    }
+    // streams that read a capture in place (zero-copy batch, the pinned host capture of the fast seam) hold nothing in the slab: left alone
+    std::vector<int> act;
+    for (int k = 0; k < nstreams; k++) {
+        const int s = stream_ids ? stream_ids[k] : k;
+        if (retained) retained[k] = 0;
+        if (!e->attached[s] && e->hc_stream != s) act.push_back(s);
+    }
+    if (act.empty()) return 0;
+    const int n = (int)act.size();
+    int rc = leave_mirror(e, n, act.data()); if (rc) return rc;
+    if (e->dec_chunk) HIPCHK(hipStreamSynchronize(e->dec_stream));           // a chunked append still writing the slab
+    HIPCHK(hipMemcpy(e->ids_dev, act.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    // workgroups per stream of the disjoint move: about 512 over the whole launch (two per CU), at most 32 per stream -- what is moved is under one window
+    // (70 tiles of 4096 samples) per stream when the blocks have been processed.  Not tuned: a whole trim of 64 stations measured 0.1 ms.
+    launch_trim(e->db, n, e->ids_dev, e->trim_plan_dev, std::min(32, std::max(1, 512 / n)), e->main);
+    HIPCHK(hipGetLastError());
+    std::vector<TrimPlan> plan(n);
+    HIPCHK(hipMemcpyAsync(plan.data(), e->trim_plan_dev, n * sizeof(TrimPlan), hipMemcpyDeviceToHost, e->main));
+    HIPCHK(hipStreamSynchronize(e->main));
+    for (int k = 0; k < n; k++) {
+        const int s = act[k];
+        if (plan[k].wr != e->wr_host[s] || plan[k].base < e->base_host[s] || plan[k].base > plan[k].wr)
+            FAIL(NRSC5HIP_EHIP, "stream %d: the trim found wr %lld base %lld where the host holds wr %lld base %lld", s, plan[k].wr, plan[k].base, e->wr_host[s], e->base_host[s]);
+        e->base_host[s] = plan[k].base;
+    }
+    if (retained) for (int k = 0; k < nstreams; k++) {
+        const int s = stream_ids ? stream_ids[k] : k;
+        if (!e->attached[s] && e->hc_stream != s) retained[k] = e->wr_host[s] - e->base_host[s];
+    }
     return 0;
 }
 

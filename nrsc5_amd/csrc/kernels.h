@@ -126,6 +126,12 @@ void launch_sync(const DevTables &tb, const DevBuffers &db, int nstreams, const 
 // replay (k_replay.hip): apply the first-header verdicts of finished deferred P1 decodes -- rewind the stream to the failed frame
 void launch_rollback(const DevBuffers &db, int nstreams, const int *stream_ids, int cur_window, int min_age, hipStream_t st);
 void launch_rollback_am(const DevBuffers &db, int nstreams, const int *stream_ids, int cur_window, int min_age, hipStream_t st);
+// batched FIFO trim (k_trim.hip): per listed stream, move [floor, wr) to the front of its slab and set base = floor, where floor = the oldest sample the
+// stream itself or a replay checkpoint with a verdict still open may read.  plan[k] (device, one per list position): what was moved and the stream's
+// counters afterwards.  row_wgs: workgroups per stream for spans whose source and destination are disjoint (an overlapping span is walked by one).
+// A stream must not be listed twice
+struct TrimPlan { long long off, n, base, wr; };
+void launch_trim(const DevBuffers &db, int nstreams, const int *stream_ids, TrimPlan *plan, int row_wgs, hipStream_t st);
 void launch_pids_decode(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int nslots, hipStream_t st);
 // extended sidebands: interleaver IV for streams whose block pair just completed (after k_sync), and the staged P3/P4 decodes
 void launch_px_deint(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int slot, hipStream_t st);

@@ -93,6 +93,8 @@ IQ_CU8, IQ_CS16, IQ_CF32 = 0, 1, 2
 IQ_FORMATS = {"cu8": IQ_CU8, "cs16": IQ_CS16, "cf32": IQ_CF32}
 IQ_DTYPES = {IQ_CU8: np.uint8, IQ_CS16: np.int16, IQ_CF32: np.float32}
 EINVAL, ENOMEM, EHIP, EOVERFLOW = -1, -2, -3, -4
+TRIM_RETAIN_MAX = (8 * 16 + 1) * 71280      # NRSC5HIP_TRIM_RETAIN_MAX: what Engine.batch_trim can retain per FM stream (pipeline depth, include/nrsc5hip.h)
+TRIM_RETAIN_MAX_AM = (8 * 8 + 1) * 8910     # NRSC5HIP_TRIM_RETAIN_MAX_AM: ... per AM stream
 
 L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
 TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
@@ -146,6 +148,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_batch_append_cu8.argtypes = [vp, ci, vp, vp, ctypes.c_longlong, vp]
     lib.nrsc5hip_batch_append_cs16.argtypes = [vp, ci, vp, vp, ctypes.c_longlong, vp]
     lib.nrsc5hip_batch_process.argtypes = [vp, ci, vp, ci, ctypes.POINTER(ci)]
+    lib.nrsc5hip_batch_trim.argtypes = [vp, ci, vp, vp]
     lib.nrsc5hip_drain.argtypes = [vp, ci, vp, ci, ctypes.POINTER(ci)]
     lib.nrsc5hip_p1_frame_packed.argtypes = [vp, ci, ci, vp]
     lib.nrsc5hip_p1_frame_bits.argtypes = [vp, ci, ci, vp]
@@ -227,7 +230,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
 EXPORTED_SYMBOLS = [
     "nrsc5hip_engine_create", "nrsc5hip_engine_destroy", "nrsc5hip_last_error", "nrsc5hip_source_sha", "nrsc5hip_engine_hip_stream",
     "nrsc5hip_push_cu8", "nrsc5hip_push_cs16", "nrsc5hip_stream_reset", "nrsc5hip_stream_fresh", "nrsc5hip_force_resync", "nrsc5hip_bytes_to_next_block",
-    "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_drain",
+    "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
     "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
@@ -373,6 +376,15 @@ class Engine:
         self._check(self.lib.nrsc5hip_batch_process(self._h, nstreams, None if ids is None else ids.ctypes.data,
                                                     max_steps, ctypes.byref(done)))
         return done.value
+
+    def batch_trim(self, nstreams: int, stream_ids=None) -> np.ndarray:
+        """nrsc5hip_batch_trim: give back the FIFO space in front of everything the listed streams (0..nstreams-1 without a list) may
+        still read -- their read position and every replay checkpoint whose first-header verdict is still open.  -> the samples each
+        stream retains (wr - base); at most TRIM_RETAIN_MAX once batch_process has run to the end.  Results are unchanged."""
+        ids = None if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.int32)
+        kept = np.zeros(nstreams, dtype=np.int64)
+        self._check(self.lib.nrsc5hip_batch_trim(self._h, nstreams, None if ids is None else ids.ctypes.data, kept.ctypes.data))
+        return kept
 
     # ---- results ---------------------------------------------------------------------------------
     def drain(self, stream: int, max_records: int | None = None) -> np.ndarray:

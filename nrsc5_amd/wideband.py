@@ -2,8 +2,11 @@
 and the batch engine decodes them (p1_async, l2_feedback).
 
     python -m nrsc5_amd.wideband FILE --format cs16 --rate 20000000 --offsets -800e3,0,400e3
+    rtl_sdr -f 98.1e6 -s 2400000 - | python -m nrsc5_amd.wideband - --format cu8 --rate 2400000 --offsets -800e3,0,600e3
 
-prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  Without --offsets the stations are found
+prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  FILE may be `-` (standard input, read in
+--chunk pieces until it ends; --offsets is then required): the session may be of any length, the receiver gives FIFO space back as it
+goes (nrsc5hip_batch_trim).  Without --offsets the stations are found
 first (scan(): the band scan nrsc5hip_scan_* nominates centres from the capture's power spectrum, a short decode confirms them):
 
     python -m nrsc5_amd.wideband FILE --format cs16 --rate 20000000 [--scan-only] [--spectrum band.csv]
@@ -25,8 +28,12 @@ class WidebandReceiver:
     """rate: S/s (int, Fraction or float); fmt: "cu8" | "cs16" | "cf32"; offsets_hz: one station centre per entry, relative to the
     capture centre.  push() takes interleaved samples as a host numpy array or a torch tensor on the device; every push decodes what
     it completes, and each station's events (records_to_log's ordered log, frames included) accumulate in `logs[k]`.
-    q15_capacity: 744 187.5 S/s samples each station's engine stream holds -- the whole session's (the replay of l2_feedback
-    needs the samples since a frame's first block; size it for the capture)."""
+    q15_capacity: 744 187.5 S/s samples each station's engine stream holds.  A session may be of any length: when the next push
+    would not fit, push() first gives back what nothing can read again (Engine.batch_trim: everything in front of the read
+    position and of every replay checkpoint of l2_feedback whose verdict is still open).  The least capacity is
+    eng.TRIM_RETAIN_MAX (9 195 120: the depth of the decode pipeline, include/nrsc5hip.h) + the outputs of the largest push
+    (chan.outputs_for); the default carries any session at pushes of up to ~7.5 M outputs per station.  max_retained: the
+    largest span a trim has left in a station's FIFO so far; trims: how many pushes had to trim."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None):
         import torch
@@ -42,6 +49,11 @@ class WidebandReceiver:
         self.ids = np.arange(self.k, dtype=np.int32)
         self.logs = [[] for _ in range(self.k)]
         self.records = [[] for _ in range(self.k)]
+        self.q15_capacity = int(q15_capacity)
+        self.held = 0                    # samples every station's FIFO holds (wr - base): the channelizer gives each station the same count
+        self.max_retained = 0
+        self.pushes = 0
+        self.trims = 0
 
     def push(self, chunk) -> list:
         """-> the events this push produced: [(station, kind, fields), ...] in stream order per station"""
@@ -51,7 +63,15 @@ class WidebandReceiver:
         chunk = chunk.contiguous()
         torch.cuda.current_stream(chunk.device).synchronize()      # the channelizer works on its own stream
         n = chunk.numel() // 2
-        self.chan.feed(self.engine, self.ids, chunk.data_ptr(), n)
+        m = self.chan.outputs_for(n)
+        if self.held + m > self.q15_capacity:                      # amortised: most pushes fit and copy nothing
+            kept = self.engine.batch_trim(self.k, stream_ids=self.ids)
+            self.held = int(kept.max())
+            self.max_retained = max(self.max_retained, self.held)
+            self.trims += 1
+        self.chan.feed(self.engine, self.ids, chunk.data_ptr(), n)     # (still too large: EOVERFLOW from the append, nothing was touched)
+        self.held += m
+        self.pushes += 1
         self.engine.batch_process(self.k, stream_ids=self.ids)
         new = []
         for s in range(self.k):
@@ -191,7 +211,7 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nrsc5_amd.wideband", description=__doc__.splitlines()[0])
-    ap.add_argument("file")
+    ap.add_argument("file", help="capture file, or - for standard input (needs --offsets)")
     ap.add_argument("--format", choices=sorted(eng.IQ_FORMATS), default="cs16")
     ap.add_argument("--rate", required=True, help="S/s, an integer or a fraction num/den")
     ap.add_argument("--offsets", default=None, help="comma-separated station centres in Hz relative to the capture centre (default: --scan)")
@@ -202,6 +222,8 @@ def main(argv=None) -> int:
     ap.add_argument("--spectrum", metavar="FILE.csv", default=None, help="write the scan's power spectrum: freq_hz,power_db per bin")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=1 << 22, help="samples per push")
+    ap.add_argument("--q15-capacity", type=int, default=1 << 24,
+                    help="decimated samples of FIFO per station: at least %d + the outputs of one push, whatever the length of the session" % eng.TRIM_RETAIN_MAX)
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                  # "--offsets -800e3,0,400e3": a value that starts with '-' is still the value
         if argv[i] == "--offsets":
@@ -212,11 +234,12 @@ def main(argv=None) -> int:
     offsets = None if a.offsets is None else [float(x) for x in a.offsets.split(",") if x]
     fmt = eng.IQ_FORMATS[a.format]
     dtype = eng.IQ_DTYPES[fmt]
-    import os
-    total = os.path.getsize(a.file) // (2 * np.dtype(dtype).itemsize)
+    stdin = a.file == "-"
     do_scan = a.scan or a.scan_only or offsets is None
+    if stdin and (do_scan or a.spectrum):
+        ap.error("standard input cannot be scanned (the scan reads the head of a real file): give --offsets, without --scan / --spectrum")
     if do_scan or a.spectrum:
-        head = np.fromfile(a.file, dtype=dtype, count=2 * min(total, int(a.scan_seconds * float(rate))))
+        head = np.fromfile(a.file, dtype=dtype, count=2 * int(a.scan_seconds * float(rate)))
         head = _device_samples(head, fmt, a.device)
         freqs, psd, found = survey(head, rate, a.format, threshold_db=a.threshold_db, device=a.device)
         if a.spectrum:
@@ -233,11 +256,12 @@ def main(argv=None) -> int:
                     print("no station found", file=sys.stderr)
                     return 1
         del head
-    q15 = int(total / float(rate) * 744187.5) + 4 * 71280
-    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=q15)
-    with open(a.file, "rb") as f:
+    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity)
+    item = 2 * np.dtype(dtype).itemsize
+    with (sys.stdin.buffer if stdin else open(a.file, "rb")) as f:
         while True:
-            buf = np.fromfile(f, dtype=dtype, count=2 * a.chunk)
+            raw = f.read(item * a.chunk)                       # (a pipe: read() returns short only at the end of the stream)
+            buf = np.frombuffer(bytearray(raw[:len(raw) - len(raw) % item]), dtype=dtype)
             if buf.size < 2:
                 break
             for s, kind, v in rx.push(buf[:buf.size - buf.size % 2]):
