@@ -135,5 +135,7 @@ if __name__ == "__main__":
         print(build_hip_diag(["-DNRSC5HIP_MIXFFT_NOLOAD"], "libnrsc5hip_noload.so"))
     elif "--mixfft-phases" in sys.argv:
         print(build_hip_diag(["-DNRSC5HIP_MIXFFT_PHASES"], "libnrsc5hip_mixphases.so"))
+    elif "--tbwalk-phases" in sys.argv:
+        print(build_hip_diag(["-DNRSC5HIP_TBWALK_PHASES"], "libnrsc5hip_tbphases.so"))
     else:
         print(build_hip(force=True, verbose=True))

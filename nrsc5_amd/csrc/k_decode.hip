@@ -127,6 +127,15 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_p1_fix(DevTables tb, DevBuff
 }
 
 constexpr int TB_THREADS = 1024;
+// k_p1_traceback behind k_p1_tbwalk (verify / repair, error sum, descramble, first L2 header): workgroup size.  One workgroup per frame, so
+// a launch lasts as long as one workgroup's serial loops: 1024 threads keep them short (-DNRSC5HIP_TBC_THREADS=256 builds the small form for
+// an A/B run).  A thread looks after TBC_NM chunk boundaries of the check.
+#ifndef NRSC5HIP_TBC_THREADS
+#define NRSC5HIP_TBC_THREADS 1024
+#endif
+constexpr int TBC_THREADS = NRSC5HIP_TBC_THREADS;
+constexpr int TBC_NM = (P1_LEN / 64 + 1 + TBC_THREADS - 1) / TBC_THREADS;
+static_assert(TBC_THREADS % 64 == 0 && TBC_THREADS >= 64 && TBC_THREADS <= TB_THREADS, "check workgroup: whole waves, within k_p1_traceback's launch bound");
 constexpr int TBM_WAVES = 4;
 
 // pass 1 of the traceback (chunk maps + candidate outputs) as its own launch: `parts` workgroups of 4 waves per frame
@@ -147,6 +156,11 @@ __global__ __launch_bounds__(64 * TBM_WAVES) void k_p1_tbmap(DevTables tb, DevBu
 // of LDS each), and the block-step kernels of the chain queue waited behind them: the k_sync launch that coincided with a window's traceback lasted 370 - 550 us
 // instead of 37 (one per decode window: ~6 of the pass's 30 ms; profiles/r05_trace_sync.txt).  `ntasks` (part, stream) pairs are walked by gridDim.x resident
 // workgroups, parts of one frame by neighbouring workgroups.
+#ifdef NRSC5HIP_TBWALK_PHASES
+#define TBWALK_PHASE_CYCLES(db) ((db).sync_phase_cycles ? (db).sync_phase_cycles + 8 : nullptr)
+#else
+#define TBWALK_PHASE_CYCLES(db) nullptr
+#endif
 __global__ __launch_bounds__(64) void k_p1_tbwalk(DevTables tb, DevBuffers db, const int *ids, int parity, int lane_id, int prio, int nparts, int ntasks)
 {
     wave_set_priority(prio);
@@ -158,7 +172,7 @@ __global__ __launch_bounds__(64) void k_p1_tbwalk(DevTables tb, DevBuffers db, c
         const size_t slot = (size_t)lane_id * db.nstreams_alloc + s;
         uint32_t *out = db.p1_ring + ((size_t)s * db.p1_slots + st.p1_slot[parity]) * P1_WORDS;
         viterbi3_traceback_walk(db.dec + slot * (size_t)(2 * (P1_LEN + 64)), P1_LEN, st.p1_endlane[parity], out,
-                                db.tbmap + slot * ((size_t)(P1_LEN / 64 + 1) * 64), t % nparts, lds, db.coded + slot * P1_LEN);
+                                db.tbmap + slot * ((size_t)(P1_LEN / 64 + 1) * 64), t % nparts, lds, db.coded + slot * P1_LEN, TBWALK_PHASE_CYCLES(db));
         WAVE_LDS_FENCE();                                      // the next task refills the tile
     }
 }
@@ -179,7 +193,7 @@ __global__ __launch_bounds__(TB_THREADS) void k_p1_traceback(DevTables tb, DevBu
     uint32_t *out = db.p1_ring + ((size_t)s * db.p1_slots + st.p1_slot[parity]) * P1_WORDS;
     if (tid == 0) err_total = 0;
     uint8_t *gmap = db.tbmap + ((size_t)lane_id * db.nstreams_alloc + s) * ((size_t)(P1_LEN / 64 + 1) * 64);
-    if (maps_done == 2) viterbi3_traceback_check(dec, P1_LEN, out, gmap, db.tb_stats, soft);
+    if (maps_done == 2) viterbi3_traceback_check<TBC_NM>(dec, P1_LEN, out, gmap, db.tb_stats, soft);
     else viterbi3_traceback_block(dec, P1_LEN, st.p1_endlane[parity], out, gmap, smem, maps_done != 0);
     __threadfence_block();
     __syncthreads();
@@ -252,7 +266,8 @@ void launch_p1_traceback(const DevTables &tb, const DevBuffers &db, int nstreams
         const int nparts = vit3_tb2_waves(P1_LEN), ntasks = nparts * nstreams;
         const int grid = walk > 1 ? (walk < ntasks ? walk : ntasks) : ntasks;
         hipLaunchKernelGGL(k_p1_tbwalk, dim3(grid), dim3(64), 0, st, tb, db, stream_ids, parity, lane_id, prio_tb, nparts, ntasks);
-        hipLaunchKernelGGL(k_p1_traceback, dim3(nstreams), dim3(TB_THREADS), traceback_smem(P1_LEN), st, tb, db, stream_ids, parity, lane_id, l2_mode, prio_tb, 2);
+        // check mode: no dynamic LDS (the segment tables belong to the block-parallel traceback alone)
+        hipLaunchKernelGGL(k_p1_traceback, dim3(nstreams), dim3(TBC_THREADS), 0, st, tb, db, stream_ids, parity, lane_id, l2_mode, prio_tb, 2);
     } else {
         const int split = parts >= 16 ? 16 : 0;
         if (split) hipLaunchKernelGGL(k_p1_tbmap, dim3(split, nstreams), dim3(64 * TBM_WAVES), 0, st, tb, db, stream_ids, parity, lane_id, prio_tb, split);

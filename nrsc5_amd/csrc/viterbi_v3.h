@@ -470,20 +470,23 @@ __device__ inline void viterbi3_traceback_block(uint32_t *dec, int len, int endl
 // the true end lane.  viterbi3_traceback_check verifies that chain for every chunk at once and re-walks what fails, round by round
 // until nothing does -- worst case the sequential cost, result always the sequential decoder's.
 // One wave per 64 chunks; the history words of its 65 chunks (33 KB) are staged in LDS, each chunk's row rotated by the chunk's
-// phase so that the bit a step rewrites is the same lane bit (step % 6) for every lane of the wave.
+// phase so that the bit a step rewrites is the same lane bit (step % 6) for every lane of the wave.  The wave's time is the staging's
+// round trips to memory (four bursts of 16-byte loads), the walk's 128 dependent LDS reads, and the re-encode count of its chunks
+// (bit-parallel per lane against received bits that the staging transposed with ballots): see viterbi3_traceback_walk.
 constexpr int TB2_CHUNKS = 64;
 constexpr int TB2_LDS_WORDS = (TB2_CHUNKS + 1) * 128;
 __device__ __host__ inline int vit3_tb2_waves(int len) { return ((len / 64 + 1) + TB2_CHUNKS - 1) / TB2_CHUNKS; }
 // per frame: entry lane [nchunks] then exit lane [nchunks] of every chunk's walk (logical lane numbers)
 __device__ __host__ inline size_t vit3_tb2_meta_bytes(int len) { return (size_t)3 * (len / 64 + 1); }   // + the chunk's re-encode disagreements
 
-// 64 steps back through one chunk whose rows lie in LDS in rotated order (row word h of rotated lane q at rows[64 h + q]);
-// q = rotated lane at the chunk's last step on entry, at its first step on return; ahi / alo: decisions of steps 32..63 / 0..31
-__device__ __forceinline__ void vit3_walk_rotated(const uint32_t *rows, unsigned &q, unsigned &ahi, unsigned &alo)
+// steps S0 .. 0 back through one chunk whose rows lie in LDS in rotated order (row word h of rotated lane q at rows[64 h + q]);
+// q = rotated lane at step S0 on entry, at the chunk's first step on return; ahi / alo: decisions of steps 32..63 / 0..31
+template <int S0>
+__device__ __forceinline__ void vit3_walk_rotated_from(const uint32_t *rows, unsigned &q, unsigned &ahi, unsigned &alo)
 {
     ahi = 0; alo = 0;
 #pragma unroll
-    for (int S = 63; S >= 0; S--) {
+    for (int S = S0; S >= 0; S--) {
         const int u = S % 6;                                   // the lane bit this step rewrites, in the rotated numbering
         const unsigned v = rows[(S >= 32 ? 64 : 0) + q];
         const unsigned d = (v >> (S & 31)) & 1u;
@@ -491,6 +494,8 @@ __device__ __forceinline__ void vit3_walk_rotated(const uint32_t *rows, unsigned
         q = (q & ~(1u << u)) | (d << u);
     }
 }
+// the whole chunk: q = rotated lane at the chunk's last step on entry
+__device__ __forceinline__ void vit3_walk_rotated(const uint32_t *rows, unsigned &q, unsigned &ahi, unsigned &alo) { vit3_walk_rotated_from<63>(rows, q, ahi, alo); }
 
 // the two output words of a chunk from its 64 decisions and the ROTATED lane it was entered with (see vit3_outputs: the last six
 // bits are lane bits (PH + 58 + k) % 6 = rotated bits (58 + k) % 6)
@@ -533,43 +538,142 @@ __device__ __forceinline__ unsigned vit3_prev6(int c, unsigned exit_lane)
     return v;
 }
 
+// The re-encoded bits of ONE chunk for all its 64 steps at once (the owning lane's share of the wave-wide count below): bit S of enc[g] =
+// parity(window of step S & generator g), the window as in vit3_chunk_errors = bits S .. S + 6 of the 70-bit string prev6 | olo << 6 |
+// ohi << 38; so enc[g] = XOR over the generator's taps j of (string >> j).  0133 = taps 0 1 3 4 6, 0171 = 0 3 4 5 6, 0165 = 0 2 4 5 6.
+__device__ __forceinline__ void vit3_chunk_encode(unsigned prev6, unsigned olo, unsigned ohi, unsigned long long enc[3])
+{
+    const unsigned long long wlo = (unsigned long long)prev6 | ((unsigned long long)olo << 6) | ((unsigned long long)ohi << 38);
+    const unsigned long long whi = ohi >> 26;
+    unsigned long long sh[7];
+    sh[0] = wlo;
+#pragma unroll
+    for (int j = 1; j < 7; j++) sh[j] = (wlo >> j) | (whi << (64 - j));
+    const unsigned long long common = sh[0] ^ sh[4] ^ sh[6];
+    enc[0] = common ^ sh[1] ^ sh[3];
+    enc[1] = common ^ sh[3] ^ sh[5];
+    enc[2] = common ^ sh[2] ^ sh[5];
+}
+// run-in of the speculative walk: 64 = all of chunk c + 1 (9 constraint lengths), 32 = its steps 31 .. 0 only (a quarter fewer dependent LDS
+// reads, more chunks for the check to re-walk: -DNRSC5HIP_TB2_RUNIN=32 builds it for an A/B run).  The result is the same either way.
+#ifndef NRSC5HIP_TB2_RUNIN
+#define NRSC5HIP_TB2_RUNIN 64
+#endif
+constexpr int TB2_RUNIN = NRSC5HIP_TB2_RUNIN;
+static_assert(TB2_RUNIN == 64 || TB2_RUNIN == 32, "run-in: a whole chunk or its lower history word");
+// staging in TB2_SLICES round trips to memory: per slice TB2_SLICE_V4 16-byte loads per lane of history words + TB2_SLICE_CHUNKS soft words
+constexpr int TB2_SLICES = 4, TB2_SLICE_V4 = 9, TB2_SLICE_CHUNKS = TB2_CHUNKS / TB2_SLICES;
+static_assert(TB2_SLICES * TB2_SLICE_V4 * 64 * 4 >= TB2_LDS_WORDS && TB2_SLICES * TB2_SLICE_CHUNKS == TB2_CHUNKS, "the slices cover the tile");
+
+// diagnostic build only (-DNRSC5HIP_TBWALK_PHASES, tools/gpu_tbwalk_phases.py): shader cycles of the wave between the marks, summed over all
+// waves in phase_cycles[i] (staging + received signs / run-in + walk / re-encode count); the release kernel carries none of this
+#ifdef NRSC5HIP_TBWALK_PHASES
+#define TB2_MARK_BEGIN long long tb2_t0 = (long long)clock64()
+#define TB2_MARK(i) do { __builtin_amdgcn_s_waitcnt(0); if (phase_cycles && (threadIdx.x & 63) == 0) { const long long now = (long long)clock64(); \
+    atomicAdd((unsigned long long *)&phase_cycles[i], (unsigned long long)(now - tb2_t0)); tb2_t0 = now; } } while (0)
+#else
+#define TB2_MARK_BEGIN do { } while (0)
+#define TB2_MARK(i) do { } while (0)
+#endif
+
 // one wave: chunks [64 w, 64 w + 64) of a frame.  lds: TB2_LDS_WORDS dwords.  endlane: the frame's true end lane (logical).
-// soft (may be null): the frame's trellis inputs -- each lane then also files the re-encode disagreements of its chunk (meta[2 n + c])
-__device__ __forceinline__ void viterbi3_traceback_walk(const uint32_t *dec, int len, int endlane, uint32_t *out, uint8_t *meta, int w, uint32_t *lds, const int *soft = nullptr)
+// soft (may be null): the frame's trellis inputs -- the wave then also files the re-encode disagreements of its chunks (meta[2 n + c])
+// Three phases; every lane of the wave takes part in the first:
+//   1  staging, TB2_SLICES round trips to memory.  The tile is one contiguous run of history words: per slice every lane fetches TB2_SLICE_V4
+//      16-byte pieces of it and, with soft, its soft word of TB2_SLICE_CHUNKS chunks (lane S holds step S: one coalesced 256-byte load per
+//      chunk), all in ONE burst -- nothing is waited for before all of them are in flight.  Then it files the four words of each piece under
+//      their rotated lane numbers, and the received signs are transposed: per chunk the signs of the three soft values become three 64-bit
+//      ballots (bit S = step S), parked in the lane that owns the chunk -- at the end every lane holds the received bits of ITS chunk in six
+//      registers.  (Slices, not the whole tile at once: that would be ~200 live VGPRs, and the block-step kernels share this SIMD.)
+//   2  the walk: lane j owns chunk c0 + j (run-in, own 64 steps, outputs, entry / exit lane)
+//   3  the count, per lane and bit-parallel: re-encode the chunk (vit3_chunk_encode), XOR with the received bits, mask, popcount.
+//      (vit3_chunk_errors, which the repair path still uses, fetches a chunk's soft words in ONE lane: as part of the walk every load of the
+//      wave touched 64 cache lines, and the 64 steps cost ~25 VALU each.)
+__device__ __forceinline__ void viterbi3_traceback_walk(const uint32_t *dec, int len, int endlane, uint32_t *out, uint8_t *meta, int w, uint32_t *lds, const int *soft = nullptr, long long *phase_cycles = nullptr)
 {
     const int lane = threadIdx.x & 63;
     const int nchunks = len / 64 + 1;
     const int c0 = w * TB2_CHUNKS, nrows = min(TB2_CHUNKS + 1, nchunks - c0);   // chunks staged: own + the run-in chunk of the last lane
-    // stage: history word h of logical lane L of chunk c0 + k -> lds[128 k + 64 h + rotr6(L, ph)], ph = phase of the chunk's first step
-    for (int i = lane; i < nrows * 128; i += 64) {
-        const int k = i >> 7, h = (i >> 6) & 1, L = i & 63;
-        const int ph = (4 * ((c0 + k) % 3)) % 6;               // (64 c) % 6
-        lds[128 * k + 64 * h + (int)rotr6((unsigned)L, ph)] = dec[(size_t)(2 * (c0 + k) + h) * 64 + L];
+    TB2_MARK_BEGIN;
+    // stage: history word h of logical lane L of chunk c0 + k -> lds[128 k + 64 h + rotr6(L, ph)], ph = phase of the chunk's first step.
+    // Piece i4 of the tile = dwords 4 i4 .. 4 i4 + 3 = chunk i4 >> 5, row i4 >> 4, logical lanes 4 (i4 & 15) .. + 3.
+    const uint4 *src = reinterpret_cast<const uint4 *>(dec + (size_t)128 * c0);
+    const int nv = nrows * 32;
+    int m3 = (c0 + (lane >> 5)) % 3;                           // (chunk of piece j) % 3: the chunk is c0 + (lane >> 5) + 2 j
+    int rx[6] = {0, 0, 0, 0, 0, 0};                            // received bits of this lane's chunk: generator g in rx[2 g] (steps 0..31), rx[2 g + 1]
+#pragma unroll 1
+    for (int sl = 0; sl < TB2_SLICES; sl++) {
+        uint4 piece[TB2_SLICE_V4];
+        int sw[TB2_SLICE_CHUNKS];
+#pragma unroll
+        for (int jj = 0; jj < TB2_SLICE_V4; jj++) piece[jj] = src[min(lane + 64 * (TB2_SLICE_V4 * sl + jj), nv - 1)];   // (no branch: pieces past the tile are not filed)
+        if (soft) {
+#pragma unroll
+            for (int kk = 0; kk < TB2_SLICE_CHUNKS; kk++)      // step `lane` of chunk c0 + k (clamped: masked in the count)
+                sw[kk] = soft[min(max(64 * (c0 + TB2_SLICE_CHUNKS * sl + kk) + lane - VIT_EXTRA, 0), len - 1)];
+        }
+#pragma unroll
+        for (int jj = 0; jj < TB2_SLICE_V4; jj++) {
+            const int i4 = lane + 64 * (TB2_SLICE_V4 * sl + jj);
+            const int ph = m3 == 0 ? 0 : m3 == 1 ? 4 : 2;      // (64 c) % 6
+            m3 = m3 == 0 ? 2 : m3 - 1;                         // + 2 mod 3
+            if (i4 < nv) {
+                uint32_t *row = lds + 64 * (i4 >> 4);
+                const unsigned L = 4u * (unsigned)(i4 & 15);
+                row[(((L + 0) >> ph) | ((L + 0) << (6 - ph))) & 63u] = piece[jj].x;
+                row[(((L + 1) >> ph) | ((L + 1) << (6 - ph))) & 63u] = piece[jj].y;
+                row[(((L + 2) >> ph) | ((L + 2) << (6 - ph))) & 63u] = piece[jj].z;
+                row[(((L + 3) >> ph) | ((L + 3) << (6 - ph))) & 63u] = piece[jj].w;
+            }
+        }
+        if (soft) {
+#pragma unroll
+            for (int kk = 0; kk < TB2_SLICE_CHUNKS; kk++) {
+                const int k = TB2_SLICE_CHUNKS * sl + kk, v = sw[kk];
+                const unsigned long long b0 = __ballot((int8_t)v > 0), b1 = __ballot((int8_t)(v >> 8) > 0), b2 = __ballot((int8_t)(v >> 16) > 0);
+                rx[0] = wave_writelane(rx[0], (int)(unsigned)b0, k); rx[1] = wave_writelane(rx[1], (int)(unsigned)(b0 >> 32), k);
+                rx[2] = wave_writelane(rx[2], (int)(unsigned)b1, k); rx[3] = wave_writelane(rx[3], (int)(unsigned)(b1 >> 32), k);
+                rx[4] = wave_writelane(rx[4], (int)(unsigned)b2, k); rx[5] = wave_writelane(rx[5], (int)(unsigned)(b2 >> 32), k);
+            }
+        }
     }
     WAVE_LDS_SYNC();
+    TB2_MARK(0);
     const int c = c0 + lane;
-    if (c >= nchunks) return;
+    const bool own = c < nchunks;
     const int ph = (4 * (c % 3)) % 6;
-    unsigned q, ahi, alo;
-    if (c == nchunks - 1) {
-        q = rotr6((unsigned)endlane, ph);
-    } else {
-        // run-in through chunk c + 1 from (rotated) lane 0 at its last step; its first step's lane is where chunk c ends.
-        // rotated numbering of chunk c = that of chunk c + 1 rotated left by 4 (ph(c + 1) - ph(c) = 4 mod 6)
-        unsigned qa = 0, t0, t1;
-        vit3_walk_rotated(lds + 128 * (lane + 1), qa, t0, t1);
-        q = rotl6(qa, 4);
+    unsigned ohi = 0, olo = 0, lexit = 0;
+    if (own) {
+        unsigned q, ahi, alo;
+        if (c == nchunks - 1) {
+            q = rotr6((unsigned)endlane, ph);
+        } else {
+            // run-in through chunk c + 1 from (rotated) lane 0; its first step's lane is where chunk c ends.
+            // rotated numbering of chunk c = that of chunk c + 1 rotated left by 4 (ph(c + 1) - ph(c) = 4 mod 6)
+            unsigned qa = 0, t0, t1;
+            vit3_walk_rotated_from<TB2_RUNIN - 1>(lds + 128 * (lane + 1), qa, t0, t1);
+            q = rotl6(qa, 4);
+        }
+        const unsigned qend = q;
+        vit3_walk_rotated(lds + 128 * lane, q, ahi, alo);
+        vit3_outputs_rotated(qend, ahi, alo, ohi, olo);
+        if (c < nchunks - 1) out[2 * c] = ohi;                 // steps 64c+32 .. 64c+63
+        if (c >= 1) out[2 * c - 1] = olo;                      // steps 64c .. 64c+31
+        meta[c] = (uint8_t)rotl6(qend, ph);                    // entered with (logical lane at the chunk's last step)
+        lexit = rotl6(q, ph);
+        meta[nchunks + c] = (uint8_t)lexit;                    // left with (logical lane at its first step)
     }
-    const unsigned qend = q;
-    vit3_walk_rotated(lds + 128 * lane, q, ahi, alo);
-    unsigned ohi, olo;
-    vit3_outputs_rotated(qend, ahi, alo, ohi, olo);
-    if (c < nchunks - 1) out[2 * c] = ohi;                     // steps 64c+32 .. 64c+63
-    if (c >= 1) out[2 * c - 1] = olo;                          // steps 64c .. 64c+31
-    meta[c] = (uint8_t)rotl6(qend, ph);                        // entered with (logical lane at the chunk's last step)
-    const unsigned lexit = rotl6(q, ph);
-    meta[nchunks + c] = (uint8_t)lexit;                        // left with (logical lane at its first step)
-    if (soft) meta[2 * nchunks + c] = (uint8_t)vit3_chunk_errors(soft, len, c, vit3_prev6(c, lexit), olo, ohi);
+    TB2_MARK(1);
+    if (soft && own) {
+        // frame bit i = 64 c + S - 32 counts iff 6 <= i < len (bits 0..5: the caller), its third soft value iff i is even: [1,1,1,1,1,0]
+        const unsigned long long valid = (c == 0 ? ~0ull << (VIT_EXTRA + 6) : ~0ull) & (c == nchunks - 1 ? (1ull << VIT_EXTRA) - 1 : ~0ull);
+        unsigned long long enc[3];
+        vit3_chunk_encode(vit3_prev6(c, lexit), olo, ohi, enc);
+        const unsigned long long r0 = (unsigned)rx[0] | ((unsigned long long)(unsigned)rx[1] << 32), r1 = (unsigned)rx[2] | ((unsigned long long)(unsigned)rx[3] << 32),
+                                 r2 = (unsigned)rx[4] | ((unsigned long long)(unsigned)rx[5] << 32);
+        meta[2 * nchunks + c] = (uint8_t)(__popcll((r0 ^ enc[0]) & valid) + __popcll((r1 ^ enc[1]) & valid) + __popcll((r2 ^ enc[2]) & valid & 0x5555555555555555ull));
+    }
+    TB2_MARK(2);
 }
 
 // one chunk walked from logical lane `e`, history words straight from global memory (the repair path)
@@ -593,6 +697,8 @@ __device__ inline unsigned vit3_rewalk(const uint32_t *dec, int c, unsigned e, u
 
 // whole workgroup, after every wave of viterbi3_traceback_walk of the frame is done (a later launch): verify the chain of chunk
 // boundaries and re-walk what the speculation got wrong.  stats (may be null): [0] boundaries checked, [1] chunks re-walked.
+// NM: wrong chunks a thread can take on per round, >= ceil(chunks / blockDim.x) so that every round repairs all it finds.
+template <int NM = 4>
 __device__ inline void viterbi3_traceback_check(const uint32_t *dec, int len, uint32_t *out, uint8_t *meta, int *stats, const int *soft = nullptr)
 {
     const int nchunks = len / 64 + 1;
@@ -602,10 +708,10 @@ __device__ inline void viterbi3_traceback_check(const uint32_t *dec, int len, ui
         if (threadIdx.x == 0) tb2_bad = 0;
         __syncthreads();
         // phase A: who entered with the wrong lane?  (reads only)
-        int mine[4]; unsigned want[4]; int nm = 0;
+        int mine[NM]; unsigned want[NM]; int nm = 0;
         for (int c = threadIdx.x; c < nchunks - 1; c += blockDim.x) {
             const unsigned w = meta[nchunks + c + 1];
-            if (meta[c] != w && nm < 4) { mine[nm] = c; want[nm] = w; nm++; }
+            if (meta[c] != w && nm < NM) { mine[nm] = c; want[nm] = w; nm++; }
         }
         if (nm) tb2_bad = 1;
         __syncthreads();
