@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 10   /* 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 11   /* 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -395,6 +395,24 @@ int nrsc5hip_hdc_frame_reset(nrsc5hip_hdc *h, int stream);
 int nrsc5hip_hdc_advance(nrsc5hip_hdc *h, int stream, int mode /* NRSC5HIP_MODE_FM | _AM */, nrsc5hip_hdc_cb cb, void *opaque);
 size_t nrsc5hip_hdc_adts(const uint8_t *data, unsigned count, uint8_t *out);
 size_t nrsc5hip_hdc_host_bytes(const nrsc5hip_hdc *h);                /* host memory held by the consumer */
+/* Replays block records of `nstreams` engine streams into the consumer, stream by stream, in the reference's order:
+ * output_advance at the top of every processed block, the frame reset on a transition to fine sync, then every logical frame the
+ * block delivers (FM: P1, P3, P4; AM: the P1 PDUs and P3), each through frame_process's path (nrsc5hip_hdc_push_frame).  ONE L2
+ * index launch and one copy for all frames of the call.  targets[i] is the consumer's stream for stream_ids[i] (NULL: the same
+ * ids).  records[i] / counts[i]: the records of stream_ids[i] as nrsc5hip_drain / _batch_fetch delivered them, in order; a session
+ * may be fed in as many calls as it likes.  Must be called while the frame ring slots the records name still hold their frames (the
+ * contract of nrsc5hip_p1_frame_bits).  A loss of sync (NRSC5HIP_REC_LOST_SYNC) changes nothing in the consumer, as it changes
+ * nothing in the reference's output_t: packets already pushed keep coming out, block by block, while the stream re-acquires.
+ * Packets are delivered through cb (may be NULL: count only) inside the call, all of stream_ids[0] first, then stream_ids[1], ...;
+ * returns the number of packets delivered or a negative error.  nstreams == 0 or all counts zero: 0, nothing delivered.  Ids out
+ * of range (engine or consumer), a NULL records[i] with counts[i] > 0 and a mode that is neither FM nor AM are NRSC5HIP_EINVAL
+ * and leave the consumer untouched; so does a record that names a slot the engine does not have, or a failure of the index launch
+ * or its copy.  Behind that point the call is NOT atomic: the replay can still fail on a frame whose header expansion runs into the
+ * fixed-data region (nrsc5hip_hdc_push_frame's NRSC5HIP_EINVAL, see nrsc5hip_l2_apply_audio_end), and the call then returns that
+ * error with the records in front of the frame replayed and their packets already delivered through cb; the packet count is lost.
+ * Walk such a frame on the host, or nrsc5hip_hdc_reset the stream. */
+int nrsc5hip_hdc_feed(nrsc5hip_hdc *h, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
+                      const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_hdc_cb cb, void *opaque);
 
 /* ---- stage-level entry points (host buffers): parity tests of single kernels against the oracle ---- */
 int nrsc5hip_stage_halfband_fm_cu8(nrsc5hip_engine *e, const uint8_t *iq, uint32_t nbytes, int16_t *out /* [nbytes/4][2] */);

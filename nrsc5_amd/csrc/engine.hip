@@ -722,6 +722,9 @@ static int check_stream(nrsc5hip_engine *e, int s)
     return 0;
 }
 
+// nrsc5hip_hdc_feed (hdc_consumer.hip) checks its stream ids before it touches the consumer
+int nrsc5_engine_max_streams(const nrsc5hip_engine *e) { return e ? e->cfg.max_streams : 0; }
+
 // ---- block-step scheduler --------------------------------------------------------------------------
 // One step = every listed stream whose 33-symbol window is complete advances by one block:
 //   [acquisition kernels if any stream may be un-synchronised] -> prepare -> mix+FFT -> sync (+PIDS)

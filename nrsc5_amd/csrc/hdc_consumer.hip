@@ -1,11 +1,13 @@
 // Batch consumer of the L2 audio-transport index: turns nrsc5hip_l2_frame + PDU bytes into the reference's
 // NRSC5_EVENT_HDC stream for thousands of streams without one nrsc5_t (22.9 MB: output_t alone holds 8 x 2 elastic buffers of
-// 64 x 18 269 bytes, output.h:104-122) per stream.  Host code only -- no device work, no HIP calls.
+// 64 x 18 269 bytes, output.h:104-122) per stream.  Host code only -- no HIP calls; the one entry that needs the device,
+// nrsc5hip_hdc_feed, gets its index through nrsc5hip_l2_index.
 //
 //   frame_process's hand-off   output_align / output_push            frame.c:590-640, output.c:31-92   -> nrsc5hip_hdc_push_frame
 //   output_advance             pops 2 (FM) / 4 (AM) packets per program and block, NRSC5_EVENT_HDC for every complete one
 //                                                                   output.c:100-168, nrsc5.c:709-728 -> nrsc5hip_hdc_advance
 //   dump_hdc / write_adts_header (--dump-hdc)                        main.c:182-212                    -> nrsc5hip_hdc_adts
+//   the three above driven by block records, many streams per call   acquire.c:108, sync.c:405-409     -> nrsc5hip_hdc_feed
 //
 // State per stream: for every program that ever carried audio, 64 packet slots (size, flags, shape) whose payload buffers
 // only ever grow to the largest packet that passed through them -- ~40 KB per program at the usual 300-600 byte packets.
@@ -215,6 +217,94 @@ extern "C" int nrsc5hip_hdc_advance(nrsc5hip_hdc *h, int stream, int mode, nrsc5
                 pkt.size = 0; pkt.flags = 0; pkt.shape = SHAPE_NONE;                                    // pkt_reset
             }
             ao = (ao + 1) % ELASTIC_LEN;
+        }
+    }
+    return delivered;
+}
+
+int nrsc5_engine_max_streams(const nrsc5hip_engine *e);         // engine.hip
+
+namespace {
+
+constexpr uint32_t REC_PROCESSED = NRSC5HIP_REC_PROCESSED, REC_TO_FINE = NRSC5HIP_REC_TO_FINE, REC_P1 = NRSC5HIP_REC_P1, REC_P3 = NRSC5HIP_REC_P3,
+                   REC_P4 = NRSC5HIP_REC_P4;
+
+// the logical frames one record announces, in frame_push's order (decode.c:393-437, 507-554); -> how many; job / lc may be null (count only)
+int record_jobs(const nrsc5hip_record &r, int stream, int mode, nrsc5hip_l2_job *job, int *lc)
+{
+    int n = 0;
+    auto add = [&](int slot, int kind, int which, int nbits, int channel) {
+        if (job) { job[n] = nrsc5hip_l2_job{stream, slot, kind, which, nbits}; lc[n] = channel; }
+        n++;
+    };
+    if (mode == NRSC5HIP_MODE_AM) {
+        if (r.flags & REC_P1) add(r.p1_slot, NRSC5HIP_L2_AM, r.bc_decoded, 3750, 0);
+        if (r.flags & REC_P3) add(r.p1_slot, NRSC5HIP_L2_AM, 8, r.psmi == 2 ? 30000 : 24000, 1);
+    } else {
+        const int px_bits = r.psmi == 2 ? 2304 : 4608;
+        if (r.flags & REC_P1) add(r.p1_slot, NRSC5HIP_L2_FM_P1, 0, 146176, 0);
+        if (r.flags & REC_P3) add((int)r.sis, NRSC5HIP_L2_FM_PX, 0, px_bits, 1);
+        if (r.flags & REC_P4) add((int)r.sis, NRSC5HIP_L2_FM_PX, 1, px_bits, 2);
+    }
+    return n;
+}
+
+}  // namespace
+
+// A loss of sync needs nothing here: input_set_sync_state (input.c:172-188) only reports it.  The reference keeps its elastic buffers and
+// audio offsets (output_reset runs on nrsc5_set_mode and at start-up only, nrsc5.c:549, output.c:240-245) and output_advance goes on with
+// every block while the stream re-acquires (acquire.c:108 stands in front of the sync-state test), so packets pushed before the loss still
+// come out after it; the CCC state is cleared on the NEXT transition to fine sync (sync.c:405-409), which REC_TO_FINE carries.
+extern "C" int nrsc5hip_hdc_feed(nrsc5hip_hdc *h, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
+                                 const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_hdc_cb cb, void *opaque)
+{
+    if (!h || !e || nstreams < 0 || (mode != NRSC5HIP_MODE_FM && mode != NRSC5HIP_MODE_AM)) return NRSC5HIP_EINVAL;
+    if (nstreams == 0) return 0;
+    if (!stream_ids || !records || !counts) return NRSC5HIP_EINVAL;
+    const int engine_streams = nrsc5_engine_max_streams(e);
+    size_t njobs = 0;
+    int max_bits = 0;
+    for (int i = 0; i < nstreams; i++) {
+        const int t = targets ? targets[i] : stream_ids[i];
+        if (stream_ids[i] < 0 || stream_ids[i] >= engine_streams || t < 0 || t >= (int)h->streams.size()) return NRSC5HIP_EINVAL;
+        if (counts[i] < 0 || (counts[i] > 0 && !records[i])) return NRSC5HIP_EINVAL;
+        for (int k = 0; k < counts[i]; k++) njobs += (size_t)record_jobs(records[i][k], stream_ids[i], mode, nullptr, nullptr);
+    }
+    std::vector<nrsc5hip_l2_job> jobs;
+    std::vector<int> lcs;
+    std::vector<nrsc5hip_l2_frame> frames;
+    std::vector<uint8_t> bytes;
+    long long stride = 0;
+    if (njobs) {
+        if (njobs > (size_t)INT32_MAX) return NRSC5HIP_EINVAL;
+        try { jobs.resize(njobs); lcs.resize(njobs); frames.resize(njobs); } catch (...) { return NRSC5HIP_ENOMEM; }
+        size_t n = 0;
+        for (int i = 0; i < nstreams; i++)
+            for (int k = 0; k < counts[i]; k++) n += (size_t)record_jobs(records[i][k], stream_ids[i], mode, &jobs[n], &lcs[n]);
+        for (const nrsc5hip_l2_job &j : jobs) if (j.nbits > max_bits) max_bits = j.nbits;
+        stride = ((long long)max_bits / 8 + 15) & ~15LL;                   // >= the PDU bytes of the longest frame of this call (18272 with a P1 frame in it)
+        try { bytes.resize(njobs * (size_t)stride); } catch (...) { return NRSC5HIP_ENOMEM; }
+        // one launch, one copy back; it also checks every slot / channel / length the records name, before the consumer is touched
+        const int rc = nrsc5hip_l2_index(e, (int)njobs, jobs.data(), frames.data(), bytes.data(), stride);
+        if (rc) return rc;
+    }
+    int delivered = 0;
+    size_t next = 0;
+    for (int i = 0; i < nstreams; i++) {
+        const int t = targets ? targets[i] : stream_ids[i];
+        for (int k = 0; k < counts[i]; k++) {
+            const nrsc5hip_record &r = records[i][k];
+            if (r.flags & REC_PROCESSED) {                                                                 // acquire.c:108
+                const int n = nrsc5hip_hdc_advance(h, t, mode, cb, opaque);
+                if (n < 0) return n;
+                delivered += n;
+            }
+            if (r.flags & REC_TO_FINE) (void)nrsc5hip_hdc_frame_reset(h, t);                              // sync.c:405-409
+            const int nf = record_jobs(r, stream_ids[i], mode, nullptr, nullptr);
+            for (int f = 0; f < nf; f++, next++) {
+                const int rc = nrsc5hip_hdc_push_frame(h, t, lcs[next], &frames[next], bytes.data() + next * (size_t)stride);
+                if (rc) return rc;
+            }
         }
     }
     return delivered;

@@ -203,6 +203,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_hdc_adts.restype = ctypes.c_size_t
     lib.nrsc5hip_hdc_host_bytes.argtypes = [vp]
     lib.nrsc5hip_hdc_host_bytes.restype = ctypes.c_size_t
+    lib.nrsc5hip_hdc_feed.argtypes = [vp, vp, ci, vp, vp, vp, vp, ci, HDC_CB, vp]
     ll = ctypes.c_longlong
     lib.nrsc5hip_chan_create.argtypes = [ctypes.POINTER(_ChanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_chan_destroy.argtypes = [vp]
@@ -239,6 +240,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
     "nrsc5hip_hdc_create", "nrsc5hip_hdc_destroy", "nrsc5hip_hdc_reset", "nrsc5hip_hdc_push_frame", "nrsc5hip_hdc_advance",
     "nrsc5hip_hdc_adts", "nrsc5hip_hdc_host_bytes", "nrsc5hip_hdc_fixed_audio_end", "nrsc5hip_l2_apply_audio_end", "nrsc5hip_hdc_frame_reset",
+    "nrsc5hip_hdc_feed",
     "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
     "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed",
     "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",
@@ -903,6 +905,28 @@ def feed_hdc(engine: Engine, consumer: HdcConsumer, stream: int, recs: np.ndarra
             kind, which = jobs_all[k][2], jobs_all[k][3]
             lc = 0 if kind == L2_FM_P1 or (kind == L2_AM and which < 8) else (1 + which if kind == L2_FM_PX else 1)
             consumer.push_frame(t, frames[k], by[k, :frames[k].nbytes], lc)
+
+
+def feed_hdc_batch(engine: Engine, consumer: HdcConsumer, stream_ids, recs_per_stream, mode: int = MODE_FM, targets=None) -> int:
+    """nrsc5hip_hdc_feed: what feed_hdc does, for many streams in one native call -- one L2 index launch and one copy for all their
+    frames, no Python per record.  recs_per_stream[i]: the RECORD_DTYPE array of engine stream stream_ids[i] (drained since the last
+    call; may be empty); targets[i]: the consumer's stream for it (None: the same ids).  The packets land in consumer.events, all of
+    stream_ids[0] first; -> how many.  Call it while the ring slots the records name still hold their frames."""
+    ids = np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
+    tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    n = int(ids.size)
+    if len(recs_per_stream) != n or (tg is not None and tg.size != n):
+        raise ValueError("stream_ids, recs_per_stream and targets must have one entry per stream")
+    arrs = [None if r is None else np.ascontiguousarray(r, dtype=RECORD_DTYPE) for r in recs_per_stream]       # kept alive over the call
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None or a.size == 0 else a.ctypes.data for a in arrs])
+    counts = np.array([0 if a is None else a.size for a in arrs], dtype=np.int32)
+    rc = consumer.lib.nrsc5hip_hdc_feed(consumer._h, engine._h, n, ids.ctypes.data, None if tg is None else tg.ctypes.data, ptrs,
+                                        counts.ctypes.data, mode, consumer._cb, None)
+    if rc < 0:
+        err = Nrsc5HipError(f"nrsc5hip_hdc_feed failed ({rc}): {consumer.lib.nrsc5hip_last_error().decode()}")
+        err.code = rc
+        raise err
+    return rc
 
 
 def l2_jobs_from_records(stream: int, recs: np.ndarray, mode: int = 0):

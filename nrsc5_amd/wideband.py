@@ -4,7 +4,9 @@ and the batch engine decodes them (p1_async, l2_feedback).
     python -m nrsc5_amd.wideband FILE --format cs16 --rate 20000000 --offsets -800e3,0,400e3
     rtl_sdr -f 98.1e6 -s 2400000 - | python -m nrsc5_amd.wideband - --format cu8 --rate 2400000 --offsets -800e3,0,600e3
 
-prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  FILE may be `-` (standard input, read in
+prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  --dump-hdc DIR also records every station's
+audio programs (the reference's NRSC5_EVENT_HDC packets, as `nrsc5 --dump-hdc` frames them: ADTS) into
+DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.  FILE may be `-` (standard input, read in
 --chunk pieces until it ends; --offsets is then required): the session may be of any length, the receiver gives FIFO space back as it
 goes (nrsc5hip_batch_trim).  Without --offsets the stations are found
 first (scan(): the band scan nrsc5hip_scan_* nominates centres from the capture's power spectrum, a short decode confirms them):
@@ -33,9 +35,13 @@ class WidebandReceiver:
     position and of every replay checkpoint of l2_feedback whose verdict is still open).  The least capacity is
     eng.TRIM_RETAIN_MAX (9 195 120: the depth of the decode pipeline, include/nrsc5hip.h) + the outputs of the largest push
     (chan.outputs_for); the default carries any session at pushes of up to ~7.5 M outputs per station.  max_retained: the
-    largest span a trim has left in a station's FIFO so far; trims: how many pushes had to trim."""
+    largest span a trim has left in a station's FIFO so far; trims: how many pushes had to trim.
+    programs=True: the receiver also delivers every station's audio programs -- the reference's NRSC5_EVENT_HDC packets, in its order --
+    through an HdcConsumer of its own: after the drains of a push, one eng.feed_hdc_batch call (nrsc5hip_hdc_feed) over all stations'
+    new records; packets[s] collects (program, flags, bytes) and on_packet(station, program, flags, data), if given, sees each one."""
 
-    def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None):
+    def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
+                 programs: bool = False, on_packet=None):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -54,6 +60,22 @@ class WidebandReceiver:
         self.max_retained = 0
         self.pushes = 0
         self.trims = 0
+        self.programs = bool(programs)
+        self.on_packet = on_packet
+        self.packets = [[] for _ in range(self.k)]
+        self.hdc = eng.HdcConsumer(self.k, lib=self.engine.lib) if self.programs else None
+
+    def _feed_programs(self, fresh):
+        """fresh[s]: the records station s delivered in this push; their frames are still in the rings (nothing was processed since)"""
+        if not any(len(r) for r in fresh):
+            return
+        self.hdc.events.clear()
+        eng.feed_hdc_batch(self.engine, self.hdc, self.ids, fresh)
+        for s, program, count, flags, data in self.hdc.events:
+            self.packets[s].append((program, flags, data))
+            if self.on_packet is not None:
+                self.on_packet(s, program, flags, data)
+        self.hdc.events.clear()
 
     def push(self, chunk) -> list:
         """-> the events this push produced: [(station, kind, fields), ...] in stream order per station"""
@@ -74,19 +96,25 @@ class WidebandReceiver:
         self.pushes += 1
         self.engine.batch_process(self.k, stream_ids=self.ids)
         new = []
+        fresh = [None] * self.k
         for s in range(self.k):
             recs = self.engine.drain(s)
+            fresh[s] = recs
             if len(recs):
                 log = eng.records_to_log(self.engine, s, recs)          # frames are fetched now, while their ring slots hold them
                 self.logs[s] += log
                 self.records[s].append(recs)
                 new += [(s, kind, v) for kind, v in log]
+        if self.programs:
+            self._feed_programs(fresh)
         return new
 
     def station_records(self, s: int) -> np.ndarray:
         return np.concatenate(self.records[s]) if self.records[s] else np.zeros(0, dtype=eng.RECORD_DTYPE)
 
     def close(self):
+        if self.hdc is not None:
+            self.hdc.close()
         self.engine.close()
         self.chan.close()
 
@@ -209,6 +237,44 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
     return None
 
 
+class HdcDump:
+    """--dump-hdc: one ADTS file per station and program, opened on the first packet that carries data.  A packet without data
+    (one that failed its CRC) would be a 7-byte header with no frame behind it: it is left out of the file and of the counts.  adts: the framing function (HdcConsumer.adts: nrsc5hip_hdc_adts)."""
+
+    def __init__(self, directory: str, offsets_hz, adts):
+        import os
+        os.makedirs(directory, exist_ok=True)
+        self.dir, self.offsets, self.adts = directory, [float(f) for f in offsets_hz], adts
+        self.files = {}                  # (station, program) -> [file, packets, bytes]
+
+    def path(self, station: int, program: int) -> str:
+        import os
+        return os.path.join(self.dir, f"station{station}_{int(round(self.offsets[station])):+d}_p{program}.aac")
+
+    def write(self, station: int, program: int, flags: int, data: bytes):
+        if not data:
+            return
+        ent = self.files.get((station, program))
+        if ent is None:
+            ent = self.files[(station, program)] = [open(self.path(station, program), "wb"), 0, 0]
+        frame = self.adts(data)
+        ent[0].write(frame)
+        ent[1] += 1
+        ent[2] += len(frame)
+
+    def flush(self):
+        for ent in self.files.values():
+            ent[0].flush()
+
+    def close(self) -> list:
+        """-> the summary lines, by station and program"""
+        lines = []
+        for (s, p), (f, n, nbytes) in sorted(self.files.items()):
+            f.close()
+            lines.append(f"station {s} ({self.offsets[s] / 1e3:+.1f} kHz): program {p} packets {n} bytes {nbytes}")
+        return lines
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nrsc5_amd.wideband", description=__doc__.splitlines()[0])
     ap.add_argument("file", help="capture file, or - for standard input (needs --offsets)")
@@ -224,6 +290,8 @@ def main(argv=None) -> int:
     ap.add_argument("--chunk", type=int, default=1 << 22, help="samples per push")
     ap.add_argument("--q15-capacity", type=int, default=1 << 24,
                     help="decimated samples of FIFO per station: at least %d + the outputs of one push, whatever the length of the session" % eng.TRIM_RETAIN_MAX)
+    ap.add_argument("--dump-hdc", metavar="DIR", default=None,
+                    help="write every station's audio programs as ADTS: DIR/station<k>_<offset in Hz>_p<program>.aac")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                  # "--offsets -800e3,0,400e3": a value that starts with '-' is still the value
         if argv[i] == "--offsets":
@@ -256,7 +324,11 @@ def main(argv=None) -> int:
                     print("no station found", file=sys.stderr)
                     return 1
         del head
-    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity)
+    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None)
+    dump = None
+    if a.dump_hdc is not None:
+        dump = HdcDump(a.dump_hdc, offsets, rx.hdc.adts)
+        rx.on_packet = dump.write
     item = 2 * np.dtype(dtype).itemsize
     with (sys.stdin.buffer if stdin else open(a.file, "rb")) as f:
         while True:
@@ -268,6 +340,13 @@ def main(argv=None) -> int:
                 line = format_event(rx, s, kind, v)
                 if line:
                     print(line, flush=True)
+            if dump is not None:
+                dump.flush()
+                for kept in rx.packets:                        # written: a session of any length must not keep its audio in memory
+                    kept.clear()
+    if dump is not None:
+        for line in dump.close():
+            print(line, flush=True)
     rx.close()
     return 0
 
