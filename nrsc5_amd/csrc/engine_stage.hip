@@ -1,0 +1,447 @@
+// Test hooks and micro-benchmarks: every nrsc5hip_stage_* and nrsc5hip_debug_* entry point (single kernels on caller data, peeks at
+// device state, counters) and the tuning knobs (nrsc5hip_debug_tune).  Nothing here runs in a production pass.
+#include <algorithm>
+#include "engine_internal.h"
+
+extern "C" void nrsc5hip_debug_seam_totals(double out[8], int reset)
+{
+    for (int k = 0; k < 8; k++) { if (out) out[k] = g_seam[k]; if (reset) g_seam[k] = 0; }
+}
+extern "C" void nrsc5hip_debug_seam_counts(double out[6], int reset)
+{
+    for (int k = 0; k < 6; k++) { if (out) out[k] = g_seam[8 + k]; if (reset) g_seam[8 + k] = 0; }
+}
+
+extern "C" int nrsc5hip_stage_l2_index(nrsc5hip_engine *e, const uint8_t *bits, int nbits, int nframes, nrsc5hip_l2_frame *out, uint8_t *pdu_bytes, long long stride)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !bits || !out || nbits < 1 || nframes < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    const int words = (nbits + 31) / 32;
+    std::vector<uint32_t> w((size_t)words * nframes, 0u);
+    for (int f = 0; f < nframes; f++)
+        for (int i = 0; i < nbits; i++) w[(size_t)f * words + (i >> 5)] |= (uint32_t)(bits[(size_t)f * nbits + i] & 1u) << (i & 31);
+    DevTmp tw;
+    HIPCHK(hipMalloc(&tw.p, w.size() * sizeof(uint32_t)));
+    uint32_t *dw = (uint32_t *)tw.p;
+    HIPCHK(hipMemcpy(dw, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    std::vector<L2Job> dj((size_t)nframes);
+    for (int f = 0; f < nframes; f++) dj[f] = L2Job{dw + (size_t)f * words, nbits, 0};
+    return l2_run(e, dj, out, pdu_bytes, stride);
+}
+
+extern "C" int nrsc5hip_stage_first_header(nrsc5hip_engine *e, const uint8_t *bits, int nbits, int nframes, int threads, int *ok)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !bits || !ok || nframes < 1 || (nbits != P1_LEN && nbits != AM_P1_LEN) || threads < 64 || threads > 1024 || (threads & 63)) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    const int words = (nbits + 31) / 32;
+    std::vector<uint32_t> w((size_t)nframes * words, 0u);
+    for (int f = 0; f < nframes; f++)
+        for (int i = 0; i < nbits; i++) if (bits[(size_t)f * nbits + i] & 1) w[(size_t)f * words + (i >> 5)] |= 1u << (i & 31);
+    uint32_t *dw = nullptr; int *dok = nullptr;
+    HIPCHK(hipMalloc((void **)&dw, w.size() * sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&dok, (size_t)nframes * sizeof(int)));
+    HIPCHK(hipMemcpy(dw, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    launch_stage_first_header(dw, words, nframes, nbits == AM_P1_LEN ? 1 : 0, threads, dok, e->main);
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(ok, dok, (size_t)nframes * sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(dw); (void)hipFree(dok);
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_viterbi_k9(nrsc5hip_engine *e, const int8_t *soft, int len, int nframes, const unsigned gens[3], uint8_t *bits)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !soft || !bits || !gens || len < 64 || nframes < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    int8_t *dsoft = nullptr; unsigned long long *ddec = nullptr; uint32_t *dout = nullptr;
+    const int words = (len + 31) / 32;
+    HIPCHK(hipMalloc((void **)&dsoft, (size_t)nframes * 3 * len));
+    HIPCHK(hipMalloc((void **)&ddec, (size_t)nframes * 4 * (len + 64) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void **)&dout, (size_t)nframes * words * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(dsoft, soft, (size_t)nframes * 3 * len, hipMemcpyHostToDevice));
+    K9Meta *dmeta = nullptr;                                   // segment waves (the window pipeline's form) unless tuned down to one
+    if (e->am_segments > 1 && len > 80) HIPCHK(hipMalloc((void **)&dmeta, (size_t)nframes * sizeof(K9Meta)));
+    launch_viterbi_k9_frames(dsoft, len, nframes, gens[0], gens[1], gens[2], ddec, dout, e->main, 3, dmeta, e->am_segments, e->am_warm, e->am_runin, e->db.am_k9stats);
+    HIPCHK(hipStreamSynchronize(e->main));
+    if (dmeta) (void)hipFree(dmeta);
+    std::vector<uint32_t> w((size_t)nframes * words);
+    HIPCHK(hipMemcpy(w.data(), dout, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int f = 0; f < nframes; f++) nrsc5hip_unpack_bits(w.data() + (size_t)f * words, len, bits + (size_t)f * len);
+    (void)hipFree(dsoft); (void)hipFree(ddec); (void)hipFree(dout);
+    return 0;
+}
+
+// ---- stage-level entry points ----------------------------------------------------------------------------------------
+extern "C" int nrsc5hip_stage_halfband_fm_cu8(nrsc5hip_engine *e, const uint8_t *iq, uint32_t nbytes, int16_t *out)
+{
+    ON_ENGINE_DEVICE(e);
+    // runs the production K1 kernel on stream 0 of a scratch state: requires a freshly reset stream 0
+    int rc = check_stream(e, 0); if (rc) return rc;
+    if (nbytes % 4 || nbytes > e->stage_bytes || nbytes / 4 > e->db.q15_cap) FAIL(NRSC5HIP_EINVAL, "bad length");
+    if ((rc = nrsc5hip_stream_fresh(e, 0))) return rc;
+    const int s = 0; const unsigned count = nbytes;
+    HIPCHK(hipMemcpy(e->stage_dev, iq, nbytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->ids_dev, &s, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->nbytes_dev, &count, sizeof(unsigned), hipMemcpyHostToDevice));
+    launch_decimate_fm_cu8(e->tb, e->db, 1, e->ids_dev, e->stage_dev, 0, e->nbytes_dev, count, e->main);
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(out, e->db.q15, (size_t)(nbytes / 4) * sizeof(c16), hipMemcpyDeviceToHost));
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_stage_fft2048(nrsc5hip_engine *e, const float *in, float *out, int n)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !in || !out || n < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    float2 *din = nullptr, *dout = nullptr;
+    const size_t bytes = (size_t)n * FFT_N * sizeof(float2);
+    HIPCHK(hipMalloc((void **)&din, bytes));
+    HIPCHK(hipMalloc((void **)&dout, bytes));
+    HIPCHK(hipMemcpy(din, in, bytes, hipMemcpyHostToDevice));
+    launch_fft2048(e->tb, din, dout, n, e->main, e->mixfft_syms);
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    (void)hipFree(din); (void)hipFree(dout);
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_viterbi_k7(nrsc5hip_engine *e, const int8_t *soft, int len, int nframes, uint8_t *bits)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !soft || !bits || len < 64 || nframes < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    int8_t *dsoft = nullptr; unsigned long long *ddec = nullptr; uint32_t *dout = nullptr;
+    const int words = (len + 31) / 32;
+    HIPCHK(hipMalloc((void **)&dsoft, (size_t)nframes * 3 * len));
+    HIPCHK(hipMalloc((void **)&ddec, (size_t)nframes * (len + 64) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void **)&dout, (size_t)nframes * words * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(dsoft, soft, (size_t)nframes * 3 * len, hipMemcpyHostToDevice));
+    if (launch_viterbi_frames(e->vit_scratch, dsoft, len, nframes, ddec, dout, e->main, 3 | (e->tb_walk ? 0 : 16), e->fwd_segments > 0 ? e->fwd_segments : 16, e->db.fwd_stats, e->fwd_warm)) FAIL(NRSC5HIP_EINVAL, "frame length %d not supported or out of device memory", len);
+    HIPCHK(hipStreamSynchronize(e->main));
+    std::vector<uint32_t> w((size_t)nframes * words);
+    HIPCHK(hipMemcpy(w.data(), dout, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int f = 0; f < nframes; f++) nrsc5hip_unpack_bits(w.data() + (size_t)f * words, len, bits + (size_t)f * len);
+    (void)hipFree(dsoft); (void)hipFree(ddec); (void)hipFree(dout);
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_fetch(nrsc5hip_engine *e, int stream, int8_t *pm, float *bins)
+{
+    ON_ENGINE_DEVICE(e);
+    int rc = check_stream(e, stream); if (rc) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (pm) {
+        int slot = 0;
+        HIPCHK(hipMemcpy(&slot, (const char *)(e->db.state + stream) + offsetof(StreamState, last_pm_slot), sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pm, e->db.pm + ((size_t)stream * NPM + slot) * PM_FRAME, PM_FRAME, hipMemcpyDeviceToHost));
+    }
+    if (bins) HIPCHK(hipMemcpy(bins, e->db.bins + (size_t)stream * NSYM * LIVE_N, (size_t)NSYM * LIVE_N * sizeof(float2), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_fetch_costas(nrsc5hip_engine *e, int stream, float *freq, float *phase)
+{
+    ON_ENGINE_DEVICE(e);
+    int rc = check_stream(e, stream); if (rc) return rc;
+    if (!freq || !phase) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (e->staged_stream >= 0 && (rc = flush_staged(e))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(freq, (const char *)(e->db.state + stream) + offsetof(StreamState, costas_freq), LIVE_N * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(phase, (const char *)(e->db.state + stream) + offsetof(StreamState, costas_phase), LIVE_N * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_fetch_px(nrsc5hip_engine *e, int stream, int8_t *pair)
+{
+    ON_ENGINE_DEVICE(e);
+    int rc = check_stream(e, stream); if (rc) return rc;
+    if (!pair) FAIL(NRSC5HIP_EINVAL, "null argument");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(pair, e->db.px_pair + (size_t)stream * 4 * PX_MAX, 4 * PX_MAX, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_fetch_q15(nrsc5hip_engine *e, int stream, long long n, int16_t *out)
+{
+    ON_ENGINE_DEVICE(e);
+    int rc = check_stream(e, stream); if (rc) return rc;
+    if (n < 0 || n > e->db.q15_cap || !out) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    if (e->hc_stream == stream && (rc = hc_detach(e))) return rc;      // a stream that reads the pinned capture has no FIFO to show: it gets one (from its read position on)
+    if (e->staged_stream >= 0 && (rc = flush_staged(e))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, e->db.q15 + (size_t)stream * e->db.q15_cap, (size_t)n * sizeof(c16), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" void *nrsc5hip_debug_alloc_copy(const void *host, size_t nbytes)
+{
+    void *d = nullptr;
+    if (hipMalloc(&d, nbytes ? nbytes : 1) != hipSuccess) return nullptr;
+    if (host && hipMemcpy(d, host, nbytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
+    return d;
+}
+
+extern "C" void nrsc5hip_debug_free(void *dev) { (void)hipFree(dev); }
+
+// Test / bench hygiene: overwrite every result buffer a pass writes (decoded-frame rings on the device, their pinned host mirror,
+// the record rings) with a pattern no decode produces, so that a check after the next pass can only pass on bits written by it.
+extern "C" int nrsc5hip_debug_poison_results(nrsc5hip_engine *e)
+{
+    ON_ENGINE_DEVICE(e);
+    HIPCHK(hipDeviceSynchronize());
+    const size_t S = e->cfg.max_streams;
+    HIPCHK(hipMemset(e->db.p1_ring, 0xA5, S * e->db.p1_slots * (size_t)P1_WORDS * sizeof(uint32_t)));
+    HIPCHK(hipMemset(e->db.records, 0, S * e->db.rec_cap * sizeof(BlockRecord)));
+    HIPCHK(hipMemset(e->db.px_ring, 0xA5, S * (size_t)e->db.px_slots * 2 * PX_WORDS * sizeof(uint32_t)));
+    if (e->frames_host) memset(e->frames_host, 0xA5, S * e->db.p1_slots * (size_t)P1_WORDS * sizeof(uint32_t));
+    if (e->rec_host) memset(e->rec_host, 0, S * e->db.rec_cap * sizeof(BlockRecord));
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_selftest(nrsc5hip_engine *e, int *failures)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !failures) FAIL(NRSC5HIP_EINVAL, "null argument");
+    HIPCHK(hipMemsetAsync(e->db.counters + 2, 0, sizeof(int), e->main));
+    launch_selftest(e->db.counters + 2, e->main);
+    HIPCHK(hipMemcpyAsync(failures, e->db.counters + 2, sizeof(int), hipMemcpyDeviceToHost, e->main));
+    HIPCHK(hipStreamSynchronize(e->main));
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !soft || !bits || !dec_out || len < 64) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    int8_t *dsoft = nullptr; unsigned long long *ddec = nullptr; uint32_t *dout = nullptr;
+    const int words = (len + 31) / 32;
+    HIPCHK(hipMalloc((void **)&dsoft, (size_t)3 * len));
+    HIPCHK(hipMalloc((void **)&ddec, (size_t)(len + 64) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void **)&dout, (size_t)words * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(dsoft, soft, (size_t)3 * len, hipMemcpyHostToDevice));
+    if (launch_viterbi_frames(e->vit_scratch, dsoft, len, 1, ddec, dout, e->main)) FAIL(NRSC5HIP_EINVAL, "frame length %d not supported or out of device memory", len);
+    HIPCHK(hipStreamSynchronize(e->main));
+    std::vector<uint32_t> w(words);
+    HIPCHK(hipMemcpy(w.data(), dout, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(dec_out, ddec, (size_t)(len + 64) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    nrsc5hip_unpack_bits(w.data(), len, bits);
+    (void)hipFree(dsoft); (void)hipFree(ddec); (void)hipFree(dout);
+    return 0;
+}
+
+// micro-benchmark: nframes random frames, `phases` bit0 = forward pass, bit1 = traceback; ms per launch
+extern "C" int nrsc5hip_stage_viterbi_bench(nrsc5hip_engine *e, int len, int nframes, int phases, int reps, float *ms_per_launch)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !ms_per_launch || len < 64 || nframes < 1 || reps < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    int8_t *dsoft = nullptr; unsigned long long *ddec = nullptr; uint32_t *dout = nullptr;
+    const int words = (len + 31) / 32;
+    std::vector<int8_t> h((size_t)nframes * 3 * len);
+    unsigned x = 12345;
+    for (auto &v : h) { x = x * 1664525u + 1013904223u; v = (int8_t)((int)(x >> 24) - 128); if (v == -128) v = -127; }
+    HIPCHK(hipMalloc((void **)&dsoft, h.size()));
+    HIPCHK(hipMalloc((void **)&ddec, (size_t)nframes * (len + 64) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void **)&dout, (size_t)nframes * words * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(dsoft, h.data(), h.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(ddec, 0x55, (size_t)nframes * (len + 64) * sizeof(unsigned long long)));
+    hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+    const int seg = e->fwd_segments > 0 ? e->fwd_segments : 1;
+    if (launch_viterbi_frames(e->vit_scratch, dsoft, len, nframes, ddec, dout, e->main, phases | 1 | (e->tb_walk ? 0 : 16), seg)) FAIL(NRSC5HIP_EINVAL, "frame length %d not supported or out of device memory", len);      // warm-up; packs the soft words and leaves decisions behind
+    HIPCHK(hipEventRecord(a, e->main));
+    for (int r = 0; r < reps; r++) {
+        // a traceback-only measurement consumes the decisions in place: re-run the (untimed-irrelevant) forward pass is not possible
+        // without timing it, so phases == 2 measures forward + traceback minus nothing -- callers subtract the forward figure
+        (void)launch_viterbi_frames(e->vit_scratch, dsoft, len, nframes, ddec, dout, e->main, ((phases & 2) ? (phases | 1) : phases) | 8 | (e->tb_walk ? 0 : 16), seg);
+    }
+    HIPCHK(hipEventRecord(b, e->main));
+    HIPCHK(hipEventSynchronize(b));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, a, b));
+    *ms_per_launch = ms / reps;
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    (void)hipFree(dsoft); (void)hipFree(ddec); (void)hipFree(dout);
+    return 0;
+}
+
+// micro-benchmark of the K=9 trellis kernel (E2 code) on random hard-decision frames: phases bit0 = forward, bit1 = traceback
+extern "C" int nrsc5hip_stage_viterbi_k9_bench(nrsc5hip_engine *e, int len, int nframes, int phases, int reps, float *ms_per_launch)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !ms_per_launch || len < 128 || nframes < 1 || reps < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    int8_t *dsoft = nullptr; unsigned long long *ddec = nullptr; uint32_t *dout = nullptr;
+    const int words = (len + 31) / 32;
+    // tail-biting code words of random payloads (generators 0561 / 0753 / 0711, bit 8 - k of the register = payload bit i - k),
+    // one sign in 16 flipped: what the decoder sees on a healthy channel (pure noise would make every segment speculation fail)
+    std::vector<int8_t> h((size_t)nframes * 3 * len);
+    std::vector<uint8_t> pay((size_t)len);
+    const unsigned gens[3] = { 0561, 0753, 0711 };
+    unsigned x = 4321;
+    for (int f = 0; f < nframes; f++) {
+        for (auto &v : pay) { x = x * 1664525u + 1013904223u; v = (uint8_t)((x >> 24) & 1u); }
+        for (int i = 0; i < len; i++) {
+            unsigned r = 0;
+            for (int k = 0; k < 9; k++) r |= (unsigned)pay[(size_t)((i - k + len) % len)] << (8 - k);
+            for (int j = 0; j < 3; j++) {
+                x = x * 1664525u + 1013904223u;
+                int v = (__builtin_popcount(r & gens[j]) & 1) ? 1 : -1;
+                if (((x >> 20) & 15u) == 0) v = -v;
+                h[((size_t)f * len + i) * 3 + j] = (int8_t)v;
+            }
+        }
+    }
+    HIPCHK(hipMalloc((void **)&dsoft, h.size()));
+    HIPCHK(hipMalloc((void **)&ddec, (size_t)nframes * 4 * (len + 64) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc((void **)&dout, (size_t)nframes * words * sizeof(uint32_t)));
+    HIPCHK(hipMemcpy(dsoft, h.data(), h.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(ddec, 0x55, (size_t)nframes * 4 * (len + 64) * sizeof(unsigned long long)));
+    K9Meta *dmeta = nullptr;
+    if (e->am_segments > 1) HIPCHK(hipMalloc((void **)&dmeta, (size_t)nframes * sizeof(K9Meta)));
+    hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+    launch_viterbi_k9_frames(dsoft, len, nframes, 0561, 0753, 0711, ddec, dout, e->main, 3, dmeta, e->am_segments, e->am_warm, e->am_runin, e->db.am_k9stats);
+    HIPCHK(hipEventRecord(a, e->main));
+    for (int r = 0; r < reps; r++) launch_viterbi_k9_frames(dsoft, len, nframes, 0561, 0753, 0711, ddec, dout, e->main, phases, dmeta, e->am_segments, e->am_warm, e->am_runin, e->db.am_k9stats);
+    HIPCHK(hipEventRecord(b, e->main));
+    HIPCHK(hipEventSynchronize(b));
+    if (dmeta) (void)hipFree(dmeta);
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, a, b));
+    *ms_per_launch = ms / reps;
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    (void)hipFree(dsoft); (void)hipFree(ddec); (void)hipFree(dout);
+    return 0;
+}
+
+// Tuning knobs and test hooks: an explicit entry point, nothing is read from the environment.
+extern "C" int nrsc5hip_debug_tune(nrsc5hip_engine *e, int knob, int value)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e) FAIL(NRSC5HIP_EINVAL, "null engine");
+    HIPCHK(hipDeviceSynchronize());
+    switch (knob) {
+    case NRSC5HIP_TUNE_DECODE_STREAMS:    e->naux = std::min(std::max(value, 1), NAUX); break;
+    case NRSC5HIP_TUNE_AM_DECODE_STREAMS: e->naux_am = std::min(std::max(value, 1), NAUX); break;
+    case NRSC5HIP_TUNE_VERDICT_LAG:       e->verdict_lag = std::min(std::max(value, 0), NWIN); break;
+    case NRSC5HIP_TUNE_FWD_SEGMENTS:      e->fwd_segments = std::min(std::max(value, 0), VIT3_GMAX); break;
+    case NRSC5HIP_TUNE_FWD_WARM:          e->fwd_warm = value > 0 ? 2 : 0; break;
+    case NRSC5HIP_TUNE_DECODE_CUS: {
+        // decode streams confined to value / 32 of the CUs (the pattern keeps that share of every XCD whichever way mask bits map to CUs)
+        const int k = std::min(std::max(value, 8), 32) & ~7;
+        hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, e->cfg.device));
+        const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
+        std::vector<uint32_t> mask((size_t)words, 0u);
+        for (int i = 0; i < ncu; i++) if ((i % 32) < k) mask[(size_t)i / 32] |= 1u << (i % 32);
+        for (int a = 0; a < NAUX; a++) {                       // the new stream first; the old one is destroyed only once it exists
+            hipStream_t fresh = nullptr;
+            if (k >= 32) HIPCHK(hipStreamCreate(&fresh));
+            else HIPCHK(hipExtStreamCreateWithCUMask(&fresh, (uint32_t)words, mask.data()));
+            (void)hipStreamDestroy(e->aux[a]);
+            e->aux[a] = fresh;
+        }
+        break;
+    }
+    case NRSC5HIP_TUNE_DECODE_PRIORITY: {
+        int least = 0, greatest = 0;
+        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        for (int a = 0; a < NAUX; a++) {
+            hipStream_t fresh = nullptr;
+            if (value) HIPCHK(hipStreamCreateWithPriority(&fresh, hipStreamDefault, least));
+            else HIPCHK(hipStreamCreate(&fresh));
+            (void)hipStreamDestroy(e->aux[a]);
+            e->aux[a] = fresh;
+        }
+        break;
+    }
+    case NRSC5HIP_TUNE_TRACEBACK_WALK:    e->tb_walk = std::min(std::max(value, 0), 16384); break;
+    case NRSC5HIP_TUNE_SYNC_LANES:        e->sync_lanes = (value == 256 || value == 768) ? value : 0; break;
+    case NRSC5HIP_TUNE_SEAM_PREPARE:      e->fuse_seam_prepare = value != 0; break;
+    case NRSC5HIP_TUNE_FOLD_REPORT:       e->fold_report = value != 0; break;
+    case NRSC5HIP_TUNE_NCO_EXACT:         e->db.nco_policy = e->db.nco_tab ? std::min(std::max(value, 0), (int)NCO_EXACT_ALWAYS) : (int)NCO_CLOSED_FORM; break;
+    case NRSC5HIP_TUNE_FLOW_MIN:          e->flow_min = std::max(value, 0); break;
+    case NRSC5HIP_TUNE_LOOP_EXACT:        e->db.loop_exact = std::min(std::max(value, 0), 2); break;
+    case NRSC5HIP_TUNE_EARLY_FLUSH_KB:    e->early_flush = (size_t)std::max(value, 0) << 10; break;
+    case NRSC5HIP_TUNE_DEFER_WAIT:        e->defer_wait = value != 0; break;
+    case NRSC5HIP_TUNE_DIRECT_DECIMATE:   e->direct_decimate = value != 0; break;
+    case NRSC5HIP_TUNE_HOST_CAPTURE: {
+        if (e->hc_stream >= 0) { int rc = hc_detach(e); if (rc) return rc; }
+        if (!e->hc_pin) break;                                 // window-pipeline engines have no fast seam
+        e->host_capture = value != 0;
+        if (value >= 512) {                                    // that many KiB of pinned capture instead of the default 16 MiB (tests: small values exercise hc_rebase)
+            uint8_t *np = nullptr; void *dp = nullptr;
+            if (hipHostMalloc((void **)&np, (size_t)value << 10, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, np, 0) != hipSuccess) FAIL(NRSC5HIP_ENOMEM, "pinned capture allocation failed");
+            (void)hipHostFree(e->hc_pin);
+            e->hc_pin = np; e->hc_dev = (uint8_t *)dp; e->hc_cap = (size_t)value << 10;
+        }
+        break;
+    }
+    case NRSC5HIP_TUNE_MIXFFT_SYMS: {
+        e->mixfft_syms = (value == 2 || value == 4 || value == 8 || value == 16 || value == 32 || (value >= 100 && value <= 140)) ? value : 1;
+        if (e->mixfft_syms >= 100) {                           // DIAGNOSTIC LDS padding: never beyond what a workgroup may have beside the kernel's own ~20 KB (an oversized request failed the
+            int lds_max = 65536;                               // launch, and the failure surfaced at some later hipGetLastError)
+#ifndef HIPEMU
+            HIPCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, e->cfg.device));
+#endif
+            const int room_kib = (lds_max - 24 * 1024) / 1024;
+            if (e->mixfft_syms - 100 > room_kib) e->mixfft_syms = 100 + std::max(room_kib, 0);
+        }
+        break;
+    }
+    case NRSC5HIP_TUNE_AM_SEGMENTS:       e->am_segments = std::min(std::max(value, 1), K9_GMAX); break;
+    case NRSC5HIP_TUNE_AM_WARM:           e->am_warm = value > 0 ? K9_WARM : 0; e->am_runin = value > 0 ? K9_TB_RUNIN : 0; break;
+    case NRSC5HIP_TUNE_SYNC_PHASES:
+        if (value && !e->sync_phase_buf) {
+            int rc = dev_alloc(e, &e->sync_phase_buf, 16); if (rc) return rc;
+            HIPCHK(hipMemset(e->sync_phase_buf, 0, 16 * sizeof(long long)));
+        }
+        e->db.sync_phase_cycles = value ? e->sync_phase_buf : nullptr;
+        break;
+    default: FAIL(NRSC5HIP_EINVAL, "unknown knob %d", knob);
+    }
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_flow_stats(nrsc5hip_engine *e, long long stats[2])
+{
+    if (!e || !stats) return NRSC5HIP_EINVAL;
+    stats[0] = e->flow_bursts; stats[1] = e->flow_steps;
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_host_capture_stats(nrsc5hip_engine *e, long long stats[5])
+{
+    if (!e || !stats) return NRSC5HIP_EINVAL;
+    stats[0] = e->hc_attaches; stats[1] = e->hc_detaches; stats[2] = e->hc_rebases; stats[3] = e->hc_stream; stats[4] = e->reports_folded;
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_fwd_stats(nrsc5hip_engine *e, int stats[2])
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !stats) FAIL(NRSC5HIP_EINVAL, "null argument");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(stats, e->db.fwd_stats, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_tb_stats(nrsc5hip_engine *e, int stats[2])
+{
+    ON_ENGINE_DEVICE(e);
+    if (!stats) FAIL(NRSC5HIP_EINVAL, "null argument");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(stats, e->db.tb_stats, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_k9_stats(nrsc5hip_engine *e, int stats[4])
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !stats) FAIL(NRSC5HIP_EINVAL, "null argument");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(stats, e->db.am_k9stats, 4 * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_debug_sync_phases(nrsc5hip_engine *e, long long *cycles16)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !cycles16) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!e->sync_phase_buf) FAIL(NRSC5HIP_EINVAL, "turn the instrumentation on first: nrsc5hip_debug_tune(e, NRSC5HIP_TUNE_SYNC_PHASES, 1)");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(cycles16, e->sync_phase_buf, 16 * sizeof(long long), hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -19,8 +19,7 @@
 #include <string>
 #include <vector>
 #include "nrsc5hip.h"
-
-namespace nrsc5 { void set_last_error(const char *msg); }
+#include "host_util.h"
 
 namespace {
 
@@ -198,21 +197,7 @@ struct nrsc5hip_chan {
     long long n_total = 0, m_total = 0;                     // input samples pushed / outputs produced since create or reset
 };
 
-#define CFAIL(code, ...) do { char _m[512]; snprintf(_m, sizeof(_m), __VA_ARGS__); nrsc5::set_last_error(_m); return (code); } while (0)
-#define CHIPCHK(expr)                                                                                                          \
-    do {                                                                                                                       \
-        hipError_t _e = (expr);                                                                                                \
-        if (_e != hipSuccess) CFAIL(NRSC5HIP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
-// as the engine's entry points: switch to the channelizer's device for the call, restore the caller's on return
-struct ChanDeviceGuard {
-    int prev = -1, want = -1;
-    explicit ChanDeviceGuard(int dev) : want(dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != want) (void)hipSetDevice(want); }
-    ~ChanDeviceGuard() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-};
-
 // number of outputs m with floor(t_m) + T/2 < n, i.e. m >= 0 with floor(m P / Q) <= n - 1 - T/2
 long long outputs_total(const nrsc5hip_chan *c, long long n)
 {
@@ -236,11 +221,11 @@ void free_chan(nrsc5hip_chan *c)
 
 int chan_zero_state(nrsc5hip_chan *c)
 {
-    if (c->eng_pending) { CHIPCHK(hipEventSynchronize(c->ev_eng)); c->eng_pending = false; }
-    CHIPCHK(hipMemsetAsync(c->d_hist[0], 0, sizeof(float2) * c->T, c->stream));
-    CHIPCHK(hipMemsetAsync(c->d_hist[1], 0, sizeof(float2) * c->T, c->stream));
-    CHIPCHK(hipMemsetAsync(c->d_clips, 0, sizeof(unsigned long long) * c->nchan, c->stream));
-    CHIPCHK(hipStreamSynchronize(c->stream));
+    if (c->eng_pending) { HIPCHK(hipEventSynchronize(c->ev_eng)); c->eng_pending = false; }
+    HIPCHK(hipMemsetAsync(c->d_hist[0], 0, sizeof(float2) * c->T, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_hist[1], 0, sizeof(float2) * c->T, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_clips, 0, sizeof(unsigned long long) * c->nchan, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     c->cur = 0; c->n_total = 0; c->m_total = 0;
     return 0;
 }
@@ -251,7 +236,7 @@ int chan_launch(nrsc5hip_chan *c, const void *dev_in, long long n_in, long long 
     if (n_in <= 0) return 0;
     if (nout > 0) {
         const long long tiles = (c->m_total + nout - 1) / c->mt - c->m_total / c->mt + 1;
-        if (tiles > 0x7fffffffLL) CFAIL(NRSC5HIP_EINVAL, "push too large: %lld output tiles", tiles);
+        if (tiles > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "push too large: %lld output tiles", tiles);
         ChanArgs a;
         a.in = dev_in; a.fmt = c->fmt; a.T = c->T; a.n0 = c->n_total; a.n_in = n_in; a.hist = c->d_hist[c->cur];
         a.table = c->d_table; a.step = c->d_step; a.gain = c->d_gain; a.P = c->P; a.Q = c->Q; a.L = c->L; a.mt = c->mt;
@@ -261,11 +246,11 @@ int chan_launch(nrsc5hip_chan *c, const void *dev_in, long long n_in, long long 
         const int block = c->mt < 64 ? 64 : c->mt;
         dim3 grid((unsigned)tiles, (unsigned)((c->nchan + GROUP - 1) / GROUP));
         hipLaunchKernelGGL(k_channelize, grid, dim3(block), (size_t)CG * c->span * sizeof(float2), c->stream, a);
-        CHIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_chan_history, dim3((c->T + 255) / 256), dim3(256), 0, c->stream, dev_in, c->fmt, c->n_total, n_in,
                        (const float2 *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], c->T);
-    CHIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     c->cur ^= 1;
     c->n_total += n_in;
     c->m_total += nout;
@@ -275,28 +260,28 @@ int chan_launch(nrsc5hip_chan *c, const void *dev_in, long long n_in, long long 
 
 extern "C" int nrsc5hip_chan_create(const nrsc5hip_chan_config *cfg, nrsc5hip_chan **out)
 {
-    if (!cfg || !out) CFAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!cfg || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
     *out = nullptr;
-    if (cfg->format < NRSC5HIP_IQ_CU8 || cfg->format > NRSC5HIP_IQ_CF32) CFAIL(NRSC5HIP_EINVAL, "bad input format %d", cfg->format);
-    if (cfg->nchan < 1 || cfg->nchan > MAX_CHANNELS) CFAIL(NRSC5HIP_EINVAL, "nchan %d out of range 1..%d", cfg->nchan, MAX_CHANNELS);
-    if (!cfg->offset_hz) CFAIL(NRSC5HIP_EINVAL, "null offset_hz");
-    if (cfg->rate_num <= 0 || cfg->rate_den <= 0) CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld not positive", cfg->rate_num, cfg->rate_den);
+    if (cfg->format < NRSC5HIP_IQ_CU8 || cfg->format > NRSC5HIP_IQ_CF32) FAIL(NRSC5HIP_EINVAL, "bad input format %d", cfg->format);
+    if (cfg->nchan < 1 || cfg->nchan > MAX_CHANNELS) FAIL(NRSC5HIP_EINVAL, "nchan %d out of range 1..%d", cfg->nchan, MAX_CHANNELS);
+    if (!cfg->offset_hz) FAIL(NRSC5HIP_EINVAL, "null offset_hz");
+    if (cfg->rate_num <= 0 || cfg->rate_den <= 0) FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld not positive", cfg->rate_num, cfg->rate_den);
     const __int128 num = cfg->rate_num, den = cfg->rate_den;          // 744 187.5 <= num / den <= 64e6, exactly
     if (num * OUT_RATE_DEN < (__int128)OUT_RATE_NUM * den || num > (__int128)64000000 * den)
-        CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld S/s outside 744187.5 .. 64e6", cfg->rate_num, cfg->rate_den);
+        FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld S/s outside 744187.5 .. 64e6", cfg->rate_num, cfg->rate_den);
     // R = Fs_in / 744 187.5 = (num * 2) / (den * 1488375) = P / Q, reduced
     const __int128 p128 = num * OUT_RATE_DEN, q128 = den * OUT_RATE_NUM;
-    if (p128 >= ((__int128)1 << 62) || q128 >= ((__int128)1 << 62)) CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld: terms too large", cfg->rate_num, cfg->rate_den);
+    if (p128 >= ((__int128)1 << 62) || q128 >= ((__int128)1 << 62)) FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld: terms too large", cfg->rate_num, cfg->rate_den);
     unsigned long long P = (unsigned long long)p128, Q = (unsigned long long)q128;
     const unsigned long long g = gcd_u64(P, Q);
     P /= g; Q /= g;
     if (P >= (1ull << 31) || Q >= (1ull << 31))
-        CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld: resampling ratio %llu/%llu needs terms below 2^31", cfg->rate_num, cfg->rate_den, P, Q);
+        FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld: resampling ratio %llu/%llu needs terms below 2^31", cfg->rate_num, cfg->rate_den, P, Q);
     const double fs = (double)cfg->rate_num / (double)cfg->rate_den;
     for (int k = 0; k < cfg->nchan; k++) {
         const double f = cfg->offset_hz[k];
-        if (!(fabs(f) <= fs / 2 - PASS_HZ)) CFAIL(NRSC5HIP_EINVAL, "channel %d: |offset| %.1f Hz > Fs/2 - %.1f Hz", k, f, PASS_HZ);
-        if (cfg->gain && !std::isfinite(cfg->gain[k])) CFAIL(NRSC5HIP_EINVAL, "channel %d: gain not finite", k);
+        if (!(fabs(f) <= fs / 2 - PASS_HZ)) FAIL(NRSC5HIP_EINVAL, "channel %d: |offset| %.1f Hz > Fs/2 - %.1f Hz", k, f, PASS_HZ);
+        if (cfg->gain && !std::isfinite(cfg->gain[k])) FAIL(NRSC5HIP_EINVAL, "channel %d: gain not finite", k);
     }
     // prototype: Kaiser-windowed sinc, cut-off half-way through the transition band, support T input samples
     const double beta = 0.1102 * (DESIGN_ATTEN_DB - 8.7);
@@ -311,10 +296,10 @@ extern "C" int nrsc5hip_chan_create(const nrsc5hip_chan_config *cfg, nrsc5hip_ch
     for (; mt > 16; mt /= 2)
         if ((long long)((mt - 1) * (unsigned __int128)P / Q) + T + 2 <= SPAN_MAX) break;
     const long long span = (long long)((mt - 1) * (unsigned __int128)P / Q) + T + 2;
-    if (span > SPAN_MAX) CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld: tile span %lld exceeds %d", cfg->rate_num, cfg->rate_den, span, SPAN_MAX);
+    if (span > SPAN_MAX) FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld: tile span %lld exceeds %d", cfg->rate_num, cfg->rate_den, span, SPAN_MAX);
 
     nrsc5hip_chan *c = new (std::nothrow) nrsc5hip_chan;
-    if (!c) CFAIL(NRSC5HIP_ENOMEM, "out of host memory");
+    if (!c) FAIL(NRSC5HIP_ENOMEM, "out of host memory");
     c->device = cfg->device; c->fmt = cfg->format; c->nchan = cfg->nchan;
     c->fs = fs; c->P = P; c->Q = Q; c->T = T; c->L = L; c->mt = mt; c->span = (int)span;
     for (int k = 0; k < cfg->nchan; k++) {
@@ -336,8 +321,8 @@ extern "C" int nrsc5hip_chan_create(const nrsc5hip_chan_config *cfg, nrsc5hip_ch
             c->table[(size_t)p * T + j] = (float)v;
         }
 
-    ChanDeviceGuard guard(c->device);
-#define CREATE_CHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { char _m[512]; snprintf(_m, sizeof(_m), "%s failed: %s", #expr, hipGetErrorString(_e)); free_chan(c); nrsc5::set_last_error(_m); return NRSC5HIP_EHIP; } } while (0)
+    nrsc5::DeviceGuard guard(c->device);
+#define CREATE_CHK(expr) HIPCHK_OR(expr, free_chan(c))
     CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     CREATE_CHK(hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
     CREATE_CHK(hipEventCreateWithFlags(&c->ev_eng, hipEventDisableTiming));
@@ -361,21 +346,21 @@ extern "C" int nrsc5hip_chan_create(const nrsc5hip_chan_config *cfg, nrsc5hip_ch
 extern "C" void nrsc5hip_chan_destroy(nrsc5hip_chan *c)
 {
     if (!c) return;
-    ChanDeviceGuard guard(c->device);
+    nrsc5::DeviceGuard guard(c->device);
     free_chan(c);
 }
 
 extern "C" int nrsc5hip_chan_reset(nrsc5hip_chan *c)
 {
-    if (!c) CFAIL(NRSC5HIP_EINVAL, "null channelizer");
-    ChanDeviceGuard guard(c->device);
-    CHIPCHK(hipStreamSynchronize(c->stream));
+    if (!c) FAIL(NRSC5HIP_EINVAL, "null channelizer");
+    nrsc5::DeviceGuard guard(c->device);
+    HIPCHK(hipStreamSynchronize(c->stream));
     return chan_zero_state(c);
 }
 
 extern "C" int nrsc5hip_chan_info(nrsc5hip_chan *c, double *realised_offset_hz, int *taps, int *phases)
 {
-    if (!c) CFAIL(NRSC5HIP_EINVAL, "null channelizer");
+    if (!c) FAIL(NRSC5HIP_EINVAL, "null channelizer");
     if (realised_offset_hz)
         for (int k = 0; k < c->nchan; k++) realised_offset_hz[k] = (double)(int)c->step[k] * c->fs / 4294967296.0;
     if (taps) *taps = c->T;
@@ -385,83 +370,83 @@ extern "C" int nrsc5hip_chan_info(nrsc5hip_chan *c, double *realised_offset_hz, 
 
 extern "C" int nrsc5hip_chan_taps(nrsc5hip_chan *c, float *table)
 {
-    if (!c || !table) CFAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!c || !table) FAIL(NRSC5HIP_EINVAL, "null argument");
     memcpy(table, c->table.data(), sizeof(float) * c->table.size());
     return 0;
 }
 
 extern "C" long long nrsc5hip_chan_outputs_for(nrsc5hip_chan *c, long long n_in)
 {
-    if (!c) CFAIL(NRSC5HIP_EINVAL, "null channelizer");
-    if (n_in < 0) CFAIL(NRSC5HIP_EINVAL, "n_in %lld negative", n_in);
+    if (!c) FAIL(NRSC5HIP_EINVAL, "null channelizer");
+    if (n_in < 0) FAIL(NRSC5HIP_EINVAL, "n_in %lld negative", n_in);
     return outputs_total(c, c->n_total + n_in) - c->m_total;
 }
 
 extern "C" int nrsc5hip_chan_process(nrsc5hip_chan *c, const void *dev_in, long long n_in, int16_t *dev_out, long long out_stride_elems,
                                      long long out_capacity, long long *n_out)
 {
-    if (!c) CFAIL(NRSC5HIP_EINVAL, "null channelizer");
-    if (n_in < 0 || (n_in > 0 && !dev_in)) CFAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
+    if (!c) FAIL(NRSC5HIP_EINVAL, "null channelizer");
+    if (n_in < 0 || (n_in > 0 && !dev_in)) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
     const long long nout = outputs_total(c, c->n_total + n_in) - c->m_total;
-    if (nout > 0 && !dev_out) CFAIL(NRSC5HIP_EINVAL, "null output");
+    if (nout > 0 && !dev_out) FAIL(NRSC5HIP_EINVAL, "null output");
     if (out_capacity < 0 || (c->nchan > 1 && out_stride_elems < 2 * out_capacity))
-        CFAIL(NRSC5HIP_EINVAL, "out_stride_elems %lld < 2 * out_capacity %lld", out_stride_elems, out_capacity);
-    if (nout > out_capacity) CFAIL(NRSC5HIP_EOVERFLOW, "push of %lld samples yields %lld outputs per channel > out_capacity %lld", n_in, nout, out_capacity);
-    ChanDeviceGuard guard(c->device);
+        FAIL(NRSC5HIP_EINVAL, "out_stride_elems %lld < 2 * out_capacity %lld", out_stride_elems, out_capacity);
+    if (nout > out_capacity) FAIL(NRSC5HIP_EOVERFLOW, "push of %lld samples yields %lld outputs per channel > out_capacity %lld", n_in, nout, out_capacity);
+    nrsc5::DeviceGuard guard(c->device);
     int rc = chan_launch(c, dev_in, n_in, nout, dev_out, out_stride_elems);
     if (rc) return rc;
-    CHIPCHK(hipStreamSynchronize(c->stream));               // outputs complete, dev_in no longer read
+    HIPCHK(hipStreamSynchronize(c->stream));               // outputs complete, dev_in no longer read
     if (n_out) *n_out = nout;
     return 0;
 }
 
 extern "C" int nrsc5hip_chan_clip_counts(nrsc5hip_chan *c, long long *counts)
 {
-    if (!c || !counts) CFAIL(NRSC5HIP_EINVAL, "null argument");
-    ChanDeviceGuard guard(c->device);
-    CHIPCHK(hipStreamSynchronize(c->stream));
-    CHIPCHK(hipMemcpy(counts, c->d_clips, sizeof(long long) * c->nchan, hipMemcpyDeviceToHost));
+    if (!c || !counts) FAIL(NRSC5HIP_EINVAL, "null argument");
+    nrsc5::DeviceGuard guard(c->device);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(counts, c->d_clips, sizeof(long long) * c->nchan, hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int nrsc5hip_chan_feed(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, const void *dev_in, long long n_in)
 {
-    if (!c || !e || !stream_ids) CFAIL(NRSC5HIP_EINVAL, "null argument");
-    if (n_in < 0 || (n_in > 0 && !dev_in)) CFAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
+    if (!c || !e || !stream_ids) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (n_in < 0 || (n_in > 0 && !dev_in)) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
     const long long nout = outputs_total(c, c->n_total + n_in) - c->m_total;
-    if (2 * nout > 0xffffffffLL) CFAIL(NRSC5HIP_EINVAL, "push too large for one append (%lld outputs)", nout);
-    ChanDeviceGuard guard(c->device);
+    if (2 * nout > 0xffffffffLL) FAIL(NRSC5HIP_EINVAL, "push too large for one append (%lld outputs)", nout);
+    nrsc5::DeviceGuard guard(c->device);
     if (nout > c->feed_cap) {                               // grow the staging buffer once the engine has read the old one
-        if (c->eng_pending) { CHIPCHK(hipEventSynchronize(c->ev_eng)); c->eng_pending = false; }
-        CHIPCHK(hipStreamSynchronize(c->stream));
-        CHIPCHK(hipFree(c->d_feed)); c->d_feed = nullptr; c->feed_cap = 0;
+        if (c->eng_pending) { HIPCHK(hipEventSynchronize(c->ev_eng)); c->eng_pending = false; }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(c->d_feed)); c->d_feed = nullptr; c->feed_cap = 0;
         const long long cap = nout + nout / 4 + 1024;
-        CHIPCHK(hipMalloc(&c->d_feed, sizeof(int16_t) * 2 * (size_t)cap * c->nchan));
+        HIPCHK(hipMalloc(&c->d_feed, sizeof(int16_t) * 2 * (size_t)cap * c->nchan));
         c->feed_cap = cap;
     }
-    if (c->eng_pending) CHIPCHK(hipStreamWaitEvent(c->stream, c->ev_eng, 0));   // the engine's previous append has read the buffer
+    if (c->eng_pending) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_eng, 0));   // the engine's previous append has read the buffer
     // the state before this push: an append the engine refuses (stream id, q15_capacity) leaves the channelizer as it was
     const int cur0 = c->cur; const long long n0 = c->n_total, m0 = c->m_total;
-    CHIPCHK(hipMemcpyAsync(c->d_clips_saved, c->d_clips, sizeof(unsigned long long) * c->nchan, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_clips_saved, c->d_clips, sizeof(unsigned long long) * c->nchan, hipMemcpyDeviceToDevice, c->stream));
     int rc = chan_launch(c, dev_in, n_in, nout, c->d_feed, 2 * c->feed_cap);
     if (rc) return rc;
     if (nout > 0) {
         hipStream_t es = (hipStream_t)nrsc5hip_engine_hip_stream(e);
-        CHIPCHK(hipEventRecord(c->ev_out, c->stream));
-        CHIPCHK(hipStreamWaitEvent(es, c->ev_out, 0));
+        HIPCHK(hipEventRecord(c->ev_out, c->stream));
+        HIPCHK(hipStreamWaitEvent(es, c->ev_out, 0));
         std::vector<uint32_t> nelems(c->nchan, (uint32_t)(2 * nout));
         rc = nrsc5hip_batch_append_cs16(e, c->nchan, stream_ids, c->d_feed, 2 * c->feed_cap, nelems.data());
         if (rc) {
             std::string msg = nrsc5hip_last_error();
-            CHIPCHK(hipStreamSynchronize(c->stream));
-            CHIPCHK(hipMemcpy(c->d_clips, c->d_clips_saved, sizeof(unsigned long long) * c->nchan, hipMemcpyDeviceToDevice));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            HIPCHK(hipMemcpy(c->d_clips, c->d_clips_saved, sizeof(unsigned long long) * c->nchan, hipMemcpyDeviceToDevice));
             c->cur = cur0; c->n_total = n0; c->m_total = m0;        // the old history buffer was only read
             nrsc5::set_last_error(msg.c_str());
             return rc;
         }
-        CHIPCHK(hipEventRecord(c->ev_eng, es));
+        HIPCHK(hipEventRecord(c->ev_eng, es));
         c->eng_pending = true;
     }
-    CHIPCHK(hipStreamSynchronize(c->stream));               // dev_in no longer read when the call returns
+    HIPCHK(hipStreamSynchronize(c->stream));               // dev_in no longer read when the call returns
     return 0;
 }

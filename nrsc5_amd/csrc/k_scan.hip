@@ -32,8 +32,7 @@
 #include <new>
 #include <vector>
 #include "nrsc5hip.h"
-
-namespace nrsc5 { void set_last_error(const char *msg); }
+#include "host_util.h"
 
 namespace {
 
@@ -175,20 +174,7 @@ struct nrsc5hip_scan {
     long long n_total = 0, segments = 0;                    // samples pushed / complete segments since create or reset
 };
 
-#define CFAIL(code, ...) do { char _m[512]; snprintf(_m, sizeof(_m), __VA_ARGS__); nrsc5::set_last_error(_m); return (code); } while (0)
-#define CHIPCHK(expr)                                                                                                          \
-    do {                                                                                                                       \
-        hipError_t _e = (expr);                                                                                                \
-        if (_e != hipSuccess) CFAIL(NRSC5HIP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
-struct ScanDeviceGuard {
-    int prev = -1, want = -1;
-    explicit ScanDeviceGuard(int dev) : want(dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != want) (void)hipSetDevice(want); }
-    ~ScanDeviceGuard() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-};
-
 size_t scan_lds_bytes(int nfft) { return sizeof(cplx) * (size_t)(nfft + nfft / 16); }
 
 void free_scan(nrsc5hip_scan *s)
@@ -202,10 +188,10 @@ void free_scan(nrsc5hip_scan *s)
 
 int scan_zero_state(nrsc5hip_scan *s)
 {
-    CHIPCHK(hipMemsetAsync(s->d_hist[0], 0, sizeof(float2) * s->nfft, s->stream));
-    CHIPCHK(hipMemsetAsync(s->d_hist[1], 0, sizeof(float2) * s->nfft, s->stream));
-    CHIPCHK(hipMemsetAsync(s->d_sum, 0, sizeof(double) * s->nfft, s->stream));
-    CHIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemsetAsync(s->d_hist[0], 0, sizeof(float2) * s->nfft, s->stream));
+    HIPCHK(hipMemsetAsync(s->d_hist[1], 0, sizeof(float2) * s->nfft, s->stream));
+    HIPCHK(hipMemsetAsync(s->d_sum, 0, sizeof(double) * s->nfft, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
     s->cur = 0; s->n_total = 0; s->segments = 0;
     return 0;
 }
@@ -262,12 +248,12 @@ struct Staircase {
 
 int detect_psd(const double *psd, int nfft, double fs, const nrsc5hip_scan_params *params, nrsc5hip_scan_station *out, int max, int *n_out)
 {
-    if (!psd || !n_out) CFAIL(NRSC5HIP_EINVAL, "null argument");
-    if (nfft < 16 || (nfft & (nfft - 1))) CFAIL(NRSC5HIP_EINVAL, "nfft %d is not a power of two >= 16", nfft);
-    if (!(fs > 0) || !std::isfinite(fs)) CFAIL(NRSC5HIP_EINVAL, "bad sample rate");
-    if (max < 0 || (max > 0 && !out)) CFAIL(NRSC5HIP_EINVAL, "bad output array (max %d)", max);
+    if (!psd || !n_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (nfft < 16 || (nfft & (nfft - 1))) FAIL(NRSC5HIP_EINVAL, "nfft %d is not a power of two >= 16", nfft);
+    if (!(fs > 0) || !std::isfinite(fs)) FAIL(NRSC5HIP_EINVAL, "bad sample rate");
+    if (max < 0 || (max > 0 && !out)) FAIL(NRSC5HIP_EINVAL, "bad output array (max %d)", max);
     const double threshold = params ? params->threshold_db : 6.0, min_sep = params ? params->min_separation_hz : 100e3;
-    if (!std::isfinite(threshold) || !(min_sep >= 0)) CFAIL(NRSC5HIP_EINVAL, "bad detector parameters");
+    if (!std::isfinite(threshold) || !(min_sep >= 0)) FAIL(NRSC5HIP_EINVAL, "bad detector parameters");
     *n_out = 0;
     std::vector<double> sorted(psd, psd + nfft);
     std::sort(sorted.begin(), sorted.end());
@@ -312,25 +298,25 @@ int detect_psd(const double *psd, int nfft, double fs, const nrsc5hip_scan_param
 
 extern "C" int nrsc5hip_scan_create(const nrsc5hip_scan_config *cfg, nrsc5hip_scan **out)
 {
-    if (!cfg || !out) CFAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!cfg || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
     *out = nullptr;
-    if (cfg->format < NRSC5HIP_IQ_CU8 || cfg->format > NRSC5HIP_IQ_CF32) CFAIL(NRSC5HIP_EINVAL, "bad input format %d", cfg->format);
-    if (cfg->rate_num <= 0 || cfg->rate_den <= 0) CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld not positive", cfg->rate_num, cfg->rate_den);
+    if (cfg->format < NRSC5HIP_IQ_CU8 || cfg->format > NRSC5HIP_IQ_CF32) FAIL(NRSC5HIP_EINVAL, "bad input format %d", cfg->format);
+    if (cfg->rate_num <= 0 || cfg->rate_den <= 0) FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld not positive", cfg->rate_num, cfg->rate_den);
     const __int128 num = cfg->rate_num, den = cfg->rate_den;          // 744 187.5 <= num / den <= 64e6, exactly
     if (num * MIN_RATE_DEN < (__int128)MIN_RATE_NUM * den || num > (__int128)64000000 * den)
-        CFAIL(NRSC5HIP_EINVAL, "rate %lld/%lld S/s outside 744187.5 .. 64e6", cfg->rate_num, cfg->rate_den);
+        FAIL(NRSC5HIP_EINVAL, "rate %lld/%lld S/s outside 744187.5 .. 64e6", cfg->rate_num, cfg->rate_den);
     const double fs = (double)cfg->rate_num / (double)cfg->rate_den;
     int log2n = 0;
     if (cfg->nfft == 0) {                                             // the smallest power of two >= Fs / 2 kHz, within 512 .. 8192
         for (log2n = MIN_LOG2; log2n < MAX_LOG2 && (double)(1 << log2n) < fs / 2000.0; log2n++) {}
     } else {
         for (log2n = MIN_LOG2; log2n <= MAX_LOG2 && (1 << log2n) != cfg->nfft; log2n++) {}
-        if (log2n > MAX_LOG2) CFAIL(NRSC5HIP_EINVAL, "nfft %d is not a power of two in 512..8192", cfg->nfft);
+        if (log2n > MAX_LOG2) FAIL(NRSC5HIP_EINVAL, "nfft %d is not a power of two in 512..8192", cfg->nfft);
     }
     const int nfft = 1 << log2n;
 
     nrsc5hip_scan *s = new (std::nothrow) nrsc5hip_scan;
-    if (!s) CFAIL(NRSC5HIP_ENOMEM, "out of host memory");
+    if (!s) FAIL(NRSC5HIP_ENOMEM, "out of host memory");
     s->device = cfg->device; s->fmt = cfg->format; s->nfft = nfft; s->log2n = log2n; s->fs = fs;
     std::vector<cplx> tw(nfft);
     std::vector<double> win(nfft);
@@ -341,8 +327,8 @@ extern "C" int nrsc5hip_scan_create(const nrsc5hip_scan_config *cfg, nrsc5hip_sc
         s->sum_w2 += win[k] * win[k];
     }
 
-    ScanDeviceGuard guard(s->device);
-#define CREATE_CHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { char _m[512]; snprintf(_m, sizeof(_m), "%s failed: %s", #expr, hipGetErrorString(_e)); free_scan(s); nrsc5::set_last_error(_m); return NRSC5HIP_EHIP; } } while (0)
+    nrsc5::DeviceGuard guard(s->device);
+#define CREATE_CHK(expr) HIPCHK_OR(expr, free_scan(s))
     CREATE_CHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     CREATE_CHK(hipMalloc(&s->d_tw, sizeof(cplx) * nfft));
     CREATE_CHK(hipMalloc(&s->d_win, sizeof(double) * nfft));
@@ -369,34 +355,34 @@ extern "C" int nrsc5hip_scan_create(const nrsc5hip_scan_config *cfg, nrsc5hip_sc
 extern "C" void nrsc5hip_scan_destroy(nrsc5hip_scan *s)
 {
     if (!s) return;
-    ScanDeviceGuard guard(s->device);
+    nrsc5::DeviceGuard guard(s->device);
     free_scan(s);
 }
 
 extern "C" int nrsc5hip_scan_reset(nrsc5hip_scan *s)
 {
-    if (!s) CFAIL(NRSC5HIP_EINVAL, "null scanner");
-    ScanDeviceGuard guard(s->device);
-    CHIPCHK(hipStreamSynchronize(s->stream));
+    if (!s) FAIL(NRSC5HIP_EINVAL, "null scanner");
+    nrsc5::DeviceGuard guard(s->device);
+    HIPCHK(hipStreamSynchronize(s->stream));
     return scan_zero_state(s);
 }
 
 extern "C" int nrsc5hip_scan_push(nrsc5hip_scan *s, const void *dev_in, long long n_in)
 {
-    if (!s) CFAIL(NRSC5HIP_EINVAL, "null scanner");
-    if (n_in < 0 || (n_in > 0 && !dev_in)) CFAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
+    if (!s) FAIL(NRSC5HIP_EINVAL, "null scanner");
+    if (n_in < 0 || (n_in > 0 && !dev_in)) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
     if (n_in == 0) return 0;
     const long long nseg = segments_total(s, s->n_total + n_in) - s->segments;
-    if (nseg > 0x7fffffffLL) CFAIL(NRSC5HIP_EINVAL, "push too large: %lld segments", nseg);
-    ScanDeviceGuard guard(s->device);
+    if (nseg > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "push too large: %lld segments", nseg);
+    nrsc5::DeviceGuard guard(s->device);
     if (nseg > 0) {
         int run = (int)((nseg + ROWS_TARGET - 1) / ROWS_TARGET);
         if (run > RUN_MAX) run = RUN_MAX;
         const int rows = (int)((nseg + run - 1) / run);
         if (rows > s->part_rows) {
-            CHIPCHK(hipStreamSynchronize(s->stream));
-            CHIPCHK(hipFree(s->d_part)); s->d_part = nullptr; s->part_rows = 0;
-            CHIPCHK(hipMalloc(&s->d_part, sizeof(double) * (size_t)rows * s->nfft));
+            HIPCHK(hipStreamSynchronize(s->stream));
+            HIPCHK(hipFree(s->d_part)); s->d_part = nullptr; s->part_rows = 0;
+            HIPCHK(hipMalloc(&s->d_part, sizeof(double) * (size_t)rows * s->nfft));
             s->part_rows = rows;
         }
         ScanArgs a;
@@ -410,24 +396,24 @@ extern "C" int nrsc5hip_scan_push(nrsc5hip_scan *s, const void *dev_in, long lon
         case 12: scan_launch_psd<12>(a, rows, lds, s->stream); break;
         default: scan_launch_psd<13>(a, rows, lds, s->stream); break;
         }
-        CHIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_scan_reduce, dim3((s->nfft + WG - 1) / WG), dim3(WG), 0, s->stream, (const double *)s->d_part, rows, s->nfft, s->d_sum);
-        CHIPCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     const int T = s->nfft - 1;
     hipLaunchKernelGGL(k_scan_history, dim3((T + WG - 1) / WG), dim3(WG), 0, s->stream, dev_in, s->fmt, s->n_total, n_in,
                        (const float2 *)s->d_hist[s->cur], s->d_hist[s->cur ^ 1], T);
-    CHIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     s->cur ^= 1;
     s->n_total += n_in;
     s->segments += nseg;
-    CHIPCHK(hipStreamSynchronize(s->stream));               // dev_in no longer read when the call returns
+    HIPCHK(hipStreamSynchronize(s->stream));               // dev_in no longer read when the call returns
     return 0;
 }
 
 extern "C" int nrsc5hip_scan_info(nrsc5hip_scan *s, int *nfft, long long *segments, double *bin_hz)
 {
-    if (!s) CFAIL(NRSC5HIP_EINVAL, "null scanner");
+    if (!s) FAIL(NRSC5HIP_EINVAL, "null scanner");
     if (nfft) *nfft = s->nfft;
     if (segments) *segments = s->segments;
     if (bin_hz) *bin_hz = s->fs / s->nfft;
@@ -436,12 +422,12 @@ extern "C" int nrsc5hip_scan_info(nrsc5hip_scan *s, int *nfft, long long *segmen
 
 extern "C" int nrsc5hip_scan_spectrum(nrsc5hip_scan *s, double *psd)
 {
-    if (!s || !psd) CFAIL(NRSC5HIP_EINVAL, "null argument");
-    if (s->segments == 0) CFAIL(NRSC5HIP_EINVAL, "no complete segment yet (%lld of %d samples)", s->n_total, s->nfft);
-    ScanDeviceGuard guard(s->device);
+    if (!s || !psd) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (s->segments == 0) FAIL(NRSC5HIP_EINVAL, "no complete segment yet (%lld of %d samples)", s->n_total, s->nfft);
+    nrsc5::DeviceGuard guard(s->device);
     std::vector<double> sum(s->nfft);
-    CHIPCHK(hipStreamSynchronize(s->stream));
-    CHIPCHK(hipMemcpy(sum.data(), s->d_sum, sizeof(double) * s->nfft, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(sum.data(), s->d_sum, sizeof(double) * s->nfft, hipMemcpyDeviceToHost));
     const double scale = 1.0 / ((double)s->segments * s->sum_w2);
     for (int p = 0; p < s->nfft; p++) {
         const int k = (int)bitrev((unsigned)p, s->log2n);
@@ -458,8 +444,8 @@ extern "C" int nrsc5hip_scan_detect_psd(const double *psd, int nfft, double fs, 
 
 extern "C" int nrsc5hip_scan_detect(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_station *stations_out, int max, int *n)
 {
-    if (!s || !n) CFAIL(NRSC5HIP_EINVAL, "null argument");
-    if (max < 0 || (max > 0 && !stations_out)) CFAIL(NRSC5HIP_EINVAL, "bad output array (max %d)", max);
+    if (!s || !n) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (max < 0 || (max > 0 && !stations_out)) FAIL(NRSC5HIP_EINVAL, "bad output array (max %d)", max);
     std::vector<double> psd(s->nfft);
     int rc = nrsc5hip_scan_spectrum(s, psd.data());
     if (rc) return rc;

@@ -18,7 +18,7 @@
 //
 // The checkpoint terms are DEFENSIVE: with today's scheduler they never lower the floor.  Every nrsc5hip_batch_process -- also one that
 // runs out of max_steps -- ends with flush_p1 / am_flush (all deferred decodes done) and a rollback with lag 0 that takes every verdict
-// (engine.hip: run_steps, run_steps_am), and a trim is a host call between two of them: p1_pending is 0, no verdict is open and
+// (engine_steps.hip: run_steps, run_steps_am), and a trim is a host call between two of them: p1_pending is 0, no verdict is open and
 // floor == st.rd.  They keep the rule right should a scheduler ever return with decodes in flight; no test can reach them through the
 // public interface, and the tests would pass the same with floor = st.rd.
 //

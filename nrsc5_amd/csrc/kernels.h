@@ -96,7 +96,7 @@ struct DevBuffers {
 
 // ---- K1 -------------------------------------------------------------------------------
 // cu8 -> Q15 half-band 2:1 for one chunk per stream.  iq[s] = base + s*stride, nbytes[s] each.
-// what a block step of the fast streaming seam posts into pinned host memory (engine.hip: harvest)
+// what a block step of the fast streaming seam posts into pinned host memory (engine_seam.hip: harvest)
 struct StreamReport { int counters[4]; long long rd; int nblocks; int nrec; BlockRecord rec[4]; unsigned seq; unsigned pad; };
 // streaming seam, ONE stream: the chunk is read where the host staged it (pinned, device-visible: no copy engine, no second buffer),
 // every input byte once; the workgroup that finishes last rolls the decimator history and publishes the new write position

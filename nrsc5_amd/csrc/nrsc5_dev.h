@@ -169,7 +169,7 @@ struct StreamState {
     float nco_re, nco_im, inc_re, inc_im;
     int nco_exact, nco_mode;
     int coarse_samperr; float coarse_re, coarse_im;
-    // P1 hand-off, one slot per in-flight decode window (see engine.hip: P1 pipeline); `parity` = window % NWIN
+    // P1 hand-off, one slot per in-flight decode window (see block_step.h: issue_step, launch_window_decode); `parity` = window % NWIN
     int p1_pending[NWIN];          // 1: frame completed this step (gather it), 2: gathered into coded[s][parity]
     int p1_slot[NWIN];             // slot of the stream's P1 ring the decoder must fill
     int p1_record[NWIN];           // record index that gets the BER
