@@ -15,8 +15,6 @@
 
 namespace nrsc5 {
 
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 __device__ inline bool needs_coarse(const StreamState &st) { return window_ready(st) && st.sync_state != SYNC_FINE; }
 
 // acquisition window of a stream: the FIFO at rd, or -- zero-copy batch -- the window decimated by k_acq_decimate

@@ -1,10 +1,12 @@
 // AM (hybrid MA1 / all-digital MA3) path for gfx950.  Replaces, for NRSC5_MODE_AM:
-//   decimate_samples' 5-stage 32:1 cascade (input.c:70-91)                         -> k_am_decimate_cu8
+//   decimate_samples' 5-stage 32:1 cascade (input.c:70-91)                         -> k_am_decimate_cu8 (k_am_decimate.hip)
 //   acquire_process incl. the AM carrier regression (acquire.c:98-263)             -> k_am_block (fused)
 //   sync_push / sync_process_am, find_ref_am, find_block_am (sync.c:209-252,612-767)-> k_am_block
 //   decode_process_pids_am (decode.c:474-505)                                      -> k_am_block tail
-//   decode_process_p1_p3_am, nrsc5_conv_decode_e1 / _e2_e3 (decode.c:507-554)      -> k_am_viterbi
+//   decode_process_p1_p3_am, nrsc5_conv_decode_e1 / _e2_e3 (decode.c:507-554)      -> k_am_viterbi, k_am_decode_* (k_am_decode.hip; the
+//                                                                                     trellis itself: viterbi_k9.h)
 //   interleaver_ma1 incl. the 3-frame diversity delay (decode.c:74-231)            -> k_am_interleave
+// This file holds the block step and the interleaver.
 //
 // The AM stream is 32 x slower than FM (46.5 kS/s), so one workgroup owns one stream for a whole block:
 // the 32 x 256-point FFTs, the carrier line fit and sync_process_am all run out of one 64 KB LDS tile and
@@ -15,546 +17,9 @@
 #include "fastmath.h"
 #include "wave_ops.h"
 #include "l2_header.h"
+#include "viterbi_k9.h"
 
 namespace nrsc5 {
-
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
-// =====================================================================================================
-// K1-AM: cu8 -> (Q15 >> 4) -> five cascaded 15-tap half-bands
-// =====================================================================================================
-// Output m of the cascade depends on raw samples [32 m - 434, 32 m] and exists once raw sample 32 m + 31 has
-// arrived.  A tile of AMD_T outputs recomputes the dependency cone from raw samples (history kept in the stream
-// state), stage by stage in LDS, so tiles are independent of each other and of how the caller chunks its pushes.
-constexpr int AMD_T = 32;
-constexpr int AMD_N0 = 32 * (AMD_T - 1) + 435;   // raw samples per tile
-constexpr int AMD_N1 = 16 * (AMD_T - 1) + 211;
-constexpr int AMD_N2 = 8 * (AMD_T - 1) + 99;
-constexpr int AMD_N3 = 4 * (AMD_T - 1) + 43;
-constexpr int AMD_N4 = 2 * (AMD_T - 1) + 15;
-
-__device__ inline int am_hb_dot(const int16_t *a, int stride, int t0, int t1, int t2, int t3)
-{
-    int acc = 0;                                               // firdecim_q15.c:137-151: shift before add, int16 accumulator
-    acc = (int16_t)(acc + (((a[0] + a[14 * stride]) * t0) >> 15));
-    acc = (int16_t)(acc + (((a[2 * stride] + a[12 * stride]) * t1) >> 15));
-    acc = (int16_t)(acc + (((a[4 * stride] + a[10 * stride]) * t2) >> 15));
-    acc = (int16_t)(acc + (((a[6 * stride] + a[8 * stride]) * t3) >> 15));
-    return (int16_t)(acc + a[7 * stride]);
-}
-
-// raw sample r (absolute index since reset) of the virtual stream [history | chunk]
-__device__ inline void am_raw_fetch(const AmStream &am, const uint8_t *iq, long long r, long long nraw_new, int &re, int &im)
-{
-    re = 0; im = 0;
-    if (r < 0) return;
-    unsigned a, b;
-    if (r < am.raw_count) {
-        const long long h = r - (am.raw_count - AM_RAW_HIST);
-        if (h < 0) return;
-        a = am.raw_hist[2 * h]; b = am.raw_hist[2 * h + 1];
-    } else {
-        const long long k = r - am.raw_count;
-        if (k >= nraw_new) return;
-        a = iq[2 * k]; b = iq[2 * k + 1];
-    }
-    re = (((int)a - 127) * 64) >> 4;                           // U8_Q15 then x >>= 4 (input.c:67-70)
-    im = (((int)b - 127) * 64) >> 4;
-}
-
-__global__ __launch_bounds__(256) void k_am_decimate_cu8(DevTables tb, DevBuffers db, const int *ids,
-                                                         const uint8_t *iq_base, long long iq_stride, const unsigned *nbytes)
-{
-    const int sidx = blockIdx.y;
-    const int s = stream_of(ids, sidx);
-    const StreamState &st = db.state[s];
-    const AmStream &am = db.am[s];
-    const long long nraw = nbytes[sidx] / 2;
-    const long long m_first = am.raw_count / 32, m_end = (am.raw_count + nraw) / 32;
-    const long long m0 = m_first + (long long)blockIdx.x * AMD_T;
-    if (m0 >= m_end) return;
-    const uint8_t *iq = iq_base + (size_t)sidx * iq_stride;
-    __shared__ int16_t bufA[2 * AMD_N0], bufB[2 * AMD_N1];     // interleaved re, im
-    const int tid = threadIdx.x;
-    const int t0 = tb.hb_q15[0], t1 = tb.hb_q15[1], t2 = tb.hb_q15[2], t3 = tb.hb_q15[3];
-
-    const long long lo0 = 32 * m0 - 434;
-    for (int k = tid; k < AMD_N0; k += 256) {
-        int re, im;
-        am_raw_fetch(am, iq, lo0 + k, nraw, re, im);
-        bufA[2 * k] = (int16_t)re; bufA[2 * k + 1] = (int16_t)im;
-    }
-    // The first outputs after a reset: what lies in front of sample 0 of stage l's input is the window content the reset left there
-    // (AmStream::seed; zeros for a fresh session), not something computed from earlier raw samples.  Stage l's local sample k is its
-    // absolute sample base_l + k, base = lo0, 16 m0 - 210, 8 m0 - 98, 4 m0 - 42, 2 m0 - 14.
-    const bool edge = m0 < 14;                                 // block-uniform: only then does the cone reach below sample 0
-    if (edge) {
-        __syncthreads();
-        if (tid < 14 && -14 + tid - lo0 >= 0 && -14 + tid - lo0 < AMD_N0) { const int k = (int)(-14 + tid - lo0); bufA[2 * k] = am.seed[0][tid].r; bufA[2 * k + 1] = am.seed[0][tid].i; }
-    }
-#define AM_SEED_STAGE(buf, n, base, l) do { if (edge) { __syncthreads(); const long long kk = -14 + tid - (base); \
-        if (tid < 14 && kk >= 0 && kk < (n)) { (buf)[2 * kk] = am.seed[l][tid].r; (buf)[2 * kk + 1] = am.seed[l][tid].i; } } } while (0)
-    __syncthreads();
-    // local index jl of a stage's output reads the previous stage's local samples 2 jl .. 2 jl + 14
-    for (int k = tid; k < 2 * AMD_N1; k += 256) bufB[k] = (int16_t)am_hb_dot(bufA + 4 * (k >> 1) + (k & 1), 2, t0, t1, t2, t3);
-    AM_SEED_STAGE(bufB, AMD_N1, 16 * m0 - 210, 1);
-    __syncthreads();
-    for (int k = tid; k < 2 * AMD_N2; k += 256) bufA[k] = (int16_t)am_hb_dot(bufB + 4 * (k >> 1) + (k & 1), 2, t0, t1, t2, t3);
-    AM_SEED_STAGE(bufA, AMD_N2, 8 * m0 - 98, 2);
-    __syncthreads();
-    for (int k = tid; k < 2 * AMD_N3; k += 256) bufB[k] = (int16_t)am_hb_dot(bufA + 4 * (k >> 1) + (k & 1), 2, t0, t1, t2, t3);
-    AM_SEED_STAGE(bufB, AMD_N3, 4 * m0 - 42, 3);
-    __syncthreads();
-    for (int k = tid; k < 2 * AMD_N4; k += 256) bufA[k] = (int16_t)am_hb_dot(bufB + 4 * (k >> 1) + (k & 1), 2, t0, t1, t2, t3);
-    AM_SEED_STAGE(bufA, AMD_N4, 2 * m0 - 14, 4);
-#undef AM_SEED_STAGE
-    __syncthreads();
-    if (tid < AMD_T && m0 + tid < m_end) {
-        c16 y;
-        y.r = (int16_t)am_hb_dot(bufA + 4 * tid, 2, t0, t1, t2, t3);
-        y.i = (int16_t)am_hb_dot(bufA + 4 * tid + 1, 2, t0, t1, t2, t3);
-        db.q15[(size_t)s * db.q15_cap + (st.wr - st.base) + (m0 - m_first) + tid] = y;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_am_decimate_commit(DevTables tb, DevBuffers db, const int *ids, const uint8_t *iq_base, long long iq_stride, const unsigned *nbytes)
-{
-    const int sidx = blockIdx.x;
-    const int s = stream_of(ids, sidx);
-    StreamState &st = db.state[s];
-    AmStream &am = db.am[s];
-    const long long nraw = nbytes[sidx] / 2;
-    if (nraw == 0) return;
-    const uint8_t *iq = iq_base + (size_t)sidx * iq_stride;
-    __shared__ uint8_t nh[2 * AM_RAW_HIST];
-    const long long first = am.raw_count + nraw - AM_RAW_HIST;
-    for (int k = threadIdx.x; k < AM_RAW_HIST; k += 256) {
-        const long long r = first + k;
-        uint8_t a = 127, b = 127;                              // never read: indices before the stream start
-        if (r >= am.raw_count) { a = iq[2 * (r - am.raw_count)]; b = iq[2 * (r - am.raw_count) + 1]; }
-        else if (r >= 0 && r >= am.raw_count - AM_RAW_HIST) { const long long h = r - (am.raw_count - AM_RAW_HIST); a = am.raw_hist[2 * h]; b = am.raw_hist[2 * h + 1]; }
-        nh[2 * k] = a; nh[2 * k + 1] = b;
-    }
-    // What the last compaction of each stage's window inside this chunk leaves at its front (StaleWindows, nrsc5_dev.h).  decim[0] takes
-    // every raw sample (>> 4): an FM session after the next reset starts from these too.
-    const long long p0 = stale_start(st.stale.hb_pushed, nraw, 14);
-    if (p0 != STALE_NONE && threadIdx.x < 14) {
-        int re, im;
-        am_raw_fetch(am, iq, am.raw_count + p0 + threadIdx.x, nraw, re, im);
-        st.stale.hb[threadIdx.x].r = (int16_t)re; st.stale.hb[threadIdx.x].i = (int16_t)im;
-    }
-    // decim[l], l = 1..4, has taken 2 floor(raw / 2^(l+1)) samples y_l (y_0 = raw >> 4, y_l[j] = half-band over y_(l-1)[2j-14 .. 2j]): the 14 in
-    // front of its last compaction are recomputed from raw samples -- 14 -> 41 -> 95 -> 203 -> 419, at most 465 raw samples back from the
-    // chunk's first (AM_RAW_HIST covers it)
-    {
-        __shared__ int16_t cA[2 * 419], cB[2 * 203];
-        const int t0 = tb.hb_q15[0], t1 = tb.hb_q15[1], t2 = tb.hb_q15[2], t3 = tb.hb_q15[3];
-        for (int l = 1; l <= 4; l++) {
-            const long long a_l = 2 * (am.raw_count >> (l + 1)), b_l = 2 * ((am.raw_count + nraw) >> (l + 1));
-            const long long p = stale_start(a_l, b_l - a_l, 14);
-            if (p == STALE_NONE) continue;                     // block-uniform
-            long long base[5]; int n[5];
-            base[l] = a_l + p; n[l] = 14;
-            for (int q = l; q >= 1; q--) { base[q - 1] = 2 * base[q] - 14; n[q - 1] = 2 * n[q] + 13; }
-            // level q is held in cA when l - q is even, in cB when odd: the 419 samples of l = 4 and the 203 of l = 3 land in the buffer that fits them
-            int16_t *cur = (l & 1) ? cB : cA;
-            for (int k = threadIdx.x; k < n[0]; k += 256) {
-                int re, im;
-                am_raw_fetch(am, iq, base[0] + k, nraw, re, im);
-                cur[2 * k] = (int16_t)re; cur[2 * k + 1] = (int16_t)im;
-            }
-            __syncthreads();
-            for (int q = 1; q <= l; q++) {
-                int16_t *nxt = ((l - q) & 1) ? cB : cA;
-                for (int k = threadIdx.x; k < 2 * n[q]; k += 256) nxt[k] = (int16_t)am_hb_dot(cur + 4 * (k >> 1) + (k & 1), 2, t0, t1, t2, t3);
-                __syncthreads();
-                cur = nxt;
-            }
-            if (threadIdx.x < 14) { st.stale.am_stage[l - 1][threadIdx.x].r = cur[2 * threadIdx.x]; st.stale.am_stage[l - 1][threadIdx.x].i = cur[2 * threadIdx.x + 1]; }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 2 * AM_RAW_HIST; k += 256) am.raw_hist[k] = nh[k];
-    if (threadIdx.x == 0) {
-        st.wr += (am.raw_count + nraw) / 32 - am.raw_count / 32;
-        am.raw_count += nraw;
-        st.stale.hb_pushed += nraw;
-    }
-}
-
-void launch_am_decimate_cu8(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids,
-                            const uint8_t *iq_base, long long iq_stride, const unsigned *nbytes, unsigned max_nbytes, hipStream_t st)
-{
-    const unsigned max_out = max_nbytes / 64 + 1;
-    hipLaunchKernelGGL(k_am_decimate_cu8, dim3((max_out + AMD_T - 1) / AMD_T, nstreams), dim3(256), 0, st, tb, db, stream_ids, iq_base, iq_stride, nbytes);
-    hipLaunchKernelGGL(k_am_decimate_commit, dim3(nstreams), dim3(256), 0, st, tb, db, stream_ids, iq_base, iq_stride, nbytes);
-}
-
-// =====================================================================================================
-// K=9 rate-1/3 tail-biting Viterbi, 256 states = 256 work-items (conv_dec.c:402-453, conv_gen.h:32-123)
-// =====================================================================================================
-// Work-item n owns new state n: predecessors 2b, 2b+1 with b = n & 127, branch metric +m for n < 128 and -m above
-// (acs_butterfly).  int32 metrics, no normalisation (inputs are +-1/0: |metric| <= 3 per step); ties pick
-// predecessor 2b+1 as `if (sum0 > sum1)` does.  Decisions: one ballot per wave and step (4 x u64 per step).
-struct K9Smem {
-    int metric[2][256];
-    int8_t soft[3 * 256];
-    unsigned long long chunk[4 * 256];
-    int red_val[4], red_idx[4];
-    int state;
-};
-
-__device__ inline void viterbi_k9_block(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2,
-                                        unsigned long long *dec, uint32_t *out, K9Smem &sm)
-{
-    const int n = threadIdx.x, b = n & 127;
-    const unsigned reg = ((unsigned)b << 1) & 0xfeu;           // gen_state_info, conv_dec.c:137-153
-    const int flip = n >= 128 ? -1 : 1;
-    const int sg0 = flip * ((__popc(reg & g0) & 1) ? 1 : -1);
-    const int sg1 = flip * ((__popc(reg & g1) & 1) ? 1 : -1);
-    const int sg2 = flip * ((__popc(reg & g2) & 1) ? 1 : -1);
-    const int steps = len + 2 * VIT_EXTRA, j0 = len - VIT_EXTRA;
-    int cur = 0;
-    sm.metric[0][n] = 0;                                       // reset_decoder: all-zero for tail biting
-    for (int t0 = 0; t0 < steps; t0 += 256) {
-        __syncthreads();
-        if (t0 + n < steps) {
-            const int j = (j0 + t0 + n) % len;
-            sm.soft[3 * n] = coded[3 * j]; sm.soft[3 * n + 1] = coded[3 * j + 1]; sm.soft[3 * n + 2] = coded[3 * j + 2];
-        }
-        __syncthreads();
-        const int nst = min(256, steps - t0);
-        for (int s = 0; s < nst; s++) {
-            const int m = sm.soft[3 * s] * sg0 + sm.soft[3 * s + 1] * sg1 + sm.soft[3 * s + 2] * sg2;
-            const int e = sm.metric[cur][2 * b], o = sm.metric[cur][2 * b + 1];
-            const int pa = e + m, pc = o - m;
-            const bool take_e = pa > pc;
-            sm.metric[cur ^ 1][n] = take_e ? pa : pc;
-            const unsigned long long w = __ballot(!take_e);    // bit = 1: survivor came from 2b+1
-            if ((n & 63) == 0) dec[(size_t)(t0 + s) * 4 + (n >> 6)] = w;
-            cur ^= 1;
-            __syncthreads();
-        }
-    }
-    // end state: first maximum in state order (conv_dec.c:310-318)
-    {
-        int v = sm.metric[cur][n], idx = n;
-        for (int m = 32; m >= 1; m >>= 1) {
-            const int ov = __shfl_xor(v, m), oi = __shfl_xor(idx, m);
-            if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-        }
-        if ((n & 63) == 0) { sm.red_val[n >> 6] = v; sm.red_idx[n >> 6] = idx; }
-        __threadfence_block();
-        __syncthreads();
-        if (n == 0) {
-            for (int w = 1; w < 4; w++) if (sm.red_val[w] > v) { v = sm.red_val[w]; idx = sm.red_idx[w]; }
-            sm.state = idx;
-        }
-    }
-    // traceback: decisions staged through LDS 256 steps at a time, walked by one work-item
-    const int nchunks = (steps + 255) / 256;
-    uint32_t accw = 0; int accidx = -1;
-    for (int c = nchunks - 1; c >= 0; c--) {
-        const int t0 = c * 256, nst = min(256, steps - t0);
-        __syncthreads();
-        for (int k = n; k < 4 * nst; k += 256) sm.chunk[k] = dec[(size_t)t0 * 4 + k];
-        __syncthreads();
-        if (n == 0) {
-            unsigned state = (unsigned)sm.state;
-            for (int s = nst - 1; s >= 0; s--) {
-                const int t = t0 + s;
-                const unsigned bit = (unsigned)(sm.chunk[4 * s + (state >> 6)] >> (state & 63)) & 1u;
-                if (t >= VIT_EXTRA && t < len + VIT_EXTRA) {
-                    const int i = t - VIT_EXTRA;
-                    if ((i >> 5) != accidx) { if (accidx >= 0) out[accidx] = accw; accidx = i >> 5; accw = 0; }
-                    accw |= ((state >> 7) & 1u) << (i & 31);   // vals[state]: the newest input bit
-                }
-                state = ((state << 1) & 0xfeu) | bit;           // vstate_lshift
-            }
-            sm.state = (int)state;
-        }
-    }
-    if (n == 0 && accidx >= 0) out[accidx] = accw;
-    __threadfence_block();
-    __syncthreads();
-}
-
-// ---- the same trellis on ONE wave64, two steps per LDS round trip ------------------------------------------------------
-// Lane L reads old states 4L..4L+3 (one 16-byte LDS read).  Step t: butterflies 2L and 2L+1 give the four intermediate
-// states (i0 << 7) | (2L + xh); step t+1: butterflies L and L + 64 combine them into the four new states
-// (i1 << 7) | (i0 << 6) | L, written at stride 64 (conflict-free) into the other half of a ping-pong buffer, where they are
-// again states 4L'..4L'+3 of some lane L'.  Same eight compares per lane as two single steps, same tie rule, same int32
-// metrics -> bit-identical decisions; half the LDS latency and loop overhead per trellis step.
-// No workgroup barrier: a single-wave workgroup orders its own LDS traffic (WAVE_LDS_SYNC, wave_ops.h).
-// Decisions per step pair: one byte per lane -- bit i0 * 2 + xh for step t (1 = survivor from old state 4L + 2 xh + 1),
-// bit 4 + i1 * 2 + i0 for step t+1 (1 = survivor from xh = 1) -- so a step pair of the traceback needs ONE byte, the one
-// of lane n & 63: prev = ((n & 63) << 2) | xh << 1 | xl, read at a wave-uniform address from a chunk staged in LDS.
-struct K9WSmem { int metric[2][256]; };   // 2 KB per frame in flight (the traceback stages decisions in the same 2 KB): 32 decode
-                                         // workgroups per CU still leave room for k_am_block's 70 KB tile
-
-__device__ inline int k9_sign_word(unsigned b, unsigned g0, unsigned g1, unsigned g2)
-{
-    const unsigned reg = (b << 1) & 0xfeu;
-    const int s0 = (__popc(reg & g0) & 1) ? 1 : -1, s1 = (__popc(reg & g1) & 1) ? 1 : -1, s2 = (__popc(reg & g2) & 1) ? 1 : -1;
-    return (s0 & 0xff) | ((s1 & 0xff) << 8) | ((s2 & 0xff) << 16);
-}
-
-__device__ inline int k9_soft_word(const int8_t *coded, int j)
-{
-    return (coded[3 * j] & 0xff) | ((coded[3 * j + 1] & 0xff) << 8) | ((coded[3 * j + 2] & 0xff) << 16);
-}
-
-struct K9Signs { int a, b, c, d; };
-__device__ inline K9Signs k9_signs(int lane, unsigned g0, unsigned g1, unsigned g2)
-{
-    K9Signs sg;
-    sg.a = k9_sign_word(2u * lane, g0, g1, g2); sg.b = k9_sign_word(2u * lane + 1u, g0, g1, g2);             // step t: b = 2L + xh
-    sg.c = k9_sign_word((unsigned)lane, g0, g1, g2); sg.d = k9_sign_word((unsigned)lane + 64u, g0, g1, g2);   // step t+1: b = (i0 << 6) | L
-    return sg;
-}
-
-// A frame is steps = len + 2 * VIT_EXTRA trellis steps (even for every frame length of the AM path) = npairs step pairs, walked
-// forward in chunks of 64 step pairs and backward in chunks of 32.
-__host__ __device__ inline int k9_pairs(int len) { return (len + 2 * VIT_EXTRA) >> 1; }
-__host__ __device__ inline int k9_chunks(int len) { return (k9_pairs(len) + 63) >> 6; }
-
-// Forward pass over the chunks [c0, c1): the metrics are in sm.metric[0] on entry (every chunk but the frame's last is an even
-// number of step pairs, so a chunk boundary always finds them there); returns the half that holds them after the last pair.
-// Decisions are written for chunks >= cstore only (a segment wave's warm-up chunks belong to its predecessor), and the metrics
-// the wave enters chunk `cstore` with go to `snap` (k9_forward_fix checks them against the predecessor's end metrics).
-__device__ inline int k9_forward_chunks(const int8_t *coded, int len, const K9Signs &sg, unsigned long long *dec, K9WSmem &sm,
-                                        int c0, int c1, int cstore, int *snap)
-{
-    const int lane = threadIdx.x & 63;
-    const int j0 = len - VIT_EXTRA, npairs = k9_pairs(len);
-    int cur = 0;
-    for (int c = c0; c < c1; c++) {
-        const int p0 = c << 6, np = min(64, npairs - p0);
-        if (snap && c == cstore) *(int4 *)&snap[4 * lane] = *(const int4 *)&sm.metric[cur][4 * lane];
-        const bool store = c >= cstore;                        // wave-uniform
-        int aw0 = 0, aw1 = 0;                                   // this lane's step pair of the chunk
-        if (lane < np) {
-            const int t = 2 * (p0 + lane);
-            aw0 = k9_soft_word(coded, (j0 + t) % len);
-            aw1 = k9_soft_word(coded, (j0 + t + 1) % len);
-        }
-        for (int s = 0; s < np; s++) {
-            const int a0 = wave_readlane(aw0, s), a1 = wave_readlane(aw1, s);
-            const int mA = dot4_i8(a0, sg.a, 0), mB = dot4_i8(a0, sg.b, 0), nC = dot4_i8(a1, sg.c, 0), nD = dot4_i8(a1, sg.d, 0);
-            const int4 old = *(const int4 *)&sm.metric[cur][4 * lane];
-            // step t
-            const int e00 = old.x + mA, o00 = old.y - mA, e10 = old.x - mA, o10 = old.y + mA;   // xh = 0: i0 = 0, i0 = 1
-            const int e01 = old.z + mB, o01 = old.w - mB, e11 = old.z - mB, o11 = old.w + mB;   // xh = 1
-            const bool t00 = e00 > o00, t01 = e01 > o01, t10 = e10 > o10, t11 = e11 > o11;       // t[i0][xh]: survivor from the even predecessor
-            const int u00 = t00 ? e00 : o00, u01 = t01 ? e01 : o01, u10 = t10 ? e10 : o10, u11 = t11 ? e11 : o11;
-            // step t+1: new state (i1, i0, L) from u[i0][0] (even) and u[i0][1] (odd)
-            const int f00 = u00 + nC, p00 = u01 - nC, f10 = u00 - nC, p10 = u01 + nC;           // i0 = 0: i1 = 0, i1 = 1
-            const int f01 = u10 + nD, p01 = u11 - nD, f11 = u10 - nD, p11 = u11 + nD;           // i0 = 1
-            const bool r00 = f00 > p00, r01 = f01 > p01, r10 = f10 > p10, r11 = f11 > p11;       // r[i1][i0]
-            int *nxt = sm.metric[cur ^ 1];
-            nxt[lane] = r00 ? f00 : p00;                        // state (0, 0, L)
-            nxt[64 + lane] = r01 ? f01 : p01;                   // state (0, 1, L)
-            nxt[128 + lane] = r10 ? f10 : p10;                  // state (1, 0, L)
-            nxt[192 + lane] = r11 ? f11 : p11;                  // state (1, 1, L)
-            // this lane's eight decisions of the step pair in one byte: bit i0*2+xh for step t, bit 4+i1*2+i0 for step t+1
-            const unsigned dbyte = (t00 ? 0u : 1u) | (t01 ? 0u : 2u) | (t10 ? 0u : 4u) | (t11 ? 0u : 8u)
-                                 | (r00 ? 0u : 16u) | (r01 ? 0u : 32u) | (r10 ? 0u : 64u) | (r11 ? 0u : 128u);
-            if (store) ((uint8_t *)dec)[(size_t)(p0 + s) * 64 + lane] = (uint8_t)dbyte;     // one 64-byte row per step pair, fire and forget
-            cur ^= 1;
-            WAVE_LDS_SYNC();
-        }
-    }
-    return cur;
-}
-
-// end state: first maximum in state order (conv_dec.c:310-318); m = this lane's metrics of states 4L .. 4L+3
-__device__ inline unsigned k9_end_state(int4 m)
-{
-    const int lane = threadIdx.x & 63;
-    int v = m.x, idx = 4 * lane;
-    if (m.y > v) { v = m.y; idx = 4 * lane + 1; }
-    if (m.z > v) { v = m.z; idx = 4 * lane + 2; }
-    if (m.w > v) { v = m.w; idx = 4 * lane + 3; }
-    for (int k = 32; k >= 1; k >>= 1) {
-        const int ov = __shfl_xor(v, k), oi = __shfl_xor(idx, k);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    return (unsigned)wave_uniform(idx);
-}
-
-// Traceback over the 32-pair chunks c_hi - 1 .. c_lo (downwards) from `state`, two steps per iteration; a chunk's decisions are
-// staged in LDS (the metrics are dead: 2 KB = 32 step pairs) and looked up at a wave-uniform address.  Output words are written for
-// chunks < c_out only (the chunks above are a segment wave's run-in); `arrive` = the state on entering chunk c_out - 1.
-// Chunk c holds steps 64 c .. 64 c + 63 = frame bits 64 c - 32 .. 64 c + 31: words 2c - 1 (low half) and 2c (high half), and no
-// other chunk writes those words.
-__device__ inline unsigned k9_traceback_chunks(const unsigned long long *dec, int len, K9WSmem &sm, unsigned state, int c_hi, int c_lo, int c_out,
-                                               uint32_t *out, unsigned &arrive)
-{
-    const int lane = threadIdx.x & 63;
-    const int steps = len + 2 * VIT_EXTRA, npairs = k9_pairs(len);
-    unsigned long long *stage = (unsigned long long *)&sm.metric[0][0];
-    const uint8_t *db8 = (const uint8_t *)stage;
-    for (int c = c_hi - 1; c >= c_lo; c--) {
-        if (c == c_out - 1) arrive = state;
-        const int p0 = c << 5, np = min(32, npairs - p0);
-        for (int k = lane; k < 8 * np; k += 64) stage[k] = dec[(size_t)p0 * 8 + k];
-        WAVE_LDS_SYNC();
-        unsigned long long obits = 0;                           // output bits of steps 2 p0 .. 2 p0 + 63
-        for (int s = np - 1; s >= 0; s--) {
-            const unsigned i1 = state >> 7, i0 = (state >> 6) & 1u, L = state & 63u;
-            const unsigned q = db8[64 * s + L];                  // lane L's decision byte of this step pair: one broadcast read
-            const unsigned xh = (q >> (4 + 2 * i1 + i0)) & 1u;
-            const unsigned xl = (q >> (2 * i0 + xh)) & 1u;
-            obits = (obits << 2) | (unsigned long long)(i0 | (i1 << 1));    // the pair walked last (s = 0) ends in bits 0..1
-            state = (unsigned)wave_uniform((int)((L << 2) | (xh << 1) | xl));
-        }
-        WAVE_LDS_SYNC();
-        if (lane == 0 && c < c_out) {
-            const int wl = 2 * c - 1, wh = 2 * c;
-            if (wl >= 0 && wl * 32 < len) out[wl] = (uint32_t)obits;
-            if (wh * 32 < len && 2 * p0 + 32 < steps) out[wh] = (uint32_t)(obits >> 32);
-        }
-    }
-    return state;
-}
-
-__device__ inline void viterbi_k9_wave(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2,
-                                       unsigned long long *dec, uint32_t *out, K9WSmem &sm, int phases = 3)
-{
-    const int lane = threadIdx.x & 63;
-    const K9Signs sg = k9_signs(lane, g0, g1, g2);
-    const int npairs = k9_pairs(len), nchunks = k9_chunks(len);
-    for (int k = 0; k < 4; k++) sm.metric[0][4 * lane + k] = 0;   // reset_decoder: all-zero for tail biting
-    WAVE_LDS_SYNC();
-    const int cur = (phases & 1) ? k9_forward_chunks(coded, len, sg, dec, sm, 0, nchunks, 0, nullptr) : 0;
-    unsigned state = k9_end_state(*(const int4 *)&sm.metric[cur][4 * lane]);
-    __threadfence_block();
-    __syncthreads();
-    unsigned arrive = 0;
-    if (phases & 2) k9_traceback_chunks(dec, len, sm, state, (npairs + 31) >> 5, 0, (npairs + 31) >> 5, out, arrive);
-    __threadfence_block();
-    __syncthreads();
-}
-
-// ---- the same decode in segment waves ---------------------------------------------------------------------------------
-// FORWARD.  The chunks of a frame are cut into up to K9_GMAX segments, one wave each, all running at once.  Segment g > 0 cannot
-// know the metrics its first step starts from, so it starts `warm` chunks early from all-zero metrics -- survivor paths merge
-// within a few constraint lengths, after which metric DIFFERENCES no longer depend on where the wave started -- and notes the
-// metrics it reaches its first own step with (snap).  Decisions depend on metric differences only (int32 sums, no saturation,
-// no normalisation): k9_forward_fix walks the boundaries in order and accepts segment g iff snap[g] - snap[g][0] equals the TRUE
-// end metrics of segment g - 1 minus their element 0; otherwise it re-runs segment g from those.  Exact for any segment count and
-// any warm-up, including 0 (the test hook that forces every repair).
-// TRACEBACK.  Segment g < last starts K9_TB_RUNIN chunks above its own chunks from state 0 -- survivors merge going backwards
-// too -- and notes the state it enters its own chunks with (arrive) and leaves them with (leave); the last segment starts from
-// the true end state.  k9_traceback_fix walks down from the last segment: segment g is accepted iff arrive[g] is the state the
-// segment above truly left with, else it is walked again from that state.  Output words are per chunk, so a repair rewrites
-// exactly the words of its segment.
-// K9_GMAX, K9_WARM (chunks of 64 step pairs) and K9_TB_RUNIN (chunks of 32 step pairs): nrsc5_dev.h
-
-__host__ __device__ inline int k9_seg_chunks(int len, int G) { return (k9_chunks(len) + G - 1) / G; }
-__host__ __device__ inline int k9_seg_count(int len, int G) { const int per = k9_seg_chunks(len, G); return (k9_chunks(len) + per - 1) / per; }
-
-__device__ inline void k9_forward_segment(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2, unsigned long long *dec,
-                                          K9Meta &meta, K9WSmem &sm, int g, int G, int warm)
-{
-    const int lane = threadIdx.x & 63;
-    const int nch = k9_chunks(len), per = k9_seg_chunks(len, G);
-    const int c0 = g * per, c1 = min(nch, c0 + per);
-    if (c0 >= nch) return;                                     // wave-uniform
-    const K9Signs sg = k9_signs(lane, g0, g1, g2);
-    for (int k = 0; k < 4; k++) sm.metric[0][4 * lane + k] = 0;
-    WAVE_LDS_SYNC();
-    const int cur = k9_forward_chunks(coded, len, sg, dec, sm, g ? max(0, c0 - warm) : 0, c1, c0, g ? meta.snap[g] : nullptr);
-    *(int4 *)&meta.uend[g][4 * lane] = *(const int4 *)&sm.metric[cur][4 * lane];
-}
-
-// one wave per frame, after every segment wave has finished: returns the end state of the frame
-__device__ inline unsigned k9_forward_fix(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2, unsigned long long *dec,
-                                          K9Meta &meta, K9WSmem &sm, int G, unsigned *stats)
-{
-    const int lane = threadIdx.x & 63;
-    const int nch = k9_chunks(len), per = k9_seg_chunks(len, G), nseg = k9_seg_count(len, G);
-    const K9Signs sg = k9_signs(lane, g0, g1, g2);
-    int4 tend = *(const int4 *)&meta.uend[0][4 * lane];        // true end metrics of the segment below, up to a constant
-    unsigned repairs = 0;
-    for (int g = 1; g < nseg; g++) {
-        const int4 a = *(const int4 *)&meta.snap[g][4 * lane];
-        const int a0 = wave_readlane(a.x, 0), b0 = wave_readlane(tend.x, 0);
-        const bool same = a.x - a0 == tend.x - b0 && a.y - a0 == tend.y - b0 && a.z - a0 == tend.z - b0 && a.w - a0 == tend.w - b0;
-        if (__all(same)) { tend = *(const int4 *)&meta.uend[g][4 * lane]; continue; }
-        *(int4 *)&sm.metric[0][4 * lane] = tend;
-        WAVE_LDS_SYNC();
-        const int c0 = g * per, c1 = min(nch, c0 + per);
-        const int cur = k9_forward_chunks(coded, len, sg, dec, sm, c0, c1, c0, nullptr);
-        tend = *(const int4 *)&sm.metric[cur][4 * lane];
-        WAVE_LDS_SYNC();
-        repairs++;
-    }
-    if (stats && lane == 0) { atomicAdd(&stats[0], (unsigned)(nseg - 1)); if (repairs) atomicAdd(&stats[1], repairs); }
-    return k9_end_state(tend);
-}
-
-__device__ inline void k9_traceback_segment(const unsigned long long *dec, int len, K9Meta &meta, K9WSmem &sm, uint32_t *out, int g, int G, int runin)
-{
-    const int nch = k9_chunks(len), per = k9_seg_chunks(len, G), nseg = k9_seg_count(len, G);
-    if (g >= nseg) return;                                     // wave-uniform
-    const int ntb = (k9_pairs(len) + 31) >> 5;
-    const int lo = 2 * g * per, hi = min(ntb, 2 * min(nch, (g + 1) * per));
-    const bool last = g == nseg - 1;
-    unsigned arrive = last ? meta.end_state : 0u;
-    const unsigned leave = k9_traceback_chunks(dec, len, sm, arrive, last ? hi : min(ntb, hi + runin), lo, hi, out, arrive);
-    if ((threadIdx.x & 63) == 0) { meta.arrive[g] = arrive; meta.leave[g] = leave; }
-}
-
-// one wave per frame, after every traceback segment wave has finished
-__device__ inline void k9_traceback_fix(const unsigned long long *dec, int len, K9Meta &meta, K9WSmem &sm, uint32_t *out, int G, unsigned *stats)
-{
-    const int nch = k9_chunks(len), per = k9_seg_chunks(len, G), nseg = k9_seg_count(len, G);
-    const int ntb = (k9_pairs(len) + 31) >> 5;
-    unsigned truth = (unsigned)wave_uniform((int)meta.leave[nseg - 1]), repairs = 0;
-    for (int g = nseg - 2; g >= 0; g--) {
-        if ((unsigned)wave_uniform((int)meta.arrive[g]) == truth) { truth = (unsigned)wave_uniform((int)meta.leave[g]); continue; }
-        const int lo = 2 * g * per, hi = min(ntb, 2 * min(nch, (g + 1) * per));
-        unsigned arrive = 0;
-        truth = k9_traceback_chunks(dec, len, sm, truth, hi, lo, hi, out, arrive);
-        repairs++;
-    }
-    if (stats && (threadIdx.x & 63) == 0) { atomicAdd(&stats[2], (unsigned)(nseg - 1)); if (repairs) atomicAdd(&stats[3], repairs); }
-    __threadfence_block();
-    __syncthreads();
-}
-
-// re-encode the decoded (still scrambled) bits and count sign disagreements at unpunctured positions
-// (bit_errors, decode.c:234-261); returns the block-wide total in every work-item
-__device__ inline int am_bit_errors(const int8_t *coded, const uint32_t *bits, int len, unsigned g0, unsigned g1, unsigned g2,
-                                    unsigned pmask, int plen, int *red /* [4] */)
-{
-    int errors = 0;
-    for (int i = threadIdx.x; i < len; i += blockDim.x) {
-        unsigned r = 0;                                        // r bit 8-k = bits[i-k]
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            int q = i - k; if (q < 0) q += len;
-            r |= ((bits[q >> 5] >> (q & 31)) & 1u) << (8 - k);
-        }
-        const int j = 3 * i;
-        if (((pmask >> (j % plen)) & 1u) && ((coded[j] > 0) != (int)(__popc(r & g0) & 1))) errors++;
-        if (((pmask >> ((j + 1) % plen)) & 1u) && ((coded[j + 1] > 0) != (int)(__popc(r & g1) & 1))) errors++;
-        if (((pmask >> ((j + 2) % plen)) & 1u) && ((coded[j + 2] > 0) != (int)(__popc(r & g2) & 1))) errors++;
-    }
-    errors = wave_sum_i32(errors);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = errors;
-    __syncthreads();
-    int total = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) total += red[w];
-    return total;
-}
-
-constexpr unsigned GEN_E1_0 = 0561, GEN_E1_1 = 0657, GEN_E1_2 = 0711;     // decode.c:47-53
-constexpr unsigned GEN_E2_0 = 0561, GEN_E2_1 = 0753, GEN_E2_2 = 0711;     // decode.c:55-61
-constexpr unsigned PUNCT_E1 = 0x7f6d, PUNCT_E2 = 0x0d;                    // bit k = pattern[k]: {1,0,1,1,0,1,1,0,1,1,1,1,1,1,1}, {1,0,1,1,0,0}
 
 // =====================================================================================================
 // the block step
@@ -1194,62 +659,6 @@ __global__ __launch_bounds__(NT) void k_am_block(DevTables tb, DevBuffers db, co
     }
 }
 
-// ---- this block's P1 frame, and after block 7 the P3 frame (decode_process_p1_p3_am, decode.c:507-554) ----------
-__global__ __launch_bounds__(64) void k_am_viterbi(DevTables tb, DevBuffers db, const int *ids, int l2_feedback)
-{
-    const int s = stream_of(ids, blockIdx.y);
-    const StreamState &st = db.state[s];
-    AmStream &am = db.am[s];
-    if (!st.active || am.dec_bc < 0 || am.am_diversity_wait != 0) return;      // block-uniform
-    const int role = blockIdx.x, bc = am.dec_bc;                                 // 0: P1, 1: P3 (in-order mode)
-    if (role == 1 && (bc != 7 || am.dec_rdbi)) return;
-    __shared__ K9WSmem k9;
-    __shared__ int red[4];
-    const bool ma3 = am.dec_psmi == AM_MA3;
-    uint32_t *slot = db.p1_ring + ((size_t)s * db.p1_slots + am.frame_slot) * P1_WORDS;
-    unsigned long long *dec = db.am_dec + (size_t)s * (size_t)(8 * AM_DEC_P1 + AM_DEC_P3);
-    BlockRecord &rec = db.records[(size_t)s * db.rec_cap + am.dec_record];
-    if (role == 0) {
-        const int8_t *in = db.am_vit + (size_t)s * db.am_nvit * 2 * AM_VIT + (size_t)bc * AM_P1_LEN * 3;
-        uint32_t *out = slot + bc * AM_P1_WORDS;
-        viterbi_k9_wave(in, AM_P1_LEN, GEN_E1_0, GEN_E1_1, GEN_E1_2, dec, out, k9);
-        const int err = am_bit_errors(in, out, AM_P1_LEN, GEN_E1_0, GEN_E1_1, GEN_E1_2, PUNCT_E1, 15, red);
-        for (int w = threadIdx.x; w < AM_P1_WORDS; w += 64)      // descramble; the last word holds 6 frame bits
-            out[w] = (out[w] ^ tb.scr_p1[w]) & (w == AM_P1_WORDS - 1 ? (1u << (AM_P1_LEN & 31)) - 1u : 0xffffffffu);
-        __threadfence_block();
-        __syncthreads();
-        static_assert(sizeof(L2Smem) <= sizeof(K9WSmem), "L2 scratch aliases the trellis scratch");
-        L2Smem &l2 = *(L2Smem *)&k9;                           // the trellis scratch is dead by now
-        const bool hdr_ok = l2_feedback ? l2_first_header_ok_am_block(out, l2) : true;     // frame.c:535-540 for the 466-byte AM PDU
-        if (threadIdx.x == 0) {
-            atomicAdd(&am.am_errors, (unsigned)err);
-            atomicOr(&rec.flags, (uint32_t)REC_P1);
-            rec.p1_slot = am.frame_slot;
-            StreamState &stw = db.state[s];
-            if (!hdr_ok && stw.sync_state == SYNC_FINE) { stw.sync_state = SYNC_NONE; rec.state_after = SYNC_NONE; atomicOr(&rec.flags, (uint32_t)REC_LOST_SYNC); }
-        }
-    } else {
-        const int8_t *in = db.am_vit + (size_t)s * db.am_nvit * 2 * AM_VIT + AM_VIT;
-        uint32_t *out = slot + AM_P3_WORD0;
-        const int len = ma3 ? AM_P3_LEN_MA3 : AM_P3_LEN_MA1;
-        int err;
-        if (!ma3) {
-            viterbi_k9_wave(in, len, GEN_E2_0, GEN_E2_1, GEN_E2_2, dec + (size_t)8 * AM_DEC_P1, out, k9);
-            err = am_bit_errors(in, out, len, GEN_E2_0, GEN_E2_1, GEN_E2_2, PUNCT_E2, 6, red);
-        } else {
-            viterbi_k9_wave(in, len, GEN_E1_0, GEN_E1_1, GEN_E1_2, dec + (size_t)8 * AM_DEC_P1, out, k9);
-            err = am_bit_errors(in, out, len, GEN_E1_0, GEN_E1_1, GEN_E1_2, PUNCT_E1, 15, red);
-        }
-        const int words = (len + 31) / 32;
-        const uint32_t tailmask = (len & 31) ? (1u << (len & 31)) - 1u : 0xffffffffu;
-        for (int w = threadIdx.x; w < words; w += 64) out[w] = (out[w] ^ tb.scr_p1[w]) & (w == words - 1 ? tailmask : 0xffffffffu);
-        if (threadIdx.x == 0) {
-            atomicAdd(&am.am_errors, (unsigned)err);
-            atomicOr(&rec.flags, (uint32_t)REC_P3);
-        }
-    }
-}
-
 // ---- after block 7: BER of the frame just decoded, then interleaver_ma1 for the frame just received -------------
 // Output-centric and table-driven: every depunctured trellis input looks up which bit of which hard-symbol matrix it is
 // (DevTables::am_deint_*, built from decode.c:66-231 by engine.hip), the main (m*) bits pass through the 3-frame
@@ -1299,9 +708,7 @@ __device__ inline void am_deinterleave_slice(const DevTables &tb, const DevBuffe
     const int tid = threadIdx.x;
     const int vslot = parity < 0 ? 0 : parity;                 // window pipeline: one set of trellis inputs per window in flight
     if (part == 0 && tid == 0 && parity < 0 && am.am_diversity_wait == 0) {
-        unsigned total = 8 * (AM_P1_LEN * 12 / 5);
-        if (!am.dec_rdbi) total += ma3 ? AM_P3_LEN_MA3 * 12 / 5 : AM_P3_LEN_MA1 * 3 / 2;
-        db.records[(size_t)s * db.rec_cap + am.dec_record].ber = (float)am.am_errors / (float)total;
+        db.records[(size_t)s * db.rec_cap + am.dec_record].ber = (float)am.am_errors / (float)am_frame_coded_bits(am.dec_psmi, am.dec_rdbi);
     }
     // the frame's four hard-symbol matrices (25.6 KB) are gathered from byte by byte in interleaver order: stage them in LDS
     // first (the scattered byte loads were what the kernel waited for)
@@ -1359,164 +766,6 @@ __global__ __launch_bounds__(AM_IL_THREADS) void k_am_interleave(DevTables tb, D
     }
 }
 
-// ---- window pipeline: all nine frames of an L1 frame decode concurrently on a decode stream ---------------------------
-// Four launches (the P3 frame is 6.4 / 8 times a P1 frame: as ONE wave it kept the launch -- and a decode stream -- alive for
-// 4-5 ms after the P1 waves had gone; in K9_GMAX segment waves every wave of the launch is about one P1 frame long):
-//   k_am_decode_fwd     forward pass: 8 P1 waves, G P3 segment waves, 8 PIDS frames (whole: 144 steps)
-//   k_am_decode_fix     P3: segment boundaries checked / re-run, end state
-//   k_am_decode_tb      traceback: P1 frames whole + BER, descramble, first-header verdict; P3 in G segment waves
-//   k_am_decode_finish  P3: traceback boundaries checked / re-walked, BER, descramble; frame accounting
-struct AmDecodeFrame { const int8_t *in; uint32_t *out; unsigned long long *dec; int len; unsigned g0, g1, g2; };
-
-__device__ inline AmDecodeFrame am_decode_frame(const DevBuffers &db, const AmJob &job, int s, int parity, int lane_id, int role)
-{
-    AmDecodeFrame f;
-    const int8_t *vit = db.am_vit + ((size_t)s * db.am_nvit + parity) * 2 * AM_VIT;
-    uint32_t *slot = db.p1_ring + ((size_t)s * db.p1_slots + job.slot) * P1_WORDS;
-    unsigned long long *dec = db.am_dec + ((size_t)lane_id * db.nstreams_alloc + s) * (size_t)(8 * AM_DEC_P1 + AM_DEC_P3);
-    if (role < 8) {
-        f.in = vit + (size_t)role * AM_P1_LEN * 3; f.out = slot + role * AM_P1_WORDS; f.dec = dec + (size_t)role * AM_DEC_P1;
-        f.len = AM_P1_LEN; f.g0 = GEN_E1_0; f.g1 = GEN_E1_1; f.g2 = GEN_E1_2;
-    } else {
-        const bool ma3 = job.psmi == AM_MA3;
-        f.in = vit + AM_VIT; f.out = slot + AM_P3_WORD0; f.dec = dec + (size_t)8 * AM_DEC_P1;
-        f.len = ma3 ? AM_P3_LEN_MA3 : AM_P3_LEN_MA1;
-        f.g0 = ma3 ? GEN_E1_0 : GEN_E2_0; f.g1 = ma3 ? GEN_E1_1 : GEN_E2_1; f.g2 = ma3 ? GEN_E1_2 : GEN_E2_2;
-    }
-    return f;
-}
-
-// the frame is decoded: count it, and the last of the L1 frame's decodes closes the job (nrsc5_report_ber's value, decode.c:545)
-__device__ inline void am_decode_account(const DevBuffers &db, AmJob &job, int s, int err)
-{
-    if (threadIdx.x != 0) return;
-    atomicAdd(&job.errors, (unsigned)err);
-    __threadfence();
-    const int expected = job.rdbi ? 8 : 9;
-    if (atomicAdd(&job.done, 1) == expected - 1) {
-        const bool ma3 = job.psmi == AM_MA3;
-        unsigned total = 8 * (AM_P1_LEN * 12 / 5);
-        if (!job.rdbi) total += ma3 ? AM_P3_LEN_MA3 * 12 / 5 : AM_P3_LEN_MA1 * 3 / 2;
-        db.am_ber[(size_t)s * db.p1_slots + job.slot] = (float)atomicAdd(&job.errors, 0u) / (float)total;
-        job.pad = db.l2_am_ring ? (job.rdbi ? 0xff : 0x1ff) : 0;      // frames k_l2_index_am_window owes their index
-        job.valid = 0;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_am_decode_fwd(DevTables tb, DevBuffers db, const int *ids, int parity, int lane_id, int G, int warm)
-{
-    const int s = stream_of(ids, blockIdx.y), role = blockIdx.x;           // 0..7: P1 frame of that block, 8..8+G-1: P3 segment, then 8 PIDS frames
-    __shared__ K9WSmem k9;
-    if (role >= 8 + G) {
-        // decode_process_pids_am's trellis (decode.c:502-504) for the block processed in step `pb` of this window
-        const int pb = role - 8 - G;
-        int *recp = db.am_pids_rec + ((size_t)s * NWIN + parity) * 8 + pb;
-        const int r = *recp;
-        if (r < 0) return;                                                 // wave-uniform
-        __shared__ uint32_t pout[4];
-        const int8_t *stage = db.am_pids_stage + (((size_t)s * NWIN + parity) * 8 + pb) * (3 * PIDS_LEN);
-        unsigned long long *pdec = db.am_dec + ((size_t)lane_id * db.nstreams_alloc + s) * (size_t)(8 * AM_DEC_P1 + AM_DEC_P3)
-                                 + (size_t)8 * AM_DEC_P1 + AM_DEC_P3 - (size_t)(9 - pb) * 4 * (PIDS_LEN + 64);   // tail of the P3 scratch: its frame is shorter than AM_P3_LEN_MA3 + 64 only by the slack reserved here
-        viterbi_k9_wave(stage, PIDS_LEN, GEN_E2_0, GEN_E2_1, GEN_E2_2, pdec, pout, k9);
-        if (threadIdx.x == 0) {
-            BlockRecord &rec = db.records[(size_t)s * db.rec_cap + r];
-            const uint32_t p[3] = { pout[0] ^ tb.scr_pids[0], pout[1] ^ tb.scr_pids[1], (pout[2] ^ tb.scr_pids[2]) & 0xffffu };
-            rec.pids[0] = p[0]; rec.pids[1] = p[1]; rec.pids[2] = p[2];
-            if (pids_crc_ok(p)) atomicOr(&rec.flags, (uint32_t)REC_PIDS_CRC);
-            *recp = -1;
-        }
-        return;
-    }
-    const AmJob &job = db.am_job[(size_t)s * NWIN + parity];
-    if (!job.valid) return;                                                // wave-uniform
-    if (role >= 8 && job.rdbi) return;
-    K9Meta &meta = db.am_k9meta[(size_t)lane_id * db.nstreams_alloc + s];
-    const AmDecodeFrame f = am_decode_frame(db, job, s, parity, lane_id, role);
-    if (role < 8) {
-        const int lane = threadIdx.x;
-        const K9Signs sg = k9_signs(lane, f.g0, f.g1, f.g2);
-        for (int k = 0; k < 4; k++) k9.metric[0][4 * lane + k] = 0;
-        WAVE_LDS_SYNC();
-        const int cur = k9_forward_chunks(f.in, f.len, sg, f.dec, k9, 0, k9_chunks(f.len), 0, nullptr);
-        const unsigned end = k9_end_state(*(const int4 *)&k9.metric[cur][4 * lane]);
-        if (lane == 0) meta.p1_end[role] = end;
-    } else {
-        k9_forward_segment(f.in, f.len, f.g0, f.g1, f.g2, f.dec, meta, k9, role - 8, G, warm);
-    }
-}
-
-__global__ __launch_bounds__(64) void k_am_decode_fix(DevBuffers db, const int *ids, int parity, int lane_id, int G)
-{
-    const int s = stream_of(ids, blockIdx.x);
-    const AmJob &job = db.am_job[(size_t)s * NWIN + parity];
-    if (!job.valid || job.rdbi) return;                                    // wave-uniform
-    __shared__ K9WSmem k9;
-    K9Meta &meta = db.am_k9meta[(size_t)lane_id * db.nstreams_alloc + s];
-    const AmDecodeFrame f = am_decode_frame(db, job, s, parity, lane_id, 8);
-    const unsigned end = k9_forward_fix(f.in, f.len, f.g0, f.g1, f.g2, f.dec, meta, k9, G, db.am_k9stats);
-    if (threadIdx.x == 0) meta.end_state = end;
-}
-
-__global__ __launch_bounds__(64) void k_am_decode_tb(DevTables tb, DevBuffers db, const int *ids, int parity, int lane_id, int G, int runin, int l2_feedback)
-{
-    const int s = stream_of(ids, blockIdx.y), role = blockIdx.x;           // 0..7: P1 frame of that block, 8..8+G-1: P3 segment
-    AmJob &job = db.am_job[(size_t)s * NWIN + parity];
-    if (!job.valid) return;                                                // wave-uniform
-    if (role >= 8 && job.rdbi) return;
-    __shared__ K9WSmem k9;
-    __shared__ int red[4];
-    K9Meta &meta = db.am_k9meta[(size_t)lane_id * db.nstreams_alloc + s];
-    const AmDecodeFrame f = am_decode_frame(db, job, s, parity, lane_id, role);
-    if (role >= 8) { k9_traceback_segment(f.dec, f.len, meta, k9, f.out, role - 8, G, runin); return; }
-    unsigned arrive = 0;
-    const int ntb = (k9_pairs(f.len) + 31) >> 5;
-    k9_traceback_chunks(f.dec, f.len, k9, (unsigned)wave_uniform((int)meta.p1_end[role]), ntb, 0, ntb, f.out, arrive);
-    __threadfence_block();
-    __syncthreads();
-    uint32_t *out = f.out;
-    const int err = am_bit_errors(f.in, out, AM_P1_LEN, GEN_E1_0, GEN_E1_1, GEN_E1_2, PUNCT_E1, 15, red);
-    for (int w = threadIdx.x; w < AM_P1_WORDS; w += 64)
-        out[w] = (out[w] ^ tb.scr_p1[w]) & (w == AM_P1_WORDS - 1 ? (1u << (AM_P1_LEN & 31)) - 1u : 0xffffffffu);
-    __threadfence_block();
-    __syncthreads();
-    if (l2_feedback) {                                         // frame.c:535-540: file the verdict for the block that delivers this PDU
-        L2Smem &l2 = *(L2Smem *)&k9;                           // the trellis scratch is dead by now
-        const bool ok = l2_first_header_ok_am_block(out, l2);
-        if (threadIdx.x == 0) { __threadfence(); atomicExch(&job.verdict[role], ok ? 1 : 2); }
-    }
-    am_decode_account(db, job, s, err);
-}
-
-__global__ __launch_bounds__(64) void k_am_decode_finish(DevTables tb, DevBuffers db, const int *ids, int parity, int lane_id, int G)
-{
-    const int s = stream_of(ids, blockIdx.x);
-    AmJob &job = db.am_job[(size_t)s * NWIN + parity];
-    if (!job.valid || job.rdbi) return;                                    // wave-uniform
-    __shared__ K9WSmem k9;
-    __shared__ int red[4];
-    K9Meta &meta = db.am_k9meta[(size_t)lane_id * db.nstreams_alloc + s];
-    const AmDecodeFrame f = am_decode_frame(db, job, s, parity, lane_id, 8);
-    k9_traceback_fix(f.dec, f.len, meta, k9, f.out, G, db.am_k9stats);
-    const bool ma3 = job.psmi == AM_MA3;
-    const int err = ma3 ? am_bit_errors(f.in, f.out, f.len, GEN_E1_0, GEN_E1_1, GEN_E1_2, PUNCT_E1, 15, red)
-                        : am_bit_errors(f.in, f.out, f.len, GEN_E2_0, GEN_E2_1, GEN_E2_2, PUNCT_E2, 6, red);
-    const int words = (f.len + 31) / 32;
-    const uint32_t tailmask = (f.len & 31) ? (1u << (f.len & 31)) - 1u : 0xffffffffu;
-    for (int w = threadIdx.x; w < words; w += 64) f.out[w] = (f.out[w] ^ tb.scr_p1[w]) & (w == words - 1 ? tailmask : 0xffffffffu);
-    am_decode_account(db, job, s, err);
-}
-
-void launch_am_decode(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int lane_id, int l2_feedback, hipStream_t st,
-                      int segments, int warm, int runin)
-{
-    const int G = segments < 1 ? 1 : segments > K9_GMAX ? K9_GMAX : segments;
-    hipLaunchKernelGGL(k_am_decode_fwd, dim3(8 + G + 8, nstreams), dim3(64), 0, st, tb, db, stream_ids, parity, lane_id, G, warm);
-    hipLaunchKernelGGL(k_am_decode_fix, dim3(nstreams), dim3(64), 0, st, db, stream_ids, parity, lane_id, G);
-    hipLaunchKernelGGL(k_am_decode_tb, dim3(8 + G, nstreams), dim3(64), 0, st, tb, db, stream_ids, parity, lane_id, G, runin, l2_feedback);
-    hipLaunchKernelGGL(k_am_decode_finish, dim3(nstreams), dim3(64), 0, st, tb, db, stream_ids, parity, lane_id, G);
-    if (db.l2_am_ring) launch_l2_index_am_window(db, nstreams, stream_ids, parity, st);
-}
-
 void launch_am_step(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st, int l2_feedback, int pipeline_parity, int slot, int window)
 {
     // (per device: the attribute belongs to the function as loaded on the current device -- one process may drive several, include/nrsc5hip.h)
@@ -1529,73 +778,8 @@ void launch_am_step(const DevTables &tb, const DevBuffers &db, int nstreams, con
     }
     if (pipeline_parity >= 0) hipLaunchKernelGGL(k_am_block<512>, dim3(nstreams), dim3(512), sizeof(AmBlockSmem), st, tb, db, stream_ids, 1, pipeline_parity, slot);
     else hipLaunchKernelGGL(k_am_block<256>, dim3(nstreams), dim3(256), sizeof(AmBlockSmem), st, tb, db, stream_ids, 0, pipeline_parity, slot);
-    if (pipeline_parity < 0) {
-        hipLaunchKernelGGL(k_am_viterbi, dim3(2, nstreams), dim3(64), 0, st, tb, db, stream_ids, l2_feedback);
-        if (db.l2_am_ring) launch_l2_index_am_step(db, nstreams, stream_ids, st);
-    }
+    if (pipeline_parity < 0) launch_am_decode_in_order(tb, db, nstreams, stream_ids, l2_feedback, st);
     hipLaunchKernelGGL(k_am_interleave, dim3(AM_IL_PARTS, nstreams), dim3(AM_IL_THREADS), 0, st, tb, db, stream_ids, pipeline_parity, window);
-}
-
-// ---- stage-level entry: decode `nframes` independent K=9 frames (parity tests) ------------------------------------
-__global__ __launch_bounds__(256) void k_viterbi_k9_frames(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2,
-                                                           unsigned long long *dec, uint32_t *out)
-{
-    __shared__ K9Smem k9;
-    const int f = blockIdx.x;
-    viterbi_k9_block(coded + (size_t)f * 3 * len, len, g0, g1, g2, dec + (size_t)f * 4 * (len + 64), out + (size_t)f * ((len + 31) / 32), k9);
-}
-__global__ __launch_bounds__(64) void k_viterbi_k9_frames_wave(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2,
-                                                               unsigned long long *dec, uint32_t *out, int phases)
-{
-    __shared__ K9WSmem k9;
-    const int f = blockIdx.x;
-    viterbi_k9_wave(coded + (size_t)f * 3 * len, len, g0, g1, g2, dec + (size_t)f * 4 * (len + 64), out + (size_t)f * ((len + 31) / 32), k9, phases);
-}
-// the segment-wave form, one launch per stage (what k_am_decode_* do for the P3 frame)
-__global__ __launch_bounds__(64) void k_k9seg_fwd(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2, unsigned long long *dec, K9Meta *meta, int G, int warm)
-{
-    __shared__ K9WSmem k9;
-    const int f = blockIdx.y;
-    k9_forward_segment(coded + (size_t)f * 3 * len, len, g0, g1, g2, dec + (size_t)f * 4 * (len + 64), meta[f], k9, (int)blockIdx.x, G, warm);
-}
-__global__ __launch_bounds__(64) void k_k9seg_fix(const int8_t *coded, int len, unsigned g0, unsigned g1, unsigned g2, unsigned long long *dec, K9Meta *meta, int G, unsigned *stats)
-{
-    __shared__ K9WSmem k9;
-    const int f = blockIdx.x;
-    const unsigned end = k9_forward_fix(coded + (size_t)f * 3 * len, len, g0, g1, g2, dec + (size_t)f * 4 * (len + 64), meta[f], k9, G, stats);
-    if (threadIdx.x == 0) meta[f].end_state = end;
-}
-__global__ __launch_bounds__(64) void k_k9seg_tb(const unsigned long long *dec, int len, K9Meta *meta, uint32_t *out, int G, int runin)
-{
-    __shared__ K9WSmem k9;
-    const int f = blockIdx.y;
-    k9_traceback_segment(dec + (size_t)f * 4 * (len + 64), len, meta[f], k9, out + (size_t)f * ((len + 31) / 32), (int)blockIdx.x, G, runin);
-}
-__global__ __launch_bounds__(64) void k_k9seg_finish(const unsigned long long *dec, int len, K9Meta *meta, uint32_t *out, int G, unsigned *stats)
-{
-    __shared__ K9WSmem k9;
-    const int f = blockIdx.x;
-    k9_traceback_fix(dec + (size_t)f * 4 * (len + 64), len, meta[f], k9, out + (size_t)f * ((len + 31) / 32), G, stats);
-}
-
-void launch_viterbi_k9_frames(const int8_t *coded, int len, int nframes, unsigned g0, unsigned g1, unsigned g2,
-                              unsigned long long *dec, uint32_t *out, hipStream_t st, int phases, K9Meta *meta, int segments, int warm, int runin, unsigned *stats)
-{
-    // frames longer than a PIDS frame take the production wave form (in segment waves when `meta` is given); 80-bit frames the
-    // 256-work-item form
-    if (len > 80 && meta) {
-        const int G = segments < 1 ? 1 : segments > K9_GMAX ? K9_GMAX : segments;
-        if (phases & 1) {
-            hipLaunchKernelGGL(k_k9seg_fwd, dim3(G, nframes), dim3(64), 0, st, coded, len, g0, g1, g2, dec, meta, G, warm);
-            hipLaunchKernelGGL(k_k9seg_fix, dim3(nframes), dim3(64), 0, st, coded, len, g0, g1, g2, dec, meta, G, stats);
-        }
-        if (phases & 2) {
-            hipLaunchKernelGGL(k_k9seg_tb, dim3(G, nframes), dim3(64), 0, st, dec, len, meta, out, G, runin);
-            hipLaunchKernelGGL(k_k9seg_finish, dim3(nframes), dim3(64), 0, st, dec, len, meta, out, G, stats);
-        }
-    }
-    else if (len > 80) hipLaunchKernelGGL(k_viterbi_k9_frames_wave, dim3(nframes), dim3(64), 0, st, coded, len, g0, g1, g2, dec, out, phases);
-    else hipLaunchKernelGGL(k_viterbi_k9_frames, dim3(nframes), dim3(256), 0, st, coded, len, g0, g1, g2, dec, out);
 }
 
 }  // namespace nrsc5

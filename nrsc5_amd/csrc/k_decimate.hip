@@ -11,8 +11,6 @@
 
 namespace nrsc5 {
 
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 __device__ inline int q15_of_u8(unsigned x) { return ((int)x - 127) * 64; }             // U8_Q15, defines.h:93
 
 // one output component from the 15-sample window a[0..14]

@@ -8,8 +8,6 @@
 
 namespace nrsc5 {
 
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 // ---- K6: P1 de-interleave + depuncture (interleaver I, decode.c:296-322) ---------------------------------------
 // Coded bit i = 320 k + j of the frame sits in matrix row (11 k) % 32 of block (j/20 + 7 part) % 16, partition
 // part = PM_V[j % 20], column (11 k + k/288) % 36.  All k that share a matrix row r (k = 3r + 32 m) read the same

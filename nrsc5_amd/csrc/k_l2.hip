@@ -21,8 +21,6 @@
 
 namespace nrsc5 {
 
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 struct L2IndexSmem {
     L2Smem rs;
     uint8_t crc_tab[256];

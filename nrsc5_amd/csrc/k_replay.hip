@@ -16,8 +16,6 @@
 
 namespace nrsc5 {
 
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 __global__ __launch_bounds__(256) void k_rollback(DevBuffers db, const int *ids, int cur_window, int min_age)
 {
     const int s = stream_of(ids, blockIdx.x);

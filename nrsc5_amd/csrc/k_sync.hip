@@ -15,7 +15,7 @@
 #include "l2_header.h"
 #include "fastmath.h"
 #include "flow_ops.h"
-#include "mixfft_body.h"                                       // (defines stream_of; the symbol transform for k_flow at the end of this file)
+#include "mixfft_body.h"                                       // (the symbol transform for k_flow at the end of this file)
 
 namespace nrsc5 {
 

@@ -34,13 +34,11 @@
 
 namespace nrsc5 {
 
-__device__ inline int trim_stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 __global__ __launch_bounds__(64) void k_trim_plan(DevBuffers db, const int *ids, int nstreams, TrimPlan *plan)
 {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= nstreams) return;
-    const int s = trim_stream_of(ids, k);
+    const int s = stream_of(ids, k);
     StreamState &st = db.state[s];
     TrimPlan pl;
     pl.off = 0; pl.n = 0; pl.base = st.base; pl.wr = st.wr;
@@ -80,7 +78,7 @@ constexpr int TRIM_STAGE = 12288;                              // overlapping mo
 // source [off, off + n) and destination [0, n) are disjoint (off >= n): tiles in any order, by every workgroup of the stream's row
 __global__ __launch_bounds__(TRIM_NT) void k_trim_move(DevBuffers db, const int *ids, const TrimPlan *plan)
 {
-    const int s = trim_stream_of(ids, blockIdx.y);
+    const int s = stream_of(ids, blockIdx.y);
     const long long off = plan[blockIdx.y].off, n = plan[blockIdx.y].n;
     if (off <= 0 || n <= 0 || off < n) return;                 // block-uniform (off < n: k_trim_move_overlap's)
     uint32_t *buf = (uint32_t *)(db.q15 + (size_t)s * db.q15_cap);   // one c16 = one dword
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(TRIM_NT) void k_trim_move(DevBuffers db, const int 
 // pass's LDS loads.
 __global__ __launch_bounds__(TRIM_NT) void k_trim_move_overlap(DevBuffers db, const int *ids, const TrimPlan *plan)
 {
-    const int s = trim_stream_of(ids, blockIdx.x);
+    const int s = stream_of(ids, blockIdx.x);
     const long long off = plan[blockIdx.x].off, n = plan[blockIdx.x].n;
     if (off <= 0 || n <= 0 || off >= n) return;                // block-uniform
     uint32_t *buf = (uint32_t *)(db.q15 + (size_t)s * db.q15_cap);

@@ -143,7 +143,7 @@ void launch_p1_forward(const DevTables &tb, const DevBuffers &db, int nstreams, 
 // parts: workgroups per frame of the traceback's first pass (k_p1_tbmap), 1..16
 void launch_p1_traceback(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int lane_id, hipStream_t st, int l2_mode = 0, int parts = 4, int walk = 1);
 
-// ---- AM path (k_am.hip) -------------------------------------------------------------------------
+// ---- AM path (k_am_decimate.hip, k_am.hip, k_am_decode.hip) ---------------------------------------
 // cu8 -> five cascaded half-bands 32:1, any nbytes % 4 == 0 per stream (stage phases carry over)
 void launch_am_decimate_cu8(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids,
                             const uint8_t *iq_base, long long iq_stride, const unsigned *nbytes, unsigned max_nbytes, hipStream_t st);
@@ -151,6 +151,8 @@ void launch_am_decimate_cu8(const DevTables &tb, const DevBuffers &db, int nstre
 // and, after block 7, the bit de-interleaver of the finished L1 frame
 void launch_am_step(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st, int l2_feedback = 0, int pipeline_parity = -1, int slot = 0,
                     int window = 0);
+// in-order mode's part of a block step (called by launch_am_step): this block's P1 frame and after block 7 the P3 frame, then their L2 index
+void launch_am_decode_in_order(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int l2_feedback, hipStream_t st);
 // entry of the AM de-interleave tables: cell | bit << 13 | matrix << 16 | delayed << 18 | punctured << 19
 constexpr unsigned AMT_DELAYED = 1u << 18, AMT_PUNCT = 1u << 19;
 // window pipeline: the 8 P1 frames and the P3 frame of every L1 frame whose de-interleave happened in window `parity`

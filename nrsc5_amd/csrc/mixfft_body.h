@@ -16,8 +16,6 @@ constexpr bool DIAG_NOLOAD = true;
 constexpr bool DIAG_NOLOAD = false;
 #endif
 
-__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
-
 // Complex values as a native 2-vector: the compiler then keeps them in aligned register pairs and every complex add / subtract /
 // scale is ONE packed instruction (v_pk_add_f32 / v_pk_mul_f32, the swaps and sign flips of a complex product riding in op_sel /
 // neg modifiers) -- written on a struct of two floats the same arithmetic came out with 18 % of the kernel's VALU instructions

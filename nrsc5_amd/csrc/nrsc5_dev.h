@@ -66,6 +66,18 @@ enum { SYNC_NONE = 0, SYNC_COARSE = 1, SYNC_FINE = 2 };   // input.h:18
 __host__ __device__ inline int live_to_bin(int l) { return l < LIVE_HALF ? LB0 + l : UB0 + (l - LIVE_HALF); }
 __host__ __device__ inline int bin_to_live(int b) { return b < FFT_N / 2 ? b - LB0 : LIVE_HALF + (b - UB0); }
 
+// stream handled by list position idx of a launch: the caller's stream list, or -- without one -- the position itself
+__device__ inline int stream_of(const int *ids, int idx) { return ids ? ids[idx] : idx; }
+
+// coded (unpunctured) bits of an AM L1 frame, the denominator of its bit error rate (decode.c:545): 8 P1 frames, and the P3 frame
+// unless the reduced-bandwidth flag is set (decode.c:524)
+__host__ __device__ inline unsigned am_frame_coded_bits(int psmi, int rdbi)
+{
+    unsigned total = 8 * (AM_P1_LEN * 12 / 5);
+    if (!rdbi) total += psmi == AM_MA3 ? AM_P3_LEN_MA3 * 12 / 5 : AM_P3_LEN_MA1 * 3 / 2;
+    return total;
+}
+
 struct c16 { int16_t r, i; };
 
 // ---- what a reset leaves in the reference's FIR windows ------------------------------------------------------------
@@ -224,7 +236,7 @@ struct AmJob {
     // yet) and the decode window the job was filed in
     int verdict[8], deliver_abs[8], window, pad2;
 };
-// K=9 decode in segment waves (k_am.hip): what the segment waves of one P3 frame leave for the wave that checks their boundaries,
+// K=9 decode in segment waves (viterbi_k9.h): what the segment waves of one P3 frame leave for the wave that checks their boundaries,
 // and the end states of the L1 frame's eight P1 frames (forward and traceback are separate launches)
 constexpr int K9_GMAX = 8;            // segment waves per frame at most
 constexpr int K9_WARM = 3;            // forward warm-up of a segment wave: chunks of 64 step pairs (384 trellis steps)

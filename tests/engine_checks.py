@@ -450,7 +450,7 @@ def conv_encode_k9(bits: np.ndarray, gens) -> np.ndarray:
 
 
 def check_viterbi_k9_segmented(lib, oracle, lens=(3750, 24000), segments=(2, 3, 8), seed=14):
-    """K=9 decode in segment waves (k_am.hip: forward pass AND traceback speculate across segment boundaries, a checking wave accepts
+    """K=9 decode in segment waves (viterbi_k9.h, stage kernels in k_am_decode.hip: forward pass AND traceback speculate across segment boundaries, a checking wave accepts
     or re-runs each segment): the sequential decoder's bits for any segment count -- on noise, on the all-erasure frame (every ACS a
     tie), on constant input and on noisy code words; and again with warm-up and run-in switched off (test hook), when the
     speculation is wrong at nearly every boundary of an informative frame and the result rests on the repairs (counted)."""
