@@ -291,7 +291,9 @@ extern "C" int nrsc5hip_chan_create(const nrsc5hip_chan_config *cfg, nrsc5hip_ch
     if (T < 8) T = 8;
     int L = (int)ceil(PHASE_RATE / fs);
     L = L < 32 ? 32 : L > 4096 ? 4096 : L;
-    // tile: the largest power of two (16..256) of outputs whose input span fits SPAN_MAX
+    // tile: the largest power of two (16..256) of outputs whose input span fits SPAN_MAX.  Both terms of the span grow with the rate, and
+    // at the 64 MS/s cap a tile of 32 spans 31 * 86 + 926 + 2 = 3593 samples: the loop never gets to its floor of 16, which no test can
+    // therefore reach (tests/chan_model.py: RATE_EDGE_CASES runs 256, 64 and 32).  The floor stays as the loop's end, not as a case.
     int mt = 256;
     for (; mt > 16; mt /= 2)
         if ((long long)((mt - 1) * (unsigned __int128)P / Q) + T + 2 <= SPAN_MAX) break;

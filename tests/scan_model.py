@@ -24,6 +24,38 @@ def segments(n: int, nfft: int) -> int:
     return 0 if n < nfft else (n - nfft) // (nfft // 2) + 1
 
 
+RUN_MAX, ROWS_TARGET = 64, 1024
+
+# Even log2(nfft): the transform is radix-4 passes alone, no radix-2 pre-pass.  (rate, the nfft it defaults to); 4096 is the default
+# of every rate in (4.096 M, 8.192 M] and needs more than 64 KiB of LDS.
+EVEN_NFFT_CASES = [(1500000, 1024), (6000000, 4096)]
+
+# One push of so many segments that a workgroup sums a run of them in registers (run_rows()): name -> (nfft, n, fmt, chunks,
+# run, rows, segments in the last row -- of the largest push).  "rows-over-target": the run clamped to RUN_MAX with more than ROWS_TARGET rows, 72 MB of input.
+MANY_SEGMENT_CASES = {
+    "run3-cs16": (512, 512 + 256 * 2100 + 99, 1, None, 3, 701, 1),
+    "run3-cu8-grow": (512, 512 + 256 * 2100 + 99, 0, [1000], 3, 700, 2),       # the partial-sum rows grow between the two pushes
+    "run2-nfft1024": (1024, 1024 + 512 * 1500 + 5, 1, None, 2, 751, 1),
+    "rows-over-target": (512, 512 + 256 * 70000 + 11, 1, None, RUN_MAX, 1094, 49),
+}
+
+
+def many_segment_pushes(name: str):
+    """-> (nfft, n, fmt, chunk plan); asserts that the case's largest push launches what the table says"""
+    nfft, n, fmt, first, run, rows, last = MANY_SEGMENT_CASES[name]
+    chunks = (first or []) + [n - sum(first or [])]
+    nseg = segments(n, nfft) - segments(n - chunks[-1], nfft)
+    assert run_rows(nseg) == (run, rows, last) and run > 1 and last < run
+    return nfft, n, fmt, chunks
+
+
+def run_rows(nseg: int):
+    """the launch rule of nrsc5hip_scan_push -> (segments per workgroup, workgroups = rows of partial sums, segments in the last row)"""
+    run = min(-(-nseg // ROWS_TARGET), RUN_MAX)
+    rows = -(-nseg // run)
+    return run, rows, nseg - (rows - 1) * run
+
+
 def psd(x: np.ndarray, nfft: int, max_segments: int | None = None) -> np.ndarray:
     """x: complex128 in the library's scale -> PSD[nfft], bin i at (i - nfft/2) * fs / nfft"""
     S = segments(x.size, nfft)

@@ -51,6 +51,45 @@ def test_gpu_device_equals_float64_model(hip_lib, rate, fmt):
     assert err <= REL_BOUND, err
 
 
+@pytest.mark.parametrize("fmt", [eng.IQ_CU8, eng.IQ_CS16, eng.IQ_CF32], ids=["cu8", "cs16", "cf32"])
+@pytest.mark.parametrize("explicit", [True, False], ids=["explicit", "default"])
+@pytest.mark.parametrize("rate,nfft", sm.EVEN_NFFT_CASES, ids=[str(c[1]) for c in sm.EVEN_NFFT_CASES])
+def test_gpu_even_transform_sizes_equal_float64_model(hip_lib, rate, nfft, explicit, fmt):
+    """nfft 1024 and 4096: radix-4 passes alone, and at 4096 more than 64 KiB of dynamic LDS; asked for by size and reached through the
+    rate's default.  Measured on the twin and on the device alike: 1.1e-13 .. 4.7e-13."""
+    import torch
+    n = nfft // 2 * 15 + 37
+    raw = sm.noise_plus_tone(fmt, n, seed=nfft + fmt)
+    sc = eng.Scanner(rate, fmt, nfft=nfft if explicit else 0, lib_path=hip_lib)
+    assert sc.nfft == nfft == sm.default_nfft(rate)
+    got = _push(sc, torch.from_numpy(raw).to(_dev()), [n // 3, n - n // 3])
+    assert sc.segments == sm.segments(n, nfft)
+    sc.close()
+    err = sm.rel_error(got, sm.psd(sm.scaled(raw, fmt), nfft))
+    print(f"scan nfft {nfft} {'explicit' if explicit else 'default'} fmt {fmt}: largest relative error {err:.3e}")
+    assert err <= REL_BOUND, err
+
+
+@pytest.mark.parametrize("name", list(sm.MANY_SEGMENT_CASES))
+def test_gpu_many_segments_per_push(hip_lib, name):
+    """More than ROWS_TARGET segments in one push: every workgroup carries its sums across a run of segments (the last run is short),
+    and "rows-over-target" clamps the run to RUN_MAX with more rows than ROWS_TARGET.  Measured on the device: 4.5e-14 .. 7.3e-14."""
+    import torch
+    nfft, n, fmt, chunks = sm.many_segment_pushes(name)
+    raw = sm.noise_plus_tone(fmt, n, seed=nfft + len(name))
+    x = torch.from_numpy(raw).to(_dev())
+    sc = eng.Scanner(2400000, fmt, nfft=nfft, lib_path=hip_lib)
+    got = _push(sc, x, chunks)
+    assert sc.segments == sm.segments(n, nfft)
+    err = sm.rel_error(got, sm.psd(sm.scaled(raw, fmt), nfft))
+    print(f"scan {name}: largest relative error {err:.3e}")
+    assert err <= REL_BOUND, err
+    if name == "rows-over-target":                                    # the same pushes give the same bytes: the reduce adds 1094 rows in row order
+        sc.reset()
+        assert _push(sc, x, chunks).tobytes() == got.tobytes()
+    sc.close()
+
+
 def test_gpu_chunking_reset_and_repeatability(hip_lib):
     import torch
     rate, fmt, n = 10000000, eng.IQ_CS16, 150000

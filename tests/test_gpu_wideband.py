@@ -74,6 +74,59 @@ def test_gpu_device_equals_float64_model_20msps_64_channels(hip_lib):
     _check_model(20000000, eng.IQ_CS16, 64, 200000, seed=64, hip_lib=hip_lib)
 
 
+@pytest.mark.parametrize("case", cm.edge_case_params(), ids=cm.edge_case_id)
+def test_gpu_device_equals_float64_model_over_the_rate_range(hip_lib, case):
+    """Every kernel configuration the rate selects (tests/chan_model.py: RATE_EDGE_CASES; tiles of 256, 64 and 32 outputs, the block of
+    64 work-items over a tile of 32, P/Q = 1, 4096 phases, a fractional rate, up to 926 taps) with odd channel counts, pushed in chunks
+    that split a tile and include one shorter than the taps.  The input level is set per rate so that the model's output rms lies in
+    800..2500 LSB, where the 2.4 / 10 / 20 MS/s cases sit: the share of values the fast sincos may move is then comparable across
+    the rates.  Measured on the device (profiles/wideband_edge_cases.txt): largest difference 1 LSB, at most 0.075 % of the values
+    differing."""
+    import torch
+    rate, fmt, k = case
+    seed = rate.numerator % 997 + 10 * fmt + k
+    offs = _offsets(float(rate), max(k, 2), seed)[:k]
+    ch = eng.Channelizer(rate, fmt, offs, lib_path=hip_lib)
+    n, chunks = cm.case_size(rate, ch.taps, k)
+    raw = cm.raw_noise(fmt, n, seed, cm.level(rate))
+    got = _push(ch, torch.from_numpy(raw).to(_dev()), chunks)
+    want, y, clips = cm.model(cm.scaled(raw, fmt), rate.numerator, rate.denominator, offs, None, ch.table())
+    print(f"chan {cm.edge_case_id(case)} T {ch.taps} L {ch.phases} n {n} M {want.shape[1]}: ", end="")
+    cm.assert_equals_model(got, ch.clip_counts(), want, clips, y, rms_range=(800, 2500))
+    ch.close()
+
+
+def test_gpu_chunking_is_byte_identical_with_more_taps_than_samples(hip_lib):
+    """64 MS/s: 926 taps, tiles of 32 outputs under a block of 64.  Chunks of 7 and of T - 1 samples never hold one output's whole
+    support, so every output is summed from the history and from several pushes; one channel clips some of its outputs (measured: 53
+    of 344, as the model; 0.11 % of the values differing from it by 1 LSB)."""
+    import torch
+    rate, fmt, k, n = cm.RATE_EDGE_CASES[-1], eng.IQ_CS16, 11, 30000
+    offs = _offsets(float(rate), k, seed=64)
+    gains = [1.0] * (k - 1) + [cm.CLIP_GAIN]
+    raw = cm.raw_noise(fmt, n, 64, cm.level(rate))
+    x = torch.from_numpy(raw).to(_dev())
+    rng = np.random.default_rng(64)
+    ref = None
+    for plan in ("whole", "sevens", "taps-1", "random"):
+        ch = eng.Channelizer(rate, fmt, offs, gains=gains, lib_path=hip_lib)
+        T = ch.taps
+        chunks = {"whole": [n], "sevens": [7] * (n // 7 + 1), "taps-1": [T - 1] * (n // (T - 1) + 1),
+                  "random": list(rng.integers(1, 3001, 200))}[plan]
+        assert sum(chunks) >= n and T > 900
+        out, clips = _push(ch, x, chunks), ch.clip_counts()
+        if ref is None:
+            ref = (out, clips)
+            assert 0 < clips[k - 1] < out.shape[1] and not clips[:k - 1].any(), (clips, out.shape)
+            want, _, want_clips = cm.model(cm.scaled(raw, fmt), rate.numerator, rate.denominator, offs, gains, ch.table())
+            print("chan 64000000-cs16-K11 one channel clipping, one push: ", end="")
+            cm.assert_equals_model(out, clips, want, want_clips)
+        else:
+            assert out.tobytes() == ref[0].tobytes(), plan
+            assert np.array_equal(clips, ref[1]), plan
+        ch.close()
+
+
 def test_gpu_chunking_is_byte_identical(hip_lib):
     import torch
     rate, fmt, n = 10000000, eng.IQ_CS16, 150000

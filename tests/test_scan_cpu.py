@@ -7,7 +7,7 @@ import pytest
 from nrsc5_amd import engine as eng
 from tests import scan_model as sm
 
-# Largest relative error of the twin's spectrum against the float64 model over the nine cases of test_twin_equals_float64_model
+# Largest relative error of the twin's spectrum against the float64 model over the fifteen cases of test_twin_equals_float64_model
 # (measured: 9.4e-13, see its docstring); the bound is 4 x that, as the margin for other seeds, and never above the hard cap.
 MEASURED_REL_ERROR = 9.4e-13
 REL_BOUND = 4 * MEASURED_REL_ERROR
@@ -33,9 +33,9 @@ def _push(sc, raw: np.ndarray, chunks):
 
 
 @pytest.mark.parametrize("fmt", [eng.IQ_CU8, eng.IQ_CS16, eng.IQ_CF32], ids=["cu8", "cs16", "cf32"])
-@pytest.mark.parametrize("nfft", [512, 2048, 8192])
+@pytest.mark.parametrize("nfft", [512, 1024, 2048, 4096, 8192])
 def test_twin_equals_float64_model(emu_lib, fmt, nfft):
-    """Gaussian noise plus a tone 40 dB above the noise's total power, 14 segments.  Measured largest relative error over the nine
+    """Gaussian noise plus a tone 40 dB above the noise's total power, 14 segments.  Measured largest relative error over the fifteen
     cases: 9.4e-13 (a double transform on the twin against numpy float64; a float32 transform measured 1.4e-4 at nfft 8192); asserted: 4 x that, below the hard cap of 1e-4."""
     n = nfft // 2 * 15 + 37
     raw = sm.noise_plus_tone(fmt, n, seed=nfft + fmt)
@@ -50,6 +50,24 @@ def test_twin_equals_float64_model(emu_lib, fmt, nfft):
     print(f"nfft {nfft} fmt {fmt}: largest relative error {err:.3e}")
     assert np.max(want) / np.median(want) > 1e4                 # the tone is there
     assert err <= REL_BOUND, err
+
+
+@pytest.mark.parametrize("name", list(sm.MANY_SEGMENT_CASES))
+def test_twin_many_segments_per_push(emu_lib, name):
+    """More than ROWS_TARGET segments in one push: every workgroup carries its sums across a run of segments (the last run is short),
+    and "rows-over-target" clamps the run to RUN_MAX with more rows than ROWS_TARGET.  Measured on the twin: 5e-14 .. 7e-14."""
+    nfft, n, fmt, chunks = sm.many_segment_pushes(name)
+    raw = sm.noise_plus_tone(fmt, n, seed=nfft + len(name))
+    sc = _scanner(emu_lib, 2400000, fmt, nfft)
+    got = _push(sc, raw, chunks)
+    assert sc.segments == sm.segments(n, nfft)
+    err = sm.rel_error(got, sm.psd(sm.scaled(raw, fmt), nfft))
+    print(f"{name}: largest relative error {err:.3e}")
+    assert err <= REL_BOUND, err
+    if name == "rows-over-target":                                    # the same pushes give the same bytes: the reduce adds 1094 rows in row order
+        sc.reset()
+        assert _push(sc, raw, chunks).tobytes() == got.tobytes()
+    sc.close()
 
 
 def test_chunking_reset_and_repeatability(emu_lib):

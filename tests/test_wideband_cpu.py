@@ -7,7 +7,12 @@ import pytest
 from nrsc5_amd import engine as eng
 from tests import chan_model as cm
 
-RATES_RESPONSE = [(1488375, 1), (2048000, 1), (2400000, 1), (2500000, 1), (3200000, 1), (6000000, 1), (10000000, 1), (20000000, 1)]
+RATES_RESPONSE = [(1488375, 1), (2048000, 1), (2400000, 1), (2500000, 1), (3200000, 1), (6000000, 1), (10000000, 1), (20000000, 1),
+                  (1488375, 2), (1000000, 1), (1200000, 1), (20000000, 3), (30720000, 1), (40000000, 1), (56000000, 1), (64000000, 1)]
+
+
+def _rate_id(r):
+    return str(r[0]) if r[1] == 1 else f"{r[0]}over{r[1]}"
 
 
 def _chan(emu_lib, rate, fmt, offsets, gains=None):
@@ -45,9 +50,19 @@ def _run(ch, raw: np.ndarray, chunks) -> tuple:
     return out[:, :got]
 
 
-@pytest.mark.parametrize("rate", RATES_RESPONSE, ids=[str(r[0]) for r in RATES_RESPONSE])
+def _response_db(tab: np.ndarray, freqs: np.ndarray, fs: float) -> np.ndarray:
+    """|H_p(f)| in dB of every phase row p at every frequency, evaluated in blocks of frequencies: at 64 MS/s the stopband grid has
+    7400 points and the whole exponent matrix (taps x points) would dominate the CPU suite's memory and time"""
+    j = np.arange(tab.shape[1])
+    block = max(1, 400000 // tab.shape[1])
+    out = [np.abs(tab @ np.exp(-2j * np.pi * np.outer(j, freqs[b:b + block]) / fs)) for b in range(0, freqs.size, block)]
+    return 20 * np.log10(np.maximum(np.concatenate(out, axis=1), 1e-30))
+
+
+@pytest.mark.parametrize("rate", RATES_RESPONSE, ids=[_rate_id(r) for r in RATES_RESPONSE])
 def test_prototype_response_every_phase(emu_lib, rate):
-    ch = _chan(emu_lib, rate[0], eng.IQ_CS16, [0.0])
+    from fractions import Fraction
+    ch = _chan(emu_lib, Fraction(*rate), eng.IQ_CS16, [0.0])
     tab = ch.table().astype(np.float64)
     L, T = tab.shape
     assert (L, T) == (ch.phases, ch.taps)
@@ -55,14 +70,19 @@ def test_prototype_response_every_phase(emu_lib, rate):
     step = fs / (16 * T)
     fp = np.arange(0.0, cm.PASS_HZ + step, step)
     fp[-1] = cm.PASS_HZ
-    fstop = np.arange(cm.STOP_HZ, fs / 2 + step, step)
-    fstop[-1] = min(fstop[-1], fs / 2)
-    j = np.arange(T)
-    hp = np.abs(tab @ np.exp(-2j * np.pi * np.outer(j, fp) / fs))
-    hs = np.abs(tab @ np.exp(-2j * np.pi * np.outer(j, fstop) / fs))
-    pdb, sdb = 20 * np.log10(hp), 20 * np.log10(np.maximum(hs, 1e-30))
+    pdb = _response_db(tab, fp, fs)
+    assert pdb.shape == (L, fp.size)
     assert np.max(np.abs(pdb)) <= 0.1, np.max(np.abs(pdb))
-    assert np.max(sdb) <= -70.0, np.max(sdb)
+    # Below 2 * STOP_HZ (about 1.09 MS/s) no stopband frequency lies inside Nyquist: the stopband is what would alias into +-198.4 kHz
+    # of the output, STOP_HZ = 744 187.5 - 198.4 k, and nothing within +-Fs/2 of the input reaches that far.  There the passband is
+    # the whole check.
+    if fs / 2 >= cm.STOP_HZ:
+        fstop = np.arange(cm.STOP_HZ, fs / 2 + step, step)
+        fstop[-1] = min(fstop[-1], fs / 2)
+        sdb = _response_db(tab, fstop, fs)
+        assert sdb.shape == (L, fstop.size) and fstop.size >= 1
+        assert np.max(sdb) <= -70.0, np.max(sdb)
+        print(f"rate {fs:.1f}: passband {np.max(np.abs(pdb)):.4f} dB, stopband {np.max(sdb):.1f} dB, L {L} T {T}")
     ch.close()
 
 
@@ -88,6 +108,78 @@ def test_twin_equals_float64_model(emu_lib, fmt, rate):
     assert np.mean(diff != 0) <= 0.01, np.mean(diff != 0)
     assert np.array_equal(ch.clip_counts(), clips)
     ch.close()
+
+
+def test_rate_edge_table_covers_every_kernel_configuration(emu_lib):
+    """cm.RATE_EDGE_CASES is only worth its name while it reaches every configuration of the kernel: the tiles of 256, 64 and 32
+    outputs (32: a block of 64 work-items, half of them without an output), P/Q = 1, the phase count clamped to 4096, a fractional
+    rate, and taps in the hundreds.  Taps and phases come from the library, so a change of the design constants shows here."""
+    seen = []
+    for rate in cm.RATE_EDGE_CASES:
+        ch = _chan(emu_lib, rate, eng.IQ_CS16, [0.0])
+        T, L = ch.taps, ch.phases
+        ch.close()
+        P, Q = cm.ratio(rate.numerator, rate.denominator)
+        mt, span = cm.tile(P, Q, T)
+        assert span <= cm.SPAN_MAX and mt >= 32                  # the floor of 16 is out of reach below 64 MS/s
+        for k in (1, 11):
+            n, chunks = cm.case_size(rate, T, k)
+            assert sum(chunks) == n and min(chunks) < T
+            M = cm.outputs_total(n, P, Q, T)
+            assert M >= 3.5 * mt and cm.outputs_total(chunks[0], P, Q, T) % mt != 0
+        print(f"rate {float(rate):.1f}: P/Q {P}/{Q} T {T} L {L} mt {mt} span {span} n {n} M {M}")
+        seen.append((rate, P, Q, T, L, mt, span))
+    assert {s[5] for s in seen} == {256, 64, 32}
+    assert any(s[1] == s[2] == 1 for s in seen)
+    assert any(s[4] == 4096 for s in seen) and any(s[4] < 64 for s in seen)
+    assert any(s[0].denominator != 1 and s[0] != cm.OUT_RATE for s in seen)
+    assert any(s[3] > 400 and s[5] == 32 for s in seen)
+    assert max(s[6] for s in seen) > 0.9 * cm.SPAN_MAX          # a tile that nearly fills the LDS
+
+
+@pytest.mark.parametrize("case", cm.edge_case_params(), ids=cm.edge_case_id)
+def test_twin_equals_float64_model_over_the_rate_range(emu_lib, case):
+    """Every kernel configuration the rate selects, with odd channel counts; the input level is chosen per rate so that the model's
+    output rms lies in 800..2500 LSB, where the 2.4 / 10 / 20 MS/s cases sit.  Measured on the twin: largest difference 1 LSB, at most
+    0.074 % of the values differing, clip counts equal at every case."""
+    rate, fmt, k = case
+    fs = float(rate)
+    seed = rate.numerator % 997 + 10 * fmt + k
+    offs = _offsets(fs, max(k, 2), seed)[:k]
+    ch = _chan(emu_lib, rate, fmt, offs)
+    n, chunks = cm.case_size(rate, ch.taps, k)
+    raw = cm.raw_noise(fmt, n, seed, cm.level(rate))
+    got = _run(ch, raw, chunks)
+    want, y, clips = cm.model(cm.scaled(raw, fmt), rate.numerator, rate.denominator, offs, None, ch.table())
+    cm.assert_equals_model(got, ch.clip_counts(), want, clips, y, rms_range=(800, 2500))
+    ch.close()
+
+
+def test_chunking_is_byte_identical_with_more_taps_than_samples(emu_lib):
+    """64 MS/s: 926 taps, tiles of 32 outputs.  Chunks of 7 and of T - 1 samples never hold one output's whole support, so every output
+    is summed from the history and from several pushes; one channel clips some of its outputs."""
+    rate, fmt, k, n = cm.RATE_EDGE_CASES[-1], eng.IQ_CS16, 11, 30000
+    offs = _offsets(float(rate), k, seed=64)
+    gains = [1.0] * (k - 1) + [cm.CLIP_GAIN]
+    raw = cm.raw_noise(fmt, n, 64, cm.level(rate))
+    rng = np.random.default_rng(64)
+    ref = None
+    for plan in ("whole", "sevens", "taps-1", "random"):
+        ch = _chan(emu_lib, rate, fmt, offs, gains)
+        T = ch.taps
+        chunks = {"whole": [n], "sevens": [7] * (n // 7 + 1), "taps-1": [T - 1] * (n // (T - 1) + 1),
+                  "random": list(rng.integers(1, 3001, 200))}[plan]
+        assert sum(chunks) >= n and T > 900
+        out, clips = _run(ch, raw, chunks), ch.clip_counts()
+        if ref is None:
+            ref = (out, clips)
+            assert 0 < clips[k - 1] < out.shape[1] and not clips[:k - 1].any(), (clips, out.shape)
+            want, _, want_clips = cm.model(cm.scaled(raw, fmt), rate.numerator, rate.denominator, offs, gains, ch.table())
+            cm.assert_equals_model(out, clips, want, want_clips)
+        else:
+            assert out.tobytes() == ref[0].tobytes(), plan
+            assert np.array_equal(clips, ref[1]), plan
+        ch.close()
 
 
 def test_chunking_is_byte_identical(emu_lib):
