@@ -428,6 +428,20 @@ int nrsc5hip_stage_viterbi_k9(nrsc5hip_engine *e, const int8_t *soft /* [nframes
                               const unsigned gens[3], uint8_t *bits /* [nframes][len] */);
 /* device check of the DPP / v_permlane / v_writelane / v_dot4 helpers against generic shuffles: *failures == 0 */
 int nrsc5hip_stage_selftest(nrsc5hip_engine *e, int *failures);
+/* The device's math header (csrc/fastmath.h) on caller data, one work-item per element: what the parity contract rests on (ref_sincosf /
+ * ref_atan2f = glibc's sincosf / atan2f bit for bit) and the short forms of the sync chain, evaluated by the gfx950 code itself.  n
+ * elements; a, b, out0, out1 are HOST arrays of float (double for the two series); b and out1 may be NULL where the table says "-":
+ *   fn                                 a          b    out0    out1
+ *   NRSC5HIP_MATH_REF_SINCOSF          y          -    sin     cos
+ *   NRSC5HIP_MATH_REF_ATAN2F           y          x    angle   -
+ *   NRSC5HIP_MATH_FAST_SINCOS          x          -    sin     cos
+ *   NRSC5HIP_MATH_FAST_SINCOS_REDUCED  x          -    sin     cos       (|x| within a few turns)
+ *   NRSC5HIP_MATH_FAST_ATAN2           y          x    angle   -
+ *   NRSC5HIP_MATH_SMALL_COS_SIN        x (double) -    cos     sin       (|x| <= 0.25)
+ *   NRSC5HIP_MATH_SMALL_ATAN           t (double) -    atan    -         (|t| <= 0.26) */
+enum { NRSC5HIP_MATH_REF_SINCOSF = 0, NRSC5HIP_MATH_REF_ATAN2F, NRSC5HIP_MATH_FAST_SINCOS, NRSC5HIP_MATH_FAST_SINCOS_REDUCED,
+       NRSC5HIP_MATH_FAST_ATAN2, NRSC5HIP_MATH_SMALL_COS_SIN, NRSC5HIP_MATH_SMALL_ATAN };
+int nrsc5hip_stage_math(nrsc5hip_engine *e, int fn, const void *a, const void *b, long long n, void *out0, void *out1);
 /* one frame, also returning the len+64 survivor-decision words of the forward pass */
 int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out);
 /* micro-benchmark of the Viterbi kernel on random frames: phases bit0 = forward, bit1 = traceback */

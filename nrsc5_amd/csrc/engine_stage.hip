@@ -207,6 +207,27 @@ extern "C" int nrsc5hip_stage_selftest(nrsc5hip_engine *e, int *failures)
     return 0;
 }
 
+extern "C" int nrsc5hip_stage_math(nrsc5hip_engine *e, int fn, const void *a, const void *b, long long n, void *out0, void *out1)
+{
+    ON_ENGINE_DEVICE(e);
+    if (fn < NRSC5HIP_MATH_REF_SINCOSF || fn > NRSC5HIP_MATH_SMALL_ATAN) FAIL(NRSC5HIP_EINVAL, "unknown function %d", fn);
+    const bool two_in = fn == NRSC5HIP_MATH_REF_ATAN2F || fn == NRSC5HIP_MATH_FAST_ATAN2, two_out = !two_in && fn != NRSC5HIP_MATH_SMALL_ATAN;
+    if (!a || !out0 || (two_in && !b) || (two_out && !out1) || n < 1 || n > (1LL << 28)) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    const size_t bytes = (size_t)n * (fn >= NRSC5HIP_MATH_SMALL_COS_SIN ? sizeof(double) : sizeof(float));
+    DevTmp da, db, d0, d1;
+    HIPCHK(hipMalloc(&da.p, bytes));
+    HIPCHK(hipMalloc(&d0.p, bytes));
+    HIPCHK(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
+    if (two_in) { HIPCHK(hipMalloc(&db.p, bytes)); HIPCHK(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice)); }
+    if (two_out) HIPCHK(hipMalloc(&d1.p, bytes));
+    if (launch_stage_math(fn, da.p, db.p, n, d0.p, d1.p, e->main)) FAIL(NRSC5HIP_EINVAL, "unknown function %d", fn);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(out0, d0.p, bytes, hipMemcpyDeviceToHost));
+    if (two_out) HIPCHK(hipMemcpy(out1, d1.p, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out)
 {
     ON_ENGINE_DEVICE(e);

@@ -4,7 +4,9 @@
 // from the transcendental unit (v_sin_f32 / v_cos_f32, input in revolutions) and the arc tangent from a 4-term polynomial
 // after the tan(pi/8) reduction.  Measured on the MI355X against double precision (tools/probe/math_probe.hip):
 // |error| <= 5e-7 in sin / cos for |x| <= 2000 rad, <= 3e-7 rad in atan2 -- the reference's own float32 chain (glibc)
-// is not reproduced to the last ulp by ANY other libm either; SURVEY 8c pins these quantities at 1e-4.
+// is not reproduced to the last ulp by ANY other libm either; SURVEY 8c pins these quantities at 1e-4.  Both sets of figures are asserted
+// on the device, on 1e6 arguments per function, by tests/test_gpu_math_stage.py (through nrsc5hip_stage_math, which evaluates this header
+// on caller data), together with the exact properties: |s|, |c| <= 1, fast_atan2 carries the sign of y, stays within +-pi and is 0 at (0, 0).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -67,7 +69,10 @@ __device__ __forceinline__ float fast_atan2(float y, float x)
 // atan2f ONCE per block and their last bit matters: one ulp of the coarse angle is a phase ramp of 1.6e-5 rad across the block that runs the CFO search -- the size of the
 // oscillator's rounding drift (DESIGN.md (c) limit 2) -- and OCML's atan2f differs from glibc's in the last bit for 16 % of arguments.
 // fdlibm's float arc tangent (s_atanf.c / e_atan2f.c, as glibc 2.35 ships them for x86-64: no FMA variant exists for these two), restated: float operations only,
-// each rounded once -- the device reproduces glibc's atan2f bit for bit (tests/test_ref_atan2f.py: 2e7 arguments of four distributions against this container's libm, 0 mismatches; 1e8 when it was written).
+// each rounded once -- glibc's atan2f bit for bit.  Two tests hold that: tests/test_ref_atan2f.py compiles this header with g++ (2e7 arguments of four distributions against the
+// host's libm, 0 mismatches; 1e8 when it was written), and tests/test_gpu_math_stage.py runs the gfx950 code itself (nrsc5hip_stage_math) against the host's libm on 4.2e6 arguments:
+// the same distributions, both sides of every ratio threshold below in every quadrant, the exponent cuts of ref_atan2f, denormal operands and denormal / underflowing quotients --
+// the correctly rounded float divisions (denormals kept) and the absence of contraction are properties of the DEVICE build (hipcc's division expansion, -ffp-contract=off).
 __device__ inline float ref_atanf(float x)
 {
     const float atanhi[4] = { 4.6364760399e-01f, 7.8539812565e-01f, 9.8279368877e-01f, 1.5707962513e+00f };
@@ -135,7 +140,9 @@ __device__ inline float ref_atan2f(float y, float x)
 // last bit (1.3 % of arguments differ).  Restated here operation for operation, INCLUDING which multiply-adds are fused: on every x86-64 host with FMA + AVX2 glibc's
 // ifunc picks `__sincosf_fma` (the same source built with -mfma -mavx2, contraction on), and in that build (Ubuntu glibc 2.35-0ubuntu3.x, the image of this container and
 // of the GPU box; read from its disassembly) EVERY a + b * c of the polynomial and the `x - n * hpi` of the fast reduction is one fused operation, the products x * s,
-// x * x, x2 * x, x2 * x2, x3 * x2, x4 * x2 and x * hpi_inv are plain.  tests/test_ref_sincosf.py compares with this container's libm on 1e8 arguments.
+// x * x, x2 * x, x2 * x2, x3 * x2, x4 * x2 and x * hpi_inv are plain.  tests/test_ref_sincosf.py compares the g++ build of this header with the host's libm on 1e8 arguments;
+// tests/test_gpu_math_stage.py compares the gfx950 code (nrsc5hip_stage_math) with it on 1e6: the same distributions, every branch threshold, the quadrant flips of the fast
+// reduction and every exponent of the large one -- including the table path below (idx > 3), which no Costas loop reaches and no end-to-end test therefore covers.
 // (A host WITHOUT FMA runs the unfused build and differs from this in the last bit for a fraction of a percent of arguments -- the UNMODIFIED reference is not
 // bit-reproducible from such a host to an FMA host either.)
 __device__ inline void ref_sincosf(float y, float &sinp, float &cosp)
@@ -202,7 +209,8 @@ __device__ inline void ref_sincosf(float y, float &sinp, float &cosp)
 // block (prepare_block: the single lane that runs it sits at the end of the block-step chain; the device libm's three calls were
 // ~5 k of the sync kernel's ~11 k "finish" cycles).  |x| <= 0.25: the series are cut where the next term is below 1e-20 of the
 // result, the evaluation error is a few ulps of a double -- the callers round the results to float or use them as a phase
-// increment whose own uncertainty is twelve orders of magnitude larger.
+// increment whose own uncertainty is twelve orders of magnitude larger.  (Measured: 0.55 / 0.53 / 1.06 ulp for cos / sin / atan; tests/test_math_stage_cpu.py and
+// tests/test_gpu_math_stage.py assert 2 ulps against extended precision, and that the device returns the g++ build's doubles bit for bit.)
 __device__ __forceinline__ void small_cos_sin(double x, double &c, double &s)
 {
     const double w = x * x;

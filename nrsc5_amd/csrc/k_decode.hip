@@ -5,6 +5,7 @@
 #include "viterbi_wave.h"
 #include "viterbi_v3.h"
 #include "l2_header.h"
+#include "fastmath.h"
 
 namespace nrsc5 {
 
@@ -413,5 +414,55 @@ __global__ __launch_bounds__(64) void k_selftest(int *fail)
 }
 
 void launch_selftest(int *fail, hipStream_t st) { hipLaunchKernelGGL(k_selftest, dim3(4), dim3(64), 0, st, fail); }
+
+// ---- the functions of fastmath.h on caller data (nrsc5hip_stage_math) ----------------------------------
+// One work-item per element, arguments and results in memory, no order imposed on the arguments: the lanes of a wave take whatever
+// branches their arguments select.  The calls are the header's functions themselves, inlined into this file under the flags every
+// production kernel file is built with (the parity contract of ref_sincosf / ref_atan2f rests on -ffp-contract=off and on hipcc's
+// correctly rounded float division, denormals kept).
+template <int FN> __global__ __launch_bounds__(256) void k_stage_math(const void *a, const void *b, long long n, void *out0, void *out1)
+{
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        if constexpr (FN == NRSC5HIP_MATH_REF_SINCOSF) {
+            float s, c; ref_sincosf(((const float *)a)[i], s, c);
+            ((float *)out0)[i] = s; ((float *)out1)[i] = c;
+        } else if constexpr (FN == NRSC5HIP_MATH_REF_ATAN2F) {
+            ((float *)out0)[i] = ref_atan2f(((const float *)a)[i], ((const float *)b)[i]);
+        } else if constexpr (FN == NRSC5HIP_MATH_FAST_SINCOS) {
+            float s, c; fast_sincos(((const float *)a)[i], s, c);
+            ((float *)out0)[i] = s; ((float *)out1)[i] = c;
+        } else if constexpr (FN == NRSC5HIP_MATH_FAST_SINCOS_REDUCED) {
+            float s, c; fast_sincos_reduced(((const float *)a)[i], s, c);
+            ((float *)out0)[i] = s; ((float *)out1)[i] = c;
+        } else if constexpr (FN == NRSC5HIP_MATH_FAST_ATAN2) {
+            ((float *)out0)[i] = fast_atan2(((const float *)a)[i], ((const float *)b)[i]);
+        } else if constexpr (FN == NRSC5HIP_MATH_SMALL_COS_SIN) {
+            double c, s; small_cos_sin(((const double *)a)[i], c, s);
+            ((double *)out0)[i] = c; ((double *)out1)[i] = s;
+        } else {
+            ((double *)out0)[i] = small_atan(((const double *)a)[i]);
+        }
+    }
+}
+
+int launch_stage_math(int fn, const void *a, const void *b, long long n, void *out0, void *out1, hipStream_t st)
+{
+    if (n < 1) return -1;
+    const long long blocks = (n + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096)), block(256);    // grid-stride beyond 2^20 elements
+    switch (fn) {
+#define STAGE_MATH_CASE(F) case F: hipLaunchKernelGGL(k_stage_math<F>, grid, block, 0, st, a, b, n, out0, out1); return 0
+    STAGE_MATH_CASE(NRSC5HIP_MATH_REF_SINCOSF);
+    STAGE_MATH_CASE(NRSC5HIP_MATH_REF_ATAN2F);
+    STAGE_MATH_CASE(NRSC5HIP_MATH_FAST_SINCOS);
+    STAGE_MATH_CASE(NRSC5HIP_MATH_FAST_SINCOS_REDUCED);
+    STAGE_MATH_CASE(NRSC5HIP_MATH_FAST_ATAN2);
+    STAGE_MATH_CASE(NRSC5HIP_MATH_SMALL_COS_SIN);
+    STAGE_MATH_CASE(NRSC5HIP_MATH_SMALL_ATAN);
+#undef STAGE_MATH_CASE
+    default: return -1;
+    }
+}
 
 }  // namespace nrsc5

@@ -182,6 +182,8 @@ void vit_scratch_free(VitScratch &sc);
 // -> 0, or -1: frame too long for the block-parallel traceback (viterbi3_traceback_block: at most 64 segments of TB_SEG chunks) / out of device memory
 int launch_viterbi_frames(VitScratch &sc, const int8_t *coded, int len, int nframes, unsigned long long *dec, uint32_t *out, hipStream_t st, int phases = 3, int segments = 1, int *stats = nullptr, int warm = 2);
 void launch_selftest(int *fail_count, hipStream_t st);
+// one function of fastmath.h (fn: NRSC5HIP_MATH_*) on n elements of device memory; -> 0, or -1: unknown fn / n < 1
+int launch_stage_math(int fn, const void *a, const void *b, long long n, void *out0, void *out1, hipStream_t st);
 void launch_fft2048(const DevTables &tb, const float2 *in, float2 *out, int nffts, hipStream_t st, int form = 1);   // form 32: the 256-lane FFT
 
 }  // namespace nrsc5

@@ -1,7 +1,9 @@
 """CPU-only: `ref_atan2f` (nrsc5_amd/csrc/fastmath.h) -- the float arc tangent the device uses wherever the reference calls cargf once per block (the coarse carrier
 angle of an acquisition block, acquire.c:153; the AM carrier / equaliser phases) -- returns glibc's atan2f BIT FOR BIT: fdlibm's float algorithm restated, float
 operations only.  Compiled here with g++ from the very header the device build includes (no contraction, as the device build) and compared with this container's libm
-on 2e7 arguments of four distributions (unit square, tall / flat ratios, raw bit patterns incl. NaN / inf / denormals, the right half-plane) plus the special cases."""
+on 2e7 arguments of four distributions (unit square, tall / flat ratios, raw bit patterns incl. NaN / inf / denormals, the right half-plane) plus the special cases.
+This test vouches for the ALGORITHM as x86-64 evaluates it; what the gfx950 code returns (hipcc's float division with denormal operands and quotients, no contraction) is
+compared with the host's libm by tests/test_gpu_math_stage.py through nrsc5hip_stage_math."""
 import os
 import subprocess
 import tempfile

@@ -3,7 +3,9 @@ phases, sync.c:271-272, the NCO set-up, acquire.c:153-168) -- returns glibc's si
 (`__sincosf_fma`): the published algorithm (double-precision reduction + polynomial pair) restated with the same fused / unfused operations.  Compiled here with g++ from
 the very header the device build includes (no contraction beyond the explicit fma calls, as the device build) and compared with this container's libm on 1e8 arguments of
 five distributions: the Costas loops' steady range (+-2 pi), the CFO search's range (+-2000 rad), |y| < pi/4, raw bit patterns (incl. NaN / inf / denormals / huge), and the
-neighbourhood of multiples of pi/2.  Skipped (not failed) on a host whose CPU lacks FMA: its libm runs the unfused build, which is a different function in the last bit."""
+neighbourhood of multiples of pi/2.  Skipped (not failed) on a host whose CPU lacks FMA: its libm runs the unfused build, which is a different function in the last bit.
+This test vouches for the ALGORITHM as x86-64 evaluates it; what the gfx950 code returns (64-bit shifts and products of the large reduction, its table path, the conversions,
+no contraction) is compared with the host's libm by tests/test_gpu_math_stage.py through nrsc5hip_stage_math."""
 import os
 import subprocess
 import tempfile

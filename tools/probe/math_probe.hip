@@ -1,4 +1,5 @@
 // accuracy of nrsc5_amd/csrc/fastmath.h on the device against double precision
+// (a hand-run probe; the figures it gave are asserted by tests/test_gpu_math_stage.py through nrsc5hip_stage_math)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <math.h>
