@@ -442,6 +442,22 @@ int nrsc5hip_stage_selftest(nrsc5hip_engine *e, int *failures);
 enum { NRSC5HIP_MATH_REF_SINCOSF = 0, NRSC5HIP_MATH_REF_ATAN2F, NRSC5HIP_MATH_FAST_SINCOS, NRSC5HIP_MATH_FAST_SINCOS_REDUCED,
        NRSC5HIP_MATH_FAST_ATAN2, NRSC5HIP_MATH_SMALL_COS_SIN, NRSC5HIP_MATH_SMALL_ATAN };
 int nrsc5hip_stage_math(nrsc5hip_engine *e, int fn, const void *a, const void *b, long long n, void *out0, void *out1);
+/* The float32 half-band of the zero-copy batch (csrc/halfband_raw.h) on caller data, evaluated by the production functions themselves in
+ * one of the three forms the device runs it in:
+ *   NRSC5HIP_HB_ACQ     hb_sample_q15                            one work-item per sample, 256 per workgroup   (k_acq_decimate)
+ *   NRSC5HIP_HB_SYM128  raw_symbol_load + raw_symbol_halfband    128 work-items x 17 outputs, one per symbol   (k_mixfft<..>)
+ *   NRSC5HIP_HB_SYM256  raw_symbol_load8 + raw_symbol_halfband8  256 work-items x 9 outputs, one per symbol    (k_mixfft8)
+ * iq: nbytes HOST bytes of a cu8 capture (stream start at byte 0; zero history in front of it), placed `lead` (0, 4, 8 or 12) bytes into
+ * a 16-byte-aligned device buffer.  a0: the first decimated sample; n: the number of SYMBOLS of 2160 samples (symbol forms) or of
+ * samples (NRSC5HIP_HB_ACQ).  out[.][2]: the Q15 integers of the reference's decimator (firdecim_q15.c), samples a0 .. -- the symbol
+ * forms' tile holds the imaginary part negated, the kernel turns it back.  probe (NULL: none; symbol forms only): per symbol and
+ * work-item four words -- the bits of 1.0f + 1.5 * 2^-24 and of 2^-126 * 0.5f, operands read from memory, evaluated before the half-band
+ * and again behind it: 0x3f800001 and 0x00200000 in round-to-nearest with denormals kept (0x3f800000 when rounding down).
+ * NRSC5HIP_EINVAL, nothing launched: unknown form; lead not in {0, 4, 8, 12}; n < 1; a0 < 0; nbytes % 4 != 0; a request whose last output
+ * needs a raw sample beyond nbytes (4 (a0 + outputs) > nbytes).  Nothing outside the uploaded bytes is read. */
+enum { NRSC5HIP_HB_ACQ = 0, NRSC5HIP_HB_SYM128, NRSC5HIP_HB_SYM256 };
+int nrsc5hip_stage_halfband_raw(nrsc5hip_engine *e, int form, const uint8_t *iq, size_t nbytes, int lead, long long a0, long long n,
+                                int16_t *out, uint32_t *probe);
 /* one frame, also returning the len+64 survivor-decision words of the forward pass */
 int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out);
 /* micro-benchmark of the Viterbi kernel on random frames: phases bit0 = forward, bit1 = traceback */

@@ -228,6 +228,39 @@ extern "C" int nrsc5hip_stage_math(nrsc5hip_engine *e, int fn, const void *a, co
     return 0;
 }
 
+extern "C" int nrsc5hip_stage_halfband_raw(nrsc5hip_engine *e, int form, const uint8_t *iq, size_t nbytes, int lead, long long a0, long long n, int16_t *out, uint32_t *probe)
+{
+    ON_ENGINE_DEVICE(e);
+    if (form != NRSC5HIP_HB_ACQ && form != NRSC5HIP_HB_SYM128 && form != NRSC5HIP_HB_SYM256) FAIL(NRSC5HIP_EINVAL, "unknown form %d", form);
+    if (!iq || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (lead != 0 && lead != 4 && lead != 8 && lead != 12) FAIL(NRSC5HIP_EINVAL, "lead %d: 0, 4, 8 or 12 bytes", lead);
+    if (n < 1 || a0 < 0) FAIL(NRSC5HIP_EINVAL, "bad range");
+    if (nbytes % 4 || nbytes > ((size_t)1 << 30)) FAIL(NRSC5HIP_EINVAL, "bad length");
+    // decimated sample a reads the dwords a - 7 .. a of the capture (in front of the stream: history, never memory); a symbol workgroup reads nothing
+    // beyond its own last sample's (raw_symbol_load / _load8), so the last output's dword bounds every read
+    const long long dwords = (long long)(nbytes / 4), per = form == NRSC5HIP_HB_ACQ ? 1 : SYM_N;
+    if (a0 > dwords || n > (dwords - a0) / per) FAIL(NRSC5HIP_EINVAL, "samples %lld + %lld x %lld reach beyond the %lld raw dwords", a0, n, per, dwords);
+    const size_t nout = (size_t)(n * per), lanes = form == NRSC5HIP_HB_SYM256 ? 256 : 128;
+    const bool probing = probe && form != NRSC5HIP_HB_ACQ;
+    static const float probe_operands[4] = { 1.0f, 0x1.8p-24f, 0x1p-126f, 0.5f };   // 1 + 1.5 * 2^-24; 2^-126 * 0.5
+    DevTmp draw, dout, dpc, dprobe;
+    HIPCHK(hipMalloc(&draw.p, nbytes + 16));
+    HIPCHK(hipMalloc(&dout.p, nout * sizeof(c16)));
+    HIPCHK(hipMemcpy((uint8_t *)draw.p + lead, iq, nbytes, hipMemcpyHostToDevice));
+    if (probing) {
+        HIPCHK(hipMalloc(&dpc.p, sizeof(probe_operands)));
+        HIPCHK(hipMalloc(&dprobe.p, (size_t)n * lanes * 4 * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(dpc.p, probe_operands, sizeof(probe_operands), hipMemcpyHostToDevice));
+    }
+    if (form == NRSC5HIP_HB_ACQ) launch_stage_halfband_acq(e->tb, (const uint8_t *)draw.p + lead, a0, n, (c16 *)dout.p, e->main);
+    else launch_stage_halfband_sym(e->tb, (int)lanes, (const uint8_t *)draw.p + lead, a0, (int)n, (c16 *)dout.p, (const float *)dpc.p, (uint32_t *)dprobe.p, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(out, dout.p, nout * sizeof(c16), hipMemcpyDeviceToHost));
+    if (probing) HIPCHK(hipMemcpy(probe, dprobe.p, (size_t)n * lanes * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out)
 {
     ON_ENGINE_DEVICE(e);

@@ -7,8 +7,12 @@
 // With x' = x - 127 (|x'| <= 128) and s = x'_{2i} + x'_{14-2i}:  ((64 s) t_i) >> 15 = floor(s t_i / 512); s has 9 bits and
 // t_i 15, so s * (t_i / 512) is exact in float32 and so is its floor.  |y| <= 1.556 * 8192 + 8192 < 32768: the int16
 // accumulator never wraps for 8-bit input, and sums of five such integers are exact in float32 too.
-// (pinned: exhaustive check of the division step and a 200 000-window comparison with the integer code in
-//  tests/test_halfband_float.py; the integer kernel k_decimate_fm_cu8 stays the streaming seam's K1.)
+// (pinned on the device: tests/test_gpu_halfband_stage.py runs the three forms below -- hb_sample_q15, raw_symbol_load + raw_symbol_halfband
+//  (mixfft_body.h), raw_symbol_load8 + raw_symbol_halfband8 (k_mixfft.hip) -- through nrsc5hip_stage_halfband_raw and compares every output
+//  with the integer code on full-scale, near-zero and ramp input, at the stream start and at every alignment of the capture, and probes the
+//  rounding mode and the denormal bits on either side of the switch; tests/test_halfband_stage_cpu.py does the same on the emulated build.
+//  The arithmetic alone -- an exhaustive check of the division step and a numpy model of both chains -- is tests/test_halfband_float.py.
+//  The integer kernel k_decimate_fm_cu8 stays the streaming seam's K1.)
 #pragma once
 #include "nrsc5_dev.h"
 

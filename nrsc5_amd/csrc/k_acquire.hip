@@ -189,4 +189,19 @@ void launch_prepare(const DevBuffers &db, int nstreams, const int *stream_ids, i
     hipLaunchKernelGGL(k_prepare, dim3((nstreams + 63) / 64), dim3(64), 0, st, db, stream_ids, nstreams, acq_on);
 }
 
+// ---- stage-level entry: k_acq_decimate's half-band on caller data (nrsc5hip_stage_halfband_raw) -------------------------------------
+// the same function with the same taps, one work-item per sample in workgroups of 256 as there; samples a0 .. a0 + n - 1 of the capture
+__global__ __launch_bounds__(256) void k_stage_halfband_acq(DevTables tb, const uint8_t *raw, long long a0, long long n, c16 *out)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const HbTaps taps = hb_taps(tb.hb_q15);
+    out[t] = hb_sample_q15(raw, a0 + t, taps);
+}
+
+void launch_stage_halfband_acq(const DevTables &tb, const uint8_t *raw, long long a0, long long n, c16 *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_stage_halfband_acq, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tb, raw, a0, n, out);
+}
+
 }  // namespace nrsc5

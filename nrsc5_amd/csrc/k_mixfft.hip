@@ -421,4 +421,63 @@ void launch_fft2048(const DevTables &tb, const float2 *in, float2 *out, int nfft
     else hipLaunchKernelGGL(k_fft2048, dim3(nffts), dim3(128), 0, st, tb, in, out);
 }
 
+// ---- stage-level entry: the symbol kernels' fused half-band on caller data (nrsc5hip_stage_halfband_raw) ----------------------------
+// One workgroup of the production size per symbol, the production load and half-band functions themselves with the production taps; the
+// tile's entries 0..2159 then leave as the Q15 integers they are (imaginary part turned back).  Around the half-band every work-item
+// evaluates two probes whose operands come from memory (volatile: neither folded nor shared between the two evaluations): an addition
+// whose result tells round-to-nearest from round-down, and a product that is a denormal -- the mode switch must leave both as it found them.
+__device__ __forceinline__ void hb_mode_probe(const volatile float *pc, uint32_t *dst)
+{
+    const float one = pc[0], tiny = pc[1], small = pc[2], half = pc[3];
+    const float sum = one + tiny, den = small * half;
+    dst[0] = __builtin_bit_cast(uint32_t, sum); dst[1] = __builtin_bit_cast(uint32_t, den);
+}
+
+template <int NT> __device__ __forceinline__ void stage_halfband_leave(const cf *tile, c16 *out, const uint32_t *pr, uint32_t *probe)
+{
+    const int tid = threadIdx.x;
+    if (probe) {
+        uint32_t *dst = probe + ((size_t)blockIdx.x * NT + tid) * 4;
+        for (int k = 0; k < 4; k++) dst[k] = pr[k];
+    }
+    __syncthreads();
+    for (int j = tid; j < SYM_N; j += NT) {
+        const cf v = tile[j];
+        c16 r; r.r = (int16_t)(int)v.x; r.i = (int16_t)-(int)v.y;
+        out[(size_t)blockIdx.x * SYM_N + j] = r;
+    }
+}
+
+__global__ __launch_bounds__(128) void k_stage_halfband128(DevTables tb, const uint8_t *raw, long long a0, c16 *out, const float *pc, uint32_t *probe)
+{
+    __shared__ cf tile[8 * PITCH_A];
+    const int tid = threadIdx.x;
+    uint32_t W[24], pr[4] = {0u, 0u, 0u, 0u};
+    raw_symbol_load(raw, a0 + (long long)blockIdx.x * SYM_N, W, tid);
+    const HbTaps taps = hb_taps(tb.hb_q15);
+    if (probe) hb_mode_probe(pc, pr);
+    raw_symbol_halfband(W, tile, taps, tid);
+    if (probe) hb_mode_probe(pc, pr + 2);
+    stage_halfband_leave<128>(tile, out, pr, probe);
+}
+
+__global__ __launch_bounds__(256) void k_stage_halfband256(DevTables tb, const uint8_t *raw, long long a0, c16 *out, const float *pc, uint32_t *probe)
+{
+    __shared__ cf tile[8 * P8_ROW];
+    const int tid = threadIdx.x;
+    uint32_t W[16], pr[4] = {0u, 0u, 0u, 0u};
+    raw_symbol_load8(raw, a0 + (long long)blockIdx.x * SYM_N, W, tid);
+    const HbTaps taps = hb_taps(tb.hb_q15);
+    if (probe) hb_mode_probe(pc, pr);
+    raw_symbol_halfband8(W, tile, taps, tid);
+    if (probe) hb_mode_probe(pc, pr + 2);
+    stage_halfband_leave<256>(tile, out, pr, probe);
+}
+
+void launch_stage_halfband_sym(const DevTables &tb, int lanes, const uint8_t *raw, long long a0, int nsyms, c16 *out, const float *pc, uint32_t *probe, hipStream_t st)
+{
+    if (lanes == 256) hipLaunchKernelGGL(k_stage_halfband256, dim3(nsyms), dim3(256), 0, st, tb, raw, a0, out, pc, probe);
+    else hipLaunchKernelGGL(k_stage_halfband128, dim3(nsyms), dim3(128), 0, st, tb, raw, a0, out, pc, probe);
+}
+
 }  // namespace nrsc5

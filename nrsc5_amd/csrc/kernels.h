@@ -185,5 +185,10 @@ void launch_selftest(int *fail_count, hipStream_t st);
 // one function of fastmath.h (fn: NRSC5HIP_MATH_*) on n elements of device memory; -> 0, or -1: unknown fn / n < 1
 int launch_stage_math(int fn, const void *a, const void *b, long long n, void *out0, void *out1, hipStream_t st);
 void launch_fft2048(const DevTables &tb, const float2 *in, float2 *out, int nffts, hipStream_t st, int form = 1);   // form 32: the 256-lane FFT
+// the fused half-band's forms on a raw cu8 capture in device memory (nrsc5hip_stage_halfband_raw; the caller has checked that every sample read lies
+// inside it).  Symbol forms (k_mixfft.hip): lanes = 128 or 256, nsyms workgroups, out[nsyms][2160]; pc = four floats {1, 1.5 * 2^-24, 2^-126, 0.5}
+// and probe[nsyms][lanes][4] for the rounding-mode probes, both null for none.  Acquisition form (k_acquire.hip): n samples from a0.
+void launch_stage_halfband_sym(const DevTables &tb, int lanes, const uint8_t *raw, long long a0, int nsyms, c16 *out, const float *pc, uint32_t *probe, hipStream_t st);
+void launch_stage_halfband_acq(const DevTables &tb, const uint8_t *raw, long long a0, long long n, c16 *out, hipStream_t st);
 
 }  // namespace nrsc5

@@ -99,6 +99,8 @@ TRIM_RETAIN_MAX_AM = (8 * 8 + 1) * 8910     # NRSC5HIP_TRIM_RETAIN_MAX_AM: ... p
 L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
 TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
 MATH_REF_SINCOSF, MATH_REF_ATAN2F, MATH_FAST_SINCOS, MATH_FAST_SINCOS_REDUCED, MATH_FAST_ATAN2, MATH_SMALL_COS_SIN, MATH_SMALL_ATAN = range(7)   # NRSC5HIP_MATH_*
+HB_ACQ, HB_SYM128, HB_SYM256 = range(3)     # NRSC5HIP_HB_*: the forms of the fused half-band (csrc/halfband_raw.h)
+HB_SYM_N = 2160                             # decimated samples of one symbol
 L2_STATUS = ("end", "no_audio", "fixed_data", "header_rs", "bad_locators", "too_many_pdus", "hef_overrun", "bad_stream", "bad_length", "audio_end")
 
 
@@ -173,6 +175,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_debug_tb_stats.argtypes = [vp, vp]
     lib.nrsc5hip_stage_first_header.argtypes = [vp, vp, ci, ci, ci, vp]
     lib.nrsc5hip_stage_math.argtypes = [vp, ci, vp, vp, ctypes.c_longlong, vp, vp]
+    lib.nrsc5hip_stage_halfband_raw.argtypes = [vp, ci, vp, ctypes.c_size_t, ci, ctypes.c_longlong, ctypes.c_longlong, vp, vp]
     lib.nrsc5hip_debug_poison_results.argtypes = [vp]
     lib.nrsc5hip_debug_seam_totals.argtypes = [vp, ci]
     lib.nrsc5hip_debug_seam_totals.restype = None
@@ -236,7 +239,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
-    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
+    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
     "nrsc5hip_stream_set_mode", "nrsc5hip_am_frame_bits", "nrsc5hip_stage_viterbi_k9", "nrsc5hip_px_frame_bits",
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
@@ -647,6 +650,18 @@ class Engine:
         self._check(self.lib.nrsc5hip_stage_math(self._h, fn, a.ctypes.data, b.ctypes.data if two_in else None, a.size,
                                                  out0.ctypes.data, out1.ctypes.data if two_out else None))
         return (out0, out1) if two_out else out0
+
+    def stage_halfband_raw(self, form: int, iq: np.ndarray, a0: int, n: int, lead: int = 0, probe: bool = False):
+        """nrsc5hip_stage_halfband_raw: the fused float32 half-band in one of its device forms (HB_*) on the cu8 capture iq, placed `lead`
+        bytes into an aligned device buffer.  n symbols of 2160 samples from decimated sample a0 (n samples for HB_ACQ) -> int16 [.., 2], the
+        reference's Q15 integers; with probe (symbol forms) also uint32 [n, work-items, 4]: the rounding and denormal probes before / behind."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1)
+        per, lanes = (1, 0) if form == HB_ACQ else (HB_SYM_N, 256 if form == HB_SYM256 else 128)
+        out = np.zeros((max(n, 0) * per, 2), dtype=np.int16)
+        pr = np.zeros((max(n, 0), lanes, 4), dtype=np.uint32) if probe and lanes else None
+        self._check(self.lib.nrsc5hip_stage_halfband_raw(self._h, form, iq.ctypes.data, iq.size, lead, a0, n, out.ctypes.data,
+                                                         pr.ctypes.data if pr is not None else None))
+        return (out, pr) if probe else out
 
     def stage_selftest(self) -> int:
         n = ctypes.c_int(-1)

@@ -4,6 +4,7 @@ container; it is not a product path and proves nothing about gfx950 code generat
 `-m gpu` twins in test_gpu_parity.py do that through the real library."""
 import os
 
+import numpy as np
 import pytest
 
 from tests import engine_checks as ec
@@ -279,6 +280,22 @@ def test_emu_symbol_kernel_256_lanes(emu_lib, oracle, captures):
     caps = [synth.fm_mp1_capture(0, seed=71, cfo_hz=33.0, offset=400, snr_db=22, n_blocks=20), synth.fm_mp1_capture(0, seed=72, cfo_hz=-120.0, offset=1500, snr_db=20, n_blocks=20)]
     ec.check_zero_copy_batch(emu_lib, caps, p1_async=True, l2_feedback=False, mixfft_syms=32, singles_tuned=True)
     ec.check_golden_end_to_end(emu_lib, "fm_cu8_cfo137", captures, tune=((ec.eng.TUNE_MIXFFT_SYMS, 32),))
+
+
+@pytest.mark.parametrize("syms", [0, 32])
+def test_emu_zero_copy_batch_full_scale_capture(emu_lib, syms):
+    """tests/test_gpu_parity.py's full-scale case in short form: one capture at rms_lsb 240 (28 % of its bytes are 0 or 255), zero-copy
+    batch == streaming seam at rtol 0 in both forms of the symbol kernel"""
+    cap = synth.fm_mp1_capture(0, seed=92, cfo_hz=-310.0, offset=2750, snr_db=20, n_blocks=18, rms_lsb=240.0)
+    assert 0.25 < float(((cap.iq == 0) | (cap.iq == 255)).mean()) < 0.32
+    ec.check_zero_copy_batch(emu_lib, [cap], p1_async=True, l2_feedback=False, mixfft_syms=syms, rtol=0.0, singles_tuned=bool(syms))
+
+
+def test_emu_zero_copy_batch_full_range_noise(emu_lib):
+    """uniform random bytes 0..255, four blocks: every block through k_acq_decimate's half-band; zero-copy batch == streaming seam"""
+    import types
+    iq = np.random.default_rng(6).integers(0, 256, size=4 * (4 * 71280 + 5000), dtype=np.uint8)
+    ec.check_zero_copy_batch(emu_lib, [types.SimpleNamespace(iq=iq)], p1_async=True, l2_feedback=False, rtol=0.0)
 
 
 def test_emu_traceback_variants(emu_lib):

@@ -439,6 +439,27 @@ def test_gpu_symbol_kernel_256_lanes(hip_lib, oracle, captures):
         ec.check_golden_end_to_end(hip_lib, name, captures, tune=((ec.eng.TUNE_MIXFFT_SYMS, 32),))
 
 
+@pytest.mark.parametrize("syms", [0, 32])
+def test_gpu_zero_copy_batch_full_scale_captures(hip_lib, syms):
+    """The production kernels' fused half-band at full scale: two captures loud enough to hit the rails -- rms_lsb 120: 3.8 % of the bytes
+    are 0 or 255 (1.9 % each); rms_lsb 240: 28.5 % (14.4 % / 14.2 %), computed on the CPU; the usual 20 LSB capture has none -- through the
+    zero-copy batch against the streaming seam (the integer decimator), record for record at rtol 0, in both forms of the symbol kernel
+    (128 lanes; 32 = k_mixfft8, against its own streaming form).  Whatever the receiver makes of such captures: no frame is asserted."""
+    caps = [synth.fm_mp1_capture(0, seed=91, cfo_hz=45.0, offset=611, snr_db=20, n_blocks=24, rms_lsb=120.0),
+            synth.fm_mp1_capture(0, seed=92, cfo_hz=-310.0, offset=2750, snr_db=20, n_blocks=24, rms_lsb=240.0)]
+    for cap, lo, hi in zip(caps, (0.03, 0.25), (0.05, 0.32)):
+        assert lo < float(((cap.iq == 0) | (cap.iq == 255)).mean()) < hi
+    ec.check_zero_copy_batch(hip_lib, caps, p1_async=True, l2_feedback=False, mixfft_syms=syms, rtol=0.0, singles_tuned=bool(syms))
+
+
+def test_gpu_zero_copy_batch_full_range_noise(hip_lib):
+    """One stream of uniform random bytes 0..255 (test_gpu_noise_only_matches_oracle's is 100..155): nothing ever locks, so every block goes
+    through k_acq_decimate's half-band at full scale; zero-copy batch == streaming seam, record for record"""
+    import types
+    iq = np.random.default_rng(6).integers(0, 256, size=2 * 1488375, dtype=np.uint8)
+    ec.check_zero_copy_batch(hip_lib, [types.SimpleNamespace(iq=iq)], p1_async=True, l2_feedback=False, rtol=0.0)
+
+
 def test_gpu_traceback_variants(hip_lib):
     """single-path traceback == block-parallel traceback (records incl. the BER count, frames) on a capture with a noise frame"""
     ec.check_traceback_variants(hip_lib)
