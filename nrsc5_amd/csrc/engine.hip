@@ -316,7 +316,7 @@ extern "C" int nrsc5hip_engine_create(const nrsc5hip_config *cfg, nrsc5hip_engin
         if ((rc = dev_alloc(e, &e->flow_dev, e->flow_cap))) break;
         if (hipHostMalloc((void **)&e->flow_err, 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) { rc = NRSC5HIP_ENOMEM; break; }
         e->flow_err[0] = e->flow_err[1] = 0;
-        db.loop_exact = 1;                                     // the reference's own loop arithmetic in blocks that start un-synchronised (k_sync.hip; NRSC5HIP_TUNE_LOOP_EXACT)
+        db.loop_exact = 1;                                     // the reference's own loop arithmetic in blocks that start un-synchronised (sync_body.h; NRSC5HIP_TUNE_LOOP_EXACT)
         // Default (round 6): a freshly reset stream's FIRST block -- the block its CFO search runs on -- advances the oscillator by the reference's own float recurrence
         // (k_nco_exact), every later block by the closed-form phasor with the recurrence's amplitude ramp.  Measured on the MI355X with the loop arithmetic of k_sync on the
         // reference's own operations (loop_exact below): 0 of 722 locks through the CFO search deviate in any field (768 / 768 streams strict), against 5 failing + 8 counted

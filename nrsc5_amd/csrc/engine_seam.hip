@@ -60,7 +60,7 @@ static int ensure_space(nrsc5hip_engine *e, int s, long long incoming, bool on_i
 }
 
 // ---- streaming seam ---------------------------------------------------------------------------------------
-// (the report itself is the tail of the step's last kernel: k_stream_tail, k_sync.hip)
+// (the report itself is the tail of the step's last kernel: k_stream_tail, k_pids_px.hip)
 static int window_of(const nrsc5hip_engine *e, int s) { return e->mode_host[s] == MODE_AM ? AM_WIN : WIN_N; }
 
 

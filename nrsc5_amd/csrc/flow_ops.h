@@ -1,4 +1,4 @@
-// Hand-off primitives for work items of ONE launch that depend on each other (k_flow.hip): gfx950 has eight XCDs whose L2s are not coherent with each other and a
+// Hand-off primitives for work items of ONE launch that depend on each other (k_flow, k_sync.hip): gfx950 has eight XCDs whose L2s are not coherent with each other and a
 // vector L1 per CU that no other CU's store ever refreshes, so a value crosses from one workgroup to another only through
 //   * a store that goes THROUGH the caches (sc1: "write-through", the line is dropped from the writer's L2) and a load that goes past the reader's L1 (sc1), or
 //   * plain stores -> agent-scope RELEASE (buffer_wbl2 sc1: the XCD L2's dirty lines written back) -> flag -> agent-scope ACQUIRE on the reader (buffer_inv sc1) -> plain loads.

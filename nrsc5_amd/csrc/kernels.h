@@ -43,7 +43,7 @@ struct DevBuffers {
     float2 *bins;                    // [S][NSYM][LIVE_N]
     float2 *cfo_snap;                // [S][LIVE_N][11]  the CFO search's loop-state snapshots (k_sync: one per visit of a live bin)
     float *cfo_phase;                // [S][NSYM][LIVE_N]  exact CFO search (loop_exact): phases[][] of the visit in progress, one column per live bin
-    int loop_exact;                  // 0: fast loop arithmetic, 1: the reference's own operations in blocks that start un-synchronised, 2: in every block (k_sync.hip)
+    int loop_exact;                  // 0: fast loop arithmetic, 1: the reference's own operations in blocks that start un-synchronised, 2: in every block (sync_body.h)
     float2 *nco_tab;                 // [S][NSYM][SYM_N]  the reference's oscillator sample by sample for a block that runs in exact mode (k_nco_exact -> k_mixfft); null: closed form only
     int nco_policy;                  // NCO_*: which blocks of a freshly reset stream advance the oscillator by the reference's float recurrence
     int8_t *pm;                      // [S][NPM][PM_FRAME]  soft-bit interleaver matrices (one per frame in flight)
@@ -101,7 +101,7 @@ struct StreamReport { int counters[4]; long long rd; int nblocks; int nrec; Bloc
 // streaming seam, ONE stream: the chunk is read where the host staged it (pinned, device-visible: no copy engine, no second buffer),
 // every input byte once; the workgroup that finishes last rolls the decimator history and publishes the new write position
 void launch_decimate_fm_cu8_stream(const DevTables &tb, const DevBuffers &db, int s, const uint8_t *iq, unsigned nbytes, unsigned *ticket, hipStream_t st);
-// streaming seam, ONE stream: the block's PIDS frame (do_pids) and then the report
+// streaming seam, ONE stream: the block's PIDS frame (do_pids) and then the report (k_pids_px.hip)
 void launch_stream_tail(const DevTables &tb, const DevBuffers &db, int s, int first_rec, StreamReport *out, unsigned seq, int do_pids, hipStream_t st);
 
 void launch_decimate_fm_cu8(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids,
@@ -113,7 +113,7 @@ void launch_attach_raw(const DevBuffers &db, int nstreams, const int *stream_ids
 void launch_append_cs16(const DevBuffers &db, int nstreams, const int *stream_ids,
                         const int16_t *iq_base, long long iq_stride, const unsigned *nsamples, unsigned max_n, hipStream_t st);
 
-// ---- one block step for a set of streams ----------------------------------------------------
+// ---- one block step for a set of streams (k_acquire.hip, k_mixfft.hip, k_sync.hip; sync_body.h, mixfft_body.h) ----
 void launch_acquire(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st);
 void launch_prepare(const DevBuffers &db, int nstreams, const int *stream_ids, int acq_on, hipStream_t st);
 // streams whose current block runs in exact-oscillator mode (StreamState::nco_mode): the reference's 69 120-step float recurrence, one lane per stream
@@ -132,8 +132,9 @@ void launch_rollback_am(const DevBuffers &db, int nstreams, const int *stream_id
 // A stream must not be listed twice
 struct TrimPlan { long long off, n, base, wr; };
 void launch_trim(const DevBuffers &db, int nstreams, const int *stream_ids, TrimPlan *plan, int row_wgs, hipStream_t st);
+// behind the block step (k_pids_px.hip): the deferred PIDS decode ...
 void launch_pids_decode(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int nslots, hipStream_t st);
-// extended sidebands: interleaver IV for streams whose block pair just completed (after k_sync), and the staged P3/P4 decodes
+// ... extended sidebands: interleaver IV for streams whose block pair just completed (after k_sync), and the staged P3/P4 decodes
 void launch_px_deint(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int slot, hipStream_t st);
 void launch_px_decode(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int lane_id, hipStream_t st);
 // a window's P1 decode: de-interleave -> forward trellis pass -> traceback + BER + descramble + first-header verdict (+ fused L2 index)

@@ -1,5 +1,5 @@
 // The symbol transform of one workgroup (mix, CP fold, half-band, FFT-2048, live-bin cut) as device code shared by the kernels of k_mixfft.hip and the dataflow
-// kernel at the end of k_sync.hip (k_flow): everything here is inline / a template.  Moved out of k_mixfft.hip in round 6, unchanged.
+// kernel in k_sync.hip (k_flow): everything here is inline / a template.  Moved out of k_mixfft.hip in round 6, unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
@@ -411,7 +411,7 @@ template <int NT> struct SymPrologue {
     }
 };
 
-// FLOW (k_flow.hip): the bins leave WRITE-THROUGH (sc1 stores: straight to memory, dropped from this XCD's L2) -- the block step that consumes them runs as another
+// FLOW (k_flow, k_sync.hip): the bins leave WRITE-THROUGH (sc1 stores: straight to memory, dropped from this XCD's L2) -- the block step that consumes them runs as another
 // workgroup of the same launch, possibly on another XCD, and is released by a counter, not by a launch boundary.  wg: the workgroup's index among the stream's
 // NSYM / (SPW * NPAR) symbol workgroups (blockIdx.x of k_mixfft).
 template <bool RAW, int SPW, int NPAR, bool EXACT = false, bool FLOW = false>
@@ -554,7 +554,7 @@ __device__ __forceinline__ void mixfft_symbols(const DevTables &tb, const DevBuf
 #endif
 // NPAR = 2: two symbols of the stream side by side in one 256-lane workgroup (each half its own tile; the stage-B twiddle table, the
 // dispatch and the wave launch shared) -- half as many workgroups per launch at the same waves per SIMD
-// the workgroup's LDS as one struct (round 6: shared with the dataflow kernel, k_flow.hip)
+// the workgroup's LDS as one struct (round 6: shared with the dataflow kernel, k_flow in k_sync.hip)
 template <int NPAR> struct MixLds {
     alignas(16) cf lds_all[NPAR * 8 * PITCH_A];
     cf twB[256];
