@@ -458,6 +458,34 @@ int nrsc5hip_stage_math(nrsc5hip_engine *e, int fn, const void *a, const void *b
 enum { NRSC5HIP_HB_ACQ = 0, NRSC5HIP_HB_SYM128, NRSC5HIP_HB_SYM256 };
 int nrsc5hip_stage_halfband_raw(nrsc5hip_engine *e, int form, const uint8_t *iq, size_t nbytes, int lead, long long a0, long long n,
                                 int16_t *out, uint32_t *probe);
+/* ---- the FEC stage's permutations, error counts and descramblers on caller data (tests/fec_checks.py) ----------------------------------
+ * Each hook runs the PRODUCTION device code -- the production kernels themselves on stream 0 of the engine, which must exist and is left
+ * freshly reset (as nrsc5hip_stage_halfband_fm_cu8 does), or the production __device__ function called by a small stage kernel -- and
+ * returns what it wrote, raw.  NRSC5HIP_EINVAL with nothing launched: a null pointer, an unsupported length, a count below 1, an unknown
+ * mode / code / workgroup size.
+ * p1_deint: k_p1_deint (interleaver I + depuncture through tb.deint_lut).  pm int8 [16][23040], one L1 frame's soft-bit matrices ->
+ *   out [146176] dwords, one per trellis step: s0 | s1 << 8 | s2 << 16, punctured positions 0, byte 3 zero. */
+int nrsc5hip_stage_p1_deint(nrsc5hip_engine *e, const int8_t *pm, uint32_t *out);
+/* p1_frame: k_p1_forward + k_p1_fix + the traceback of the form `walk` selects (the value of NRSC5HIP_TUNE_TRACEBACK_WALK, 0 or 1; with
+ *   1 the re-encode count is the per-chunk counts of k_p1_tbwalk plus the six wrapped bits, with 0 the one loop of k_p1_traceback), l2_mode 0,
+ *   NRSC5HIP_TUNE_FWD_SEGMENTS honoured (16 when it is 0).  soft int8 [3 * 146176] as nrsc5hip_stage_viterbi_k7 takes it -> bits [146176]
+ *   after the descramble, *errors = the integer the BER record is made of. */
+int nrsc5hip_stage_p1_frame(nrsc5hip_engine *e, const int8_t *soft, int walk, uint8_t *bits, int *errors);
+/* pids: the gather + depuncture of block bc (0..15) through tb.pids_gather, then k_pids_decode (pids_decode_wave: 80-bit trellis, descramble,
+ *   CRC-12).  pm int8 [16][23040] -> coded [240], bits [80], *crc_ok. */
+int nrsc5hip_stage_pids(nrsc5hip_engine *e, const int8_t *pm, int bc, int8_t *coded, uint8_t *bits, int *crc_ok);
+/* px_interleave: k_px_deint + k_px_commit (interleaver IV through tb.px_delay_*) once per block pair, both channels live, from a fresh
+ *   interleaver state.  len 2304 or 4608; pairs int8 [npairs][2 channels][2 * len] -> out int8 [npairs][2][3 * len] (depunctured), ready[npairs]. */
+int nrsc5hip_stage_px_interleave(nrsc5hip_engine *e, int len, int npairs, const int8_t *pairs, int8_t *out, int *ready);
+/* am_deinterleave (engine with am_enable): k_am_interleave, all its slices and the commit, once per L1 frame from a fresh 3-frame delay ring.
+ *   psmi 1 (MA1) or 2 (MA3); sym uint8 [nframes][4][6400] in the order pl, pu, s, t -> v1 int8 [nframes][90000], v3 int8 [nframes][72000 (MA1) or 90000]. */
+int nrsc5hip_stage_am_deinterleave(nrsc5hip_engine *e, int psmi, int nframes, const uint8_t *sym, int8_t *v1, int8_t *v3);
+/* am_epilogue: am_bit_errors + am_descramble (k_am_decode.hip: am_p3_epilogue over am_decode_frame's choice of code) by one workgroup of
+ *   `threads` (64 or 256) work-items.  (len, code): (3750, NRSC5HIP_CODE_E1), (24000, NRSC5HIP_CODE_E2), (30000, NRSC5HIP_CODE_E1); soft int8 [3 * len],
+ *   bits uint8 [len] (the decoded, still scrambled frame -- the caller's choice) -> *errors, bits_out [len] and words_out [(len + 31) / 32] after the descramble. */
+enum { NRSC5HIP_CODE_E1 = 1, NRSC5HIP_CODE_E2 = 2 };
+int nrsc5hip_stage_am_epilogue(nrsc5hip_engine *e, const int8_t *soft, const uint8_t *bits, int len, int code, int threads, int *errors,
+                               uint8_t *bits_out, uint32_t *words_out);
 /* one frame, also returning the len+64 survivor-decision words of the forward pass */
 int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out);
 /* micro-benchmark of the Viterbi kernel on random frames: phases bit0 = forward, bit1 = traceback */

@@ -1,6 +1,7 @@
 // Test hooks and micro-benchmarks: every nrsc5hip_stage_* and nrsc5hip_debug_* entry point (single kernels on caller data, peeks at
 // device state, counters) and the tuning knobs (nrsc5hip_debug_tune).  Nothing here runs in a production pass.
 #include <algorithm>
+#include <cmath>
 #include "engine_internal.h"
 
 extern "C" void nrsc5hip_debug_seam_totals(double out[8], int reset)
@@ -258,6 +259,194 @@ extern "C" int nrsc5hip_stage_halfband_raw(nrsc5hip_engine *e, int form, const u
     HIPCHK(hipStreamSynchronize(e->main));
     HIPCHK(hipMemcpy(out, dout.p, nout * sizeof(c16), hipMemcpyDeviceToHost));
     if (probing) HIPCHK(hipMemcpy(probe, dprobe.p, (size_t)n * lanes * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the FEC stage on caller data (include/nrsc5hip.h; tests/fec_checks.py) ----------------------------------------------------------
+// The production kernels run on stream 0 of the engine: the hook resets it, writes the hand-off words the block step would have left
+// in its state, launches what launch_inorder_p1 / issue_step launch, and resets it again.  Nothing of the arithmetic lives here.
+#define POKE(base, type, field, value) do { const decltype(type::field) _v = (value); HIPCHK(hipMemcpy((char *)(base) + offsetof(type, field), &_v, sizeof(_v), hipMemcpyHostToDevice)); } while (0)
+#define POKE_AT(base, type, field, k, value) do { const int _v = (value); HIPCHK(hipMemcpy((char *)(base) + offsetof(type, field) + (k) * sizeof(int), &_v, sizeof(_v), hipMemcpyHostToDevice)); } while (0)
+
+// stream 0, freshly reset, FM; the buffer table without the consumers a stage run must not feed (the L2 index, the host's frame mirror)
+static int stage_stream0(nrsc5hip_engine *e, DevBuffers &db)
+{
+    int rc = check_stream(e, 0); if (rc) return rc;
+    if (e->mode_host[0] != MODE_FM) FAIL(NRSC5HIP_EINVAL, "stream 0 must be in FM mode");
+    if ((rc = nrsc5hip_stream_fresh(e, 0))) return rc;
+    db = e->db;
+    db.l2_ring = nullptr; db.l2_px_ring = nullptr; db.l2_am_ring = nullptr; db.p1_mirror = nullptr;
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_p1_deint(nrsc5hip_engine *e, const int8_t *pm, uint32_t *out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!pm || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    DevBuffers db; int rc = stage_stream0(e, db); if (rc) return rc;
+    HIPCHK(hipMemcpy(db.pm, pm, PM_FRAME, hipMemcpyHostToDevice));            // matrix slot 0 of stream 0
+    HIPCHK(hipMemset(db.coded, 0xA5, (size_t)P1_LEN * sizeof(int)));          // every dword must be written
+    POKE_AT(db.state, StreamState, p1_pending, 0, 1);
+    POKE_AT(db.state, StreamState, p1_pmslot, 0, 0);
+    launch_p1_deint(e->tb, db, 1, nullptr, 0, 0, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(out, db.coded, (size_t)P1_LEN * sizeof(int), hipMemcpyDeviceToHost));
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_stage_p1_frame(nrsc5hip_engine *e, const int8_t *soft, int walk, uint8_t *bits, int *errors)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!soft || !bits || !errors) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (walk != 0 && walk != 1) FAIL(NRSC5HIP_EINVAL, "walk %d: 0 (block-parallel traceback) or 1 (single-path walk)", walk);
+    DevBuffers db; int rc = stage_stream0(e, db); if (rc) return rc;
+    std::vector<int> words((size_t)P1_LEN);                                    // the dword per step k_p1_deint leaves for the forward pass
+    for (int i = 0; i < P1_LEN; i++) words[i] = (int)((uint32_t)(uint8_t)soft[3 * i] | (uint32_t)(uint8_t)soft[3 * i + 1] << 8 | (uint32_t)(uint8_t)soft[3 * i + 2] << 16);
+    HIPCHK(hipMemcpy(db.coded, words.data(), words.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(db.p1_ring, 0xA5, (size_t)P1_WORDS * sizeof(uint32_t)));
+    const float poison = -1.0f;
+    HIPCHK(hipMemcpy((char *)db.records + offsetof(BlockRecord, ber), &poison, sizeof(float), hipMemcpyHostToDevice));
+    POKE_AT(db.state, StreamState, p1_pending, 0, 1);
+    POKE_AT(db.state, StreamState, p1_slot, 0, 0);
+    POKE_AT(db.state, StreamState, p1_record, 0, 0);
+    const int segments = e->fwd_segments > 0 ? e->fwd_segments : 16;
+    launch_p1_forward(e->tb, db, 1, nullptr, 0, 0, e->main, segments, e->fwd_warm);
+    launch_p1_traceback(e->tb, db, 1, nullptr, 0, 0, e->main, 0, segments, walk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    std::vector<uint32_t> w((size_t)P1_WORDS);
+    float ber = -1.0f;
+    HIPCHK(hipMemcpy(w.data(), db.p1_ring, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&ber, (const char *)db.records + offsetof(BlockRecord, ber), sizeof(float), hipMemcpyDeviceToHost));
+    if (ber < 0.0f) FAIL(NRSC5HIP_EHIP, "the traceback left no error count");
+    nrsc5hip_unpack_bits(w.data(), P1_LEN, bits);
+    // the record holds (float)count / 365440 (decode.c:458): count < 2^19, so the quotient's rounding error times 365440 is below 0.03 and the integer comes back exactly
+    *errors = (int)llround((double)ber * P1_CODED);
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_stage_pids(nrsc5hip_engine *e, const int8_t *pm, int bc, int8_t *coded, uint8_t *bits, int *crc_ok)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!pm || !coded || !bits || !crc_ok) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (bc < 0 || bc > 15) FAIL(NRSC5HIP_EINVAL, "block count %d out of range", bc);
+    DevBuffers db; int rc = stage_stream0(e, db); if (rc) return rc;
+    HIPCHK(hipMemcpy(db.pm, pm, PM_FRAME, hipMemcpyHostToDevice));
+    const int rec0 = 0;
+    const uint32_t clear[4] = { 0, 0, 0, 0 };
+    HIPCHK(hipMemcpy((char *)db.records + offsetof(BlockRecord, flags), clear, sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char *)db.records + offsetof(BlockRecord, pids), clear, 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    launch_stage_pids_gather(e->tb, db.pm, bc, db.pids_stage, e->main);         // window slot 0, frame slot 0 of stream 0
+    HIPCHK(hipMemcpyAsync(db.pids_rec, &rec0, sizeof(int), hipMemcpyHostToDevice, e->main));
+    launch_pids_decode(e->tb, db, 1, nullptr, 0, 1, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    BlockRecord rec;
+    int left = 0;
+    HIPCHK(hipMemcpy(coded, db.pids_stage, 3 * PIDS_LEN, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rec, db.records, sizeof(rec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&left, db.pids_rec, sizeof(int), hipMemcpyDeviceToHost));
+    if (left != -1) FAIL(NRSC5HIP_EHIP, "the staged PIDS frame was not decoded");
+    nrsc5hip_unpack_bits(rec.pids, PIDS_LEN, bits);
+    *crc_ok = (rec.flags & REC_PIDS_CRC) ? 1 : 0;
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_stage_px_interleave(nrsc5hip_engine *e, int len, int npairs, const int8_t *pairs, int8_t *out, int *ready)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!pairs || !out || !ready) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (len != PX_MAX && len != PX_MAX / 2) FAIL(NRSC5HIP_EINVAL, "frame length %d: %d or %d", len, PX_MAX / 2, PX_MAX);
+    if (npairs < 1) FAIL(NRSC5HIP_EINVAL, "bad pair count");
+    DevBuffers db; int rc = stage_stream0(e, db); if (rc) return rc;
+    HIPCHK(hipMemset(db.px_mem, 0, (size_t)2 * PX_MEM));                      // a fresh interleaver: the reference's calloc'd memory
+    POKE(db.state, StreamState, px_nch, 2);
+    POKE(db.state, StreamState, px_record, 0);
+    POKE(db.state, StreamState, px_slot, 0);
+    for (int p = 0; p < npairs; p++) {
+        for (int ch = 0; ch < 2; ch++)
+            HIPCHK(hipMemcpy(db.px_pair + (size_t)ch * 2 * PX_MAX, pairs + ((size_t)p * 2 + ch) * 2 * len, (size_t)2 * len, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(db.px_stage, 0x5A, (size_t)2 * PX_DEPUNCT));
+        POKE(db.state, StreamState, px_go, len);                               // k_px_commit clears it
+        launch_px_deint(e->tb, db, 1, nullptr, 0, 0, e->main);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->main));
+        PxJob job[2];
+        HIPCHK(hipMemcpy(job, db.px_job, sizeof(job), hipMemcpyDeviceToHost));
+        if ((job[0].rec < 0) != (job[1].rec < 0) || job[0].len != len || job[1].len != len) FAIL(NRSC5HIP_EHIP, "the two channels' jobs disagree");
+        ready[p] = job[0].rec >= 0 ? 1 : 0;
+        for (int ch = 0; ch < 2; ch++)
+            HIPCHK(hipMemcpy(out + ((size_t)p * 2 + ch) * 3 * len, db.px_stage + (size_t)ch * PX_DEPUNCT, (size_t)3 * len, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemset(db.px_mem, 0, (size_t)2 * PX_MEM));
+    HIPCHK(hipMemset(db.px_job, 0xff, 2 * sizeof(PxJob)));
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_stage_am_deinterleave(nrsc5hip_engine *e, int psmi, int nframes, const uint8_t *sym, int8_t *v1, int8_t *v3)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!sym || !v1 || !v3) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (psmi != 1 && psmi != AM_MA3) FAIL(NRSC5HIP_EINVAL, "service mode %d: 1 (MA1) or 2 (MA3)", psmi);
+    if (nframes < 1) FAIL(NRSC5HIP_EINVAL, "bad frame count");
+    if (!e->db.am) FAIL(NRSC5HIP_EINVAL, "engine was created without am_enable");
+    DevBuffers db; int rc = stage_stream0(e, db); if (rc) return rc;
+    const size_t n3 = psmi == AM_MA3 ? (size_t)AM_VIT : (size_t)3 * AM_P3_LEN_MA1;
+    HIPCHK(hipMemset(db.am_q, 0, (size_t)3 * 2 * AM_VIT));                    // a fresh delay ring: the reference's calloc'd delay lines
+    POKE(db.state, StreamState, active, 1);
+    POKE(db.am, AmStream, dec_bc, 7);
+    POKE(db.am, AmStream, dec_psmi, psmi);
+    POKE(db.am, AmStream, dec_rdbi, 0);
+    POKE(db.am, AmStream, dec_record, 0);
+    for (int f = 0; f < nframes; f++) {
+        HIPCHK(hipMemcpy(db.am_sym, sym + (size_t)f * 4 * AM_SYMS, (size_t)4 * AM_SYMS, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(db.am_vit, 0x5A, (size_t)2 * AM_VIT));
+        launch_am_interleave(e->tb, db, 1, nullptr, -1, 0, e->main);           // all AM_IL_PARTS slices; the last one commits (delay-line head)
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->main));
+        HIPCHK(hipMemcpy(v1 + (size_t)f * AM_VIT, db.am_vit, AM_VIT, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(v3 + (size_t)f * n3, db.am_vit + AM_VIT, n3, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemset(db.am_q, 0, (size_t)3 * 2 * AM_VIT));
+    HIPCHK(hipMemset(db.am_vit, 0, (size_t)2 * AM_VIT));
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_stage_am_epilogue(nrsc5hip_engine *e, const int8_t *soft, const uint8_t *bits, int len, int code, int threads, int *errors,
+                                          uint8_t *bits_out, uint32_t *words_out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!soft || !bits || !errors || !bits_out || !words_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (threads != 64 && threads != 256) FAIL(NRSC5HIP_EINVAL, "workgroup size %d: 64 or 256", threads);
+    // the frames of an AM L1 frame (am_decode_frame): P1 = role 0, E1; P3 = role 8: MA1 E2, MA3 E1
+    int role, psmi;
+    if (len == AM_P1_LEN && code == NRSC5HIP_CODE_E1) { role = 0; psmi = 1; }
+    else if (len == AM_P3_LEN_MA1 && code == NRSC5HIP_CODE_E2) { role = 8; psmi = 1; }
+    else if (len == AM_P3_LEN_MA3 && code == NRSC5HIP_CODE_E1) { role = 8; psmi = AM_MA3; }
+    else FAIL(NRSC5HIP_EINVAL, "no AM frame of %d bits with code %d", len, code);
+    const int words = (len + 31) / 32, word0 = role == 8 ? AM_P3_WORD0 : 0;
+    static_assert(AM_P3_WORD0 + (AM_P3_LEN_MA3 + 31) / 32 <= P1_WORDS, "an AM L1 frame fits a frame slot");
+    std::vector<uint32_t> w((size_t)P1_WORDS, 0xA5A5A5A5u);
+    for (int k = 0; k < words; k++) w[word0 + k] = 0;
+    for (int i = 0; i < len; i++) if (bits[i] & 1) w[word0 + (i >> 5)] |= 1u << (i & 31);
+    if (len & 31) w[word0 + words - 1] |= ~((1u << (len & 31)) - 1u);            // the last word's bits beyond the frame arrive set: the descramble must clear them
+    DevTmp dvit, dslot, derr;
+    HIPCHK(hipMalloc(&dvit.p, (size_t)2 * AM_VIT));
+    HIPCHK(hipMalloc(&dslot.p, (size_t)P1_WORDS * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&derr.p, sizeof(int)));
+    HIPCHK(hipMemset(dvit.p, 0, (size_t)2 * AM_VIT));
+    HIPCHK(hipMemset(derr.p, 0xff, sizeof(int)));
+    HIPCHK(hipMemcpy((int8_t *)dvit.p + (role == 8 ? AM_VIT : 0), soft, (size_t)3 * len, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dslot.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    launch_stage_am_epilogue(e->tb, (const int8_t *)dvit.p, (uint32_t *)dslot.p, role, psmi, threads, (int *)derr.p, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(w.data(), dslot.p, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(errors, derr.p, sizeof(int), hipMemcpyDeviceToHost));
+    for (int k = 0; k < P1_WORDS; k++) if ((k < word0 || k >= word0 + words) && w[k] != 0xA5A5A5A5u) FAIL(NRSC5HIP_EHIP, "the epilogue wrote word %d, outside its frame", k);
+    memcpy(words_out, w.data() + word0, (size_t)words * sizeof(uint32_t));
+    nrsc5hip_unpack_bits(w.data() + word0, len, bits_out);
     return 0;
 }
 

@@ -779,7 +779,12 @@ void launch_am_step(const DevTables &tb, const DevBuffers &db, int nstreams, con
     if (pipeline_parity >= 0) hipLaunchKernelGGL(k_am_block<512>, dim3(nstreams), dim3(512), sizeof(AmBlockSmem), st, tb, db, stream_ids, 1, pipeline_parity, slot);
     else hipLaunchKernelGGL(k_am_block<256>, dim3(nstreams), dim3(256), sizeof(AmBlockSmem), st, tb, db, stream_ids, 0, pipeline_parity, slot);
     if (pipeline_parity < 0) launch_am_decode_in_order(tb, db, nstreams, stream_ids, l2_feedback, st);
-    hipLaunchKernelGGL(k_am_interleave, dim3(AM_IL_PARTS, nstreams), dim3(AM_IL_THREADS), 0, st, tb, db, stream_ids, pipeline_parity, window);
+    launch_am_interleave(tb, db, nstreams, stream_ids, pipeline_parity, window, st);
+}
+
+void launch_am_interleave(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int window, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_am_interleave, dim3(AM_IL_PARTS, nstreams), dim3(AM_IL_THREADS), 0, st, tb, db, stream_ids, parity, window);
 }
 
 }  // namespace nrsc5

@@ -38,7 +38,7 @@ __device__ inline void am_descramble(uint32_t *out, const uint32_t *scr, int len
 {
     const int words = (len + 31) / 32;
     const uint32_t tailmask = (len & 31) ? (1u << (len & 31)) - 1u : 0xffffffffu;
-    for (int w = threadIdx.x; w < words; w += 64) out[w] = (out[w] ^ scr[w]) & (w == words - 1 ? tailmask : 0xffffffffu);
+    for (int w = threadIdx.x; w < words; w += blockDim.x) out[w] = (out[w] ^ scr[w]) & (w == words - 1 ? tailmask : 0xffffffffu);
 }
 
 // the frame's (still scrambled) bits are in f.out and visible to the workgroup: bit errors against the trellis inputs, descramble
@@ -244,6 +244,20 @@ void launch_am_decode(const DevTables &tb, const DevBuffers &db, int nstreams, c
     hipLaunchKernelGGL(k_am_decode_tb, dim3(8 + G, nstreams), dim3(64), 0, st, tb, db, stream_ids, parity, lane_id, G, runin, l2_feedback);
     hipLaunchKernelGGL(k_am_decode_finish, dim3(nstreams), dim3(64), 0, st, tb, db, stream_ids, parity, lane_id, G);
     if (db.l2_am_ring) launch_l2_index_am_window(db, nstreams, stream_ids, parity, st);
+}
+
+// ---- stage-level entry (nrsc5hip_stage_am_epilogue): the frame epilogue alone, on a frame laid out as am_decode_frame expects it ----
+template <int NT> __global__ __launch_bounds__(NT) void k_stage_am_epilogue(DevTables tb, const int8_t *vit, uint32_t *slot, int role, int psmi, int *err)
+{
+    __shared__ int red[4];
+    const AmDecodeFrame f = am_decode_frame(vit, slot, nullptr, role, psmi);
+    const int n = am_p3_epilogue(tb, f, red);
+    if (threadIdx.x == 0) *err = n;
+}
+void launch_stage_am_epilogue(const DevTables &tb, const int8_t *vit, uint32_t *slot, int role, int psmi, int threads, int *err, hipStream_t st)
+{
+    if (threads == 256) hipLaunchKernelGGL(k_stage_am_epilogue<256>, dim3(1), dim3(256), 0, st, tb, vit, slot, role, psmi, err);
+    else hipLaunchKernelGGL(k_stage_am_epilogue<64>, dim3(1), dim3(64), 0, st, tb, vit, slot, role, psmi, err);
 }
 
 // ---- stage-level entry: decode `nframes` independent K=9 frames (parity tests) ------------------------------------

@@ -82,6 +82,20 @@ void launch_pids_decode(const DevTables &tb, const DevBuffers &db, int nstreams,
     hipLaunchKernelGGL(k_pids_decode, dim3(nslots, nstreams), dim3(64), 0, st, tb, db, stream_ids, parity);
 }
 
+// ---- stage-level entry (nrsc5hip_stage_pids): the gather + depuncture k_sync runs in front of k_pids_decode -- sync_body.h's two lines restated
+// over the production table (factoring them out of the block step would touch k_sync / k_flow; the table is what the test is about), the soft
+// bits read from the frame's matrices in global memory
+__global__ __launch_bounds__(256) void k_stage_pids_gather(DevTables tb, const int8_t *pm, int bc, int8_t *stage)
+{
+    const int tid = threadIdx.x;
+    for (int n = tid; n < PIDS_CODED; n += 256) stage[n + n / 5] = pm[(size_t)bc * PM_BLOCK + (int)tb.pids_gather[bc * PIDS_CODED + n]];
+    for (int n = tid; n < PIDS_CODED / 5; n += 256) stage[6 * n + 5] = 0;
+}
+void launch_stage_pids_gather(const DevTables &tb, const int8_t *pm, int bc, int8_t *stage, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_stage_pids_gather, dim3(1), dim3(256), 0, st, tb, pm, bc, stage);
+}
+
 // ---- extended sidebands: interleaver IV (decode.c:344-376) for a completed block pair ----------------------------
 // The interleaver is convolutional: the bit read at position i of a pair was written delay[i] positions earlier
 // (1..N, N = 32 blocks), either earlier in this pair (take it from the pair buffer) or in the memory.  All reads of a

@@ -191,5 +191,13 @@ void launch_fft2048(const DevTables &tb, const float2 *in, float2 *out, int nfft
 // and probe[nsyms][lanes][4] for the rounding-mode probes, both null for none.  Acquisition form (k_acquire.hip): n samples from a0.
 void launch_stage_halfband_sym(const DevTables &tb, int lanes, const uint8_t *raw, long long a0, int nsyms, c16 *out, const float *pc, uint32_t *probe, hipStream_t st);
 void launch_stage_halfband_acq(const DevTables &tb, const uint8_t *raw, long long a0, long long n, c16 *out, hipStream_t st);
+// the FEC stage hooks (nrsc5hip_stage_pids / _am_deinterleave / _am_epilogue; the others need the production launchers above only).
+// PIDS gather + depuncture of block bc of the soft-bit matrices pm through tb.pids_gather into stage[240] (k_pids_px.hip: sync_body.h's two lines restated)
+void launch_stage_pids_gather(const DevTables &tb, const int8_t *pm, int bc, int8_t *stage, hipStream_t st);
+// k_am_interleave alone (k_am.hip; launch_am_step's last launch)
+void launch_am_interleave(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int window, hipStream_t st);
+// am_p3_epilogue (k_am_decode.hip) on the frame am_decode_frame(vit, slot, ., role, psmi) describes, one workgroup of `threads`: vit [2][AM_VIT]
+// trellis inputs, slot [P1_WORDS] the packed decoded bits (descrambled in place), *err the count
+void launch_stage_am_epilogue(const DevTables &tb, const int8_t *vit, uint32_t *slot, int role, int psmi, int threads, int *err, hipStream_t st);
 
 }  // namespace nrsc5

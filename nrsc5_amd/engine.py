@@ -100,6 +100,7 @@ L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
 TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
 MATH_REF_SINCOSF, MATH_REF_ATAN2F, MATH_FAST_SINCOS, MATH_FAST_SINCOS_REDUCED, MATH_FAST_ATAN2, MATH_SMALL_COS_SIN, MATH_SMALL_ATAN = range(7)   # NRSC5HIP_MATH_*
 HB_ACQ, HB_SYM128, HB_SYM256 = range(3)     # NRSC5HIP_HB_*: the forms of the fused half-band (csrc/halfband_raw.h)
+CODE_E1, CODE_E2 = 1, 2                     # NRSC5HIP_CODE_*: the two K=9 codes of the AM path
 HB_SYM_N = 2160                             # decimated samples of one symbol
 L2_STATUS = ("end", "no_audio", "fixed_data", "header_rs", "bad_locators", "too_many_pdus", "hef_overrun", "bad_stream", "bad_length", "audio_end")
 
@@ -176,6 +177,12 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_stage_first_header.argtypes = [vp, vp, ci, ci, ci, vp]
     lib.nrsc5hip_stage_math.argtypes = [vp, ci, vp, vp, ctypes.c_longlong, vp, vp]
     lib.nrsc5hip_stage_halfband_raw.argtypes = [vp, ci, vp, ctypes.c_size_t, ci, ctypes.c_longlong, ctypes.c_longlong, vp, vp]
+    lib.nrsc5hip_stage_p1_deint.argtypes = [vp, vp, vp]
+    lib.nrsc5hip_stage_p1_frame.argtypes = [vp, vp, ci, vp, vp]
+    lib.nrsc5hip_stage_pids.argtypes = [vp, vp, ci, vp, vp, vp]
+    lib.nrsc5hip_stage_px_interleave.argtypes = [vp, ci, ci, vp, vp, vp]
+    lib.nrsc5hip_stage_am_deinterleave.argtypes = [vp, ci, ci, vp, vp, vp]
+    lib.nrsc5hip_stage_am_epilogue.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
     lib.nrsc5hip_debug_poison_results.argtypes = [vp]
     lib.nrsc5hip_debug_seam_totals.argtypes = [vp, ci]
     lib.nrsc5hip_debug_seam_totals.restype = None
@@ -239,7 +246,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
-    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
+    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
     "nrsc5hip_stream_set_mode", "nrsc5hip_am_frame_bits", "nrsc5hip_stage_viterbi_k9", "nrsc5hip_px_frame_bits",
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
@@ -281,6 +288,20 @@ def check_fresh(path: str | None = None):
 def unpack_bits(words: np.ndarray, nbits: int) -> np.ndarray:
     w = np.ascontiguousarray(words, dtype="<u4")
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:nbits]
+
+
+def _exact(a, dtype, size):
+    """a stage hook's input: None stays None (the hook rejects it), anything else must hold exactly what the hook reads"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    if a.size != size:
+        raise ValueError("expected %d elements, got %d" % (size, a.size))
+    return a
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
 
 
 class Engine:
@@ -662,6 +683,52 @@ class Engine:
         self._check(self.lib.nrsc5hip_stage_halfband_raw(self._h, form, iq.ctypes.data, iq.size, lead, a0, n, out.ctypes.data,
                                                          pr.ctypes.data if pr is not None else None))
         return (out, pr) if probe else out
+
+    # the FEC stage's permutations, error counts and descramblers: the production device code on caller data (tests/fec_checks.py)
+    def stage_p1_deint(self, pm: np.ndarray) -> np.ndarray:
+        """nrsc5hip_stage_p1_deint: k_p1_deint on the soft-bit matrices pm int8 [16 * 23040] -> uint32 [146176], one dword per trellis step"""
+        pm = _exact(pm, np.int8, 16 * 23040)
+        out = np.zeros(146176, dtype=np.uint32)
+        self._check(self.lib.nrsc5hip_stage_p1_deint(self._h, _ptr(pm), out.ctypes.data))
+        return out
+
+    def stage_p1_frame(self, soft: np.ndarray, walk: int = 1):
+        """nrsc5hip_stage_p1_frame: forward pass, fix and the traceback of form `walk` on soft int8 [3 * 146176] -> (descrambled bits [146176], error count)"""
+        soft = _exact(soft, np.int8, 3 * 146176)
+        bits = np.zeros(146176, dtype=np.uint8)
+        err = ctypes.c_int(-1)
+        self._check(self.lib.nrsc5hip_stage_p1_frame(self._h, _ptr(soft), walk, bits.ctypes.data, ctypes.byref(err)))
+        return bits, err.value
+
+    def stage_pids(self, pm: np.ndarray, bc: int):
+        """nrsc5hip_stage_pids: gather + depuncture of block bc, k_pids_decode -> (coded int8 [240], descrambled bits [80], CRC flag)"""
+        pm = _exact(pm, np.int8, 16 * 23040)
+        coded, bits, ok = np.zeros(240, dtype=np.int8), np.zeros(80, dtype=np.uint8), ctypes.c_int(-1)
+        self._check(self.lib.nrsc5hip_stage_pids(self._h, _ptr(pm), bc, coded.ctypes.data, bits.ctypes.data, ctypes.byref(ok)))
+        return coded, bits, ok.value
+
+    def stage_px_interleave(self, length: int, pairs: np.ndarray, npairs: int | None = None):
+        """nrsc5hip_stage_px_interleave: pairs int8 [npairs, 2, 2 * length] -> (int8 [npairs, 2, 3 * length], ready int32 [npairs])"""
+        n = (pairs.size // max(4 * length, 1) if pairs is not None else 0) if npairs is None else npairs
+        pairs = _exact(pairs, np.int8, max(n, 0) * 4 * length)
+        out, ready = np.zeros((max(n, 0), 2, 3 * max(length, 0)), dtype=np.int8), np.full(max(n, 0), -1, dtype=np.int32)
+        self._check(self.lib.nrsc5hip_stage_px_interleave(self._h, length, n, _ptr(pairs), out.ctypes.data, ready.ctypes.data))
+        return out, ready
+
+    def stage_am_deinterleave(self, psmi: int, sym: np.ndarray, nframes: int | None = None):
+        """nrsc5hip_stage_am_deinterleave: sym uint8 [nframes, 4 (pl, pu, s, t), 6400] -> (v1 int8 [nframes, 90000], v3 int8 [nframes, 72000 | 90000])"""
+        n = (sym.size // (4 * 6400) if sym is not None else 0) if nframes is None else nframes
+        sym = _exact(sym, np.uint8, max(n, 0) * 4 * 6400)
+        v1, v3 = np.zeros((max(n, 0), 90000), dtype=np.int8), np.zeros((max(n, 0), 90000 if psmi == 2 else 72000), dtype=np.int8)
+        self._check(self.lib.nrsc5hip_stage_am_deinterleave(self._h, psmi, n, _ptr(sym), v1.ctypes.data, v3.ctypes.data))
+        return v1, v3
+
+    def stage_am_epilogue(self, soft: np.ndarray, bits: np.ndarray, length: int, code: int, threads: int = 64):
+        """nrsc5hip_stage_am_epilogue: am_bit_errors + am_descramble -> (error count, descrambled bits [length], the packed words)"""
+        soft, bits = _exact(soft, np.int8, 3 * max(length, 0)), _exact(bits, np.uint8, max(length, 0))
+        out, words, err = np.zeros(max(length, 0), dtype=np.uint8), np.zeros((max(length, 0) + 31) // 32, dtype=np.uint32), ctypes.c_int(-1)
+        self._check(self.lib.nrsc5hip_stage_am_epilogue(self._h, _ptr(soft), _ptr(bits), length, code, threads, ctypes.byref(err), out.ctypes.data, words.ctypes.data))
+        return err.value, out, words
 
     def stage_selftest(self) -> int:
         n = ctypes.c_int(-1)

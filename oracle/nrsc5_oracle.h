@@ -6,7 +6,7 @@
  *
  * Pinning: the reference ships no unit tests or stage vectors; this
  * restatement is pinned against the UNMODIFIED reference compiled into oracle/_ref/
- * (tests/test_oracle_vs_reference.py: exact Q15 stream, soft bits, PIDS/P1 frames,
+ * (tests/test_oracle.py, test_oracle_am.py, test_oracle_l2.py: exact Q15 stream, soft bits, PIDS/P1 frames,
  * per-block timing/CFO trace) and against the fixtures under tests/golden/ that the
  * same reference build produced.  The FFT (third-party fftw3f in the reference,
  * absent here) is oracle/cpu_fft.c in both builds: parity unpinned at that boundary,
@@ -36,7 +36,8 @@ enum {
 };
 enum { ORC_TAP_Q15 = 1, ORC_TAP_FFT = 2, ORC_TAP_SOFT = 4 };
 
-/* ---- stage functions: each is the CPU twin of one HIP kernel ------------------------- */
+/* ---- stage functions: each is the CPU twin of one HIP kernel (compared with it directly in
+ * tests/fec_checks.py, halfband_checks.py, engine_checks.py) ---------------------------- */
 
 /* K1  input.c:52-69 + firdecim_q15.c:137-165.  cu8 -> Q15 -> 15-tap half-band, 2:1.
  * hist = last 14 Q15 samples pushed (zeros for a fresh session); nbytes % 4 == 0.

@@ -62,6 +62,16 @@ class _Snapshot(ctypes.Structure):
 P1_HOOK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)
 
 
+class PxState:
+    """what orc_interleave_px keeps between the block pairs of one channel: interleaver_iv_t (decode.h:9-17), as calloc leaves it"""
+
+    def __init__(self):
+        self.mem = np.zeros(32 * 4608, dtype=np.int8)
+        self.pos = ctypes.c_uint(0)
+        self.taken = (ctypes.c_uint * 4)(0, 0, 0, 0)
+        self.ready = ctypes.c_int(0)
+
+
 class Oracle:
     def __init__(self):
         self.lib = L = ctypes.CDLL(build())
@@ -84,6 +94,7 @@ class Oracle:
         L.orc_cp_correlate_fm.argtypes = [vp, ctypes.POINTER(ctypes.c_int), vp]
         L.orc_deinterleave_p1.argtypes = [vp, vp]
         L.orc_deinterleave_pids.argtypes = [vp, ctypes.c_uint, vp]
+        L.orc_interleave_px.argtypes = [vp, vp, vp, vp, vp, ctypes.c_uint, vp]
         L.orc_viterbi_k7.argtypes = [vp, ctypes.c_int, vp]
         L.orc_viterbi.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp]
         L.orc_descramble.argtypes = [vp, ctypes.c_uint]
@@ -147,6 +158,16 @@ class Oracle:
         out = np.zeros(240, dtype=np.int8)
         self.lib.orc_deinterleave_pids(pm.ctypes.data, bc, out.ctypes.data)
         return out
+
+    def interleave_px(self, pair: np.ndarray, frame_len: int, state: "PxState | None" = None):
+        """interleaver IV for one block pair (2 * frame_len soft bits) of one channel -> (3 * frame_len depunctured trellis inputs, ready,
+        state); mem / pos / taken / ready live in `state` between calls (None: a fresh interleaver)."""
+        st = PxState() if state is None else state
+        pair = np.ascontiguousarray(pair, dtype=np.int8).reshape(-1)
+        assert pair.size == 2 * frame_len and frame_len in (2304, 4608)
+        out = np.zeros(3 * frame_len, dtype=np.int8)
+        self.lib.orc_interleave_px(st.mem.ctypes.data, ctypes.byref(st.pos), st.taken, ctypes.byref(st.ready), pair.ctypes.data, frame_len, out.ctypes.data)
+        return out, int(st.ready.value), st
 
     def viterbi_k7(self, soft: np.ndarray) -> np.ndarray:
         soft = np.ascontiguousarray(soft, dtype=np.int8)
