@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 11   /* 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 12   /* 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -413,6 +413,64 @@ size_t nrsc5hip_hdc_host_bytes(const nrsc5hip_hdc *h);                /* host me
  * Walk such a frame on the host, or nrsc5hip_hdc_reset the stream. */
 int nrsc5hip_hdc_feed(nrsc5hip_hdc *h, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
                       const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_hdc_cb cb, void *opaque);
+
+/* ---- PSD transport: now-playing text without the audio payload (device side: csrc/k_psd.hip) ---------------------------------
+ * Program service data travels as an HDLC byte stream cut across the audio PDUs of each program; the reference reassembles it in
+ * parse_hdlc / aas_push (frame.c:328-391, 611) into AAS packets, of which ports 0x5100 and 0x5201..0x5207 carry ID3 tags
+ * (output.c:874-882).  This consumer does that on the device, over the L2 index and the RS-corrected PDU bytes of the frames the records
+ * name, which stay in HBM: per (consumer stream, program 0..7) it keeps frame_t.psd_buf / psd_idx (8212 bytes and an index, -1 = closed;
+ * 66 KB per stream) in device memory, and only finished packets are copied to the host.
+ * Rules, each equal to the reference's: bytes [psd_off, psd_off + psd_len) of every PDU the walk keeps (skipped == 0), whatever its
+ * stream_id or logical channel, go to the state of its prog_num -- P1, P3, P4 and AM frames of one stream share the eight states.  0x7E
+ * closes the open frame (if one is open) and opens the next; any other byte is stored while the frame is open and shorter than 8212 raw
+ * bytes, the byte that finds it full closes it unseen (overflow) and the bytes up to the next 0x7E are dropped.  A closed frame is
+ * unescaped (0x7D takes the next byte OR 0x20), an empty one is padding, one whose fcs16 is not 0xF0B8 or whose first byte is not 0x21 is
+ * dropped; what remains between the protocol byte and the FCS is one AAS packet: port (16 bits, little endian), seq (the same), data.
+ * Deviations: a frame whose last raw byte is an unpaired 0x7D is dropped ("truncated escape"; the reference ORs one stale byte of its
+ * buffer in, and the FCS then fails); a packet shorter than port + seq is dropped as wrong protocol (the reference reads past it). */
+typedef struct nrsc5hip_psd nrsc5hip_psd;
+/* data / len: what follows port and seq */
+typedef void (*nrsc5hip_aas_cb)(void *opaque, int stream, unsigned program, unsigned port, unsigned seq, const uint8_t *data, unsigned len);
+/* nstreams consumer streams on the engine's device; destroy the consumer before its engine */
+int nrsc5hip_psd_create(nrsc5hip_engine *e, int nstreams, nrsc5hip_psd **out);
+void nrsc5hip_psd_destroy(nrsc5hip_psd *p);
+int nrsc5hip_psd_reset(nrsc5hip_psd *p, int stream);                 /* all eight indices to -1 (frame_reset, frame.c:730-733) */
+/* The contract of nrsc5hip_hdc_feed: the same records, lists and targets, the frames must still be in the ring slots the records name,
+ * and ids out of range (engine or consumer), a NULL records[i] with counts[i] > 0, a mode that is neither FM nor AM and a record that
+ * names a slot the engine does not have are NRSC5HIP_EINVAL before anything is touched; so is a consumer stream listed twice.  A record
+ * with NRSC5HIP_REC_TO_FINE closes the stream's eight programs before that record's frames (sync.c:405-409); a loss of sync changes
+ * nothing.  ONE index launch, ONE k_psd launch (a wave64 workgroup per listed stream) and one copy of the finished packets for the whole
+ * call.  Packets are delivered through cb (may be NULL: count only) inside the call, all of stream_ids[0] first, each stream's in the
+ * order of its bytes; `program` is the program whose PDU carried the closing flag.  Returns the number of packets or a negative error; a
+ * session may be fed in any number of calls.
+ * Frames whose PCI announces fixed-data sub-channels (NRSC5HIP_L2_PCI_HAS_FIXED, and the fixed-only PCI): their index and PDU bytes --
+ * only theirs -- are copied to the host, where process_fixed_data's state (private to the consumer, cleared on NRSC5HIP_REC_TO_FINE like
+ * nrsc5hip_hdc_frame_reset) gives the cut (nrsc5hip_hdc_fixed_audio_end, nrsc5hip_l2_apply_audio_end).  A header expansion running into
+ * the fixed region is NRSC5HIP_EINVAL as in nrsc5hip_hdc_feed: the PSD states are untouched then, the fixed-data state has advanced.
+ * With several streams in the call, the fixed-data states of the streams listed in front of the failing frame have advanced over their
+ * whole record lists, the failing stream's up to that frame.  Each fixed-data frame costs two blocking copies of its own (index struct,
+ * PDU bytes: about 21 KB for a P1 frame), issued frame by frame between the two launches; no byte bound holds for such sessions.
+ * Device -> host per call otherwise: 4 bytes per frame of the call (the PCI words, one strided copy), 16 bytes of arena header, and per
+ * packet 12 bytes + its data padded to 4 -- so "the packets + 16 bytes each + 256 bytes per listed stream" holds up to 60 frames per
+ * stream and call, and the frames themselves never cross.
+ * NRSC5HIP_EOVERFLOW: the packet arena, sized from the host-known bounds, was too small (never a silent drop). */
+int nrsc5hip_psd_feed(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
+                      const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_aas_cb cb, void *opaque);
+/* Counters of one consumer stream since its creation: [0] PDUs walked, [1] span bytes, [2] frames closed, [3] empty frames, [4] bad FCS,
+ * [5] wrong protocol, [6] truncated escape, [7] overflows, [8] packets delivered ([2] = [3] + ... + [6] + [8]); [9] bytes the feeds copied
+ * device -> host, total over the consumer. */
+int nrsc5hip_psd_stats(nrsc5hip_psd *p, int stream, long long stats[10]);
+/* stage-level twin: nframes logical frames given as frame_push takes them (one bit per byte, nbits each; as nrsc5hip_stage_l2_index), of
+ * logical channel lc, fed in order to consumer stream `stream` through the production index kernel and k_psd */
+int nrsc5hip_stage_psd(nrsc5hip_psd *p, nrsc5hip_engine *e, int stream, const uint8_t *bits, int nbits, int nframes, int lc,
+                       nrsc5hip_aas_cb cb, void *opaque);
+/* ... and the same for several consumer streams in ONE call, the shape of a feed: one index launch over all frames, one k_psd launch with a
+ * workgroup per listed stream, one arena, delivery "all of targets[0] first".  Stream i of the call: consumer stream targets[i] (no stream
+ * twice), nframes[i] frames of nbits[i] bits at bits[i], logical channel lcs[i].  reset_at (may be NULL; entries < 0: none): the stream
+ * gets what a NRSC5HIP_REC_TO_FINE record does -- its eight programs closed, the fixed-data state cleared -- in front of frame reset_at[i],
+ * or behind the last frame when reset_at[i] == nframes[i] (a record that announces no frame). */
+int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits,
+                               const int *nbits, const int *nframes, const int *lcs, const int *reset_at, nrsc5hip_aas_cb cb, void *opaque);
 
 /* ---- stage-level entry points (host buffers): parity tests of single kernels against the oracle ---- */
 int nrsc5hip_stage_halfband_fm_cu8(nrsc5hip_engine *e, const uint8_t *iq, uint32_t nbytes, int16_t *out /* [nbytes/4][2] */);

@@ -320,31 +320,39 @@ extern "C" int nrsc5hip_am_frame_bits(nrsc5hip_engine *e, int stream, int slot, 
 
 // ---- L2 audio transport index ---------------------------------------------------------------------------------------
 
+// the device half: the job list goes up and the index kernel is queued on the chain stream; frames [n] and bytes [n][stride] (may be null) are DEVICE
+// buffers and stay there -- nothing is waited for, nothing comes back (nrsc5hip_psd_feed reads them with its own kernel)
+int nrsc5::l2_launch(nrsc5hip_engine *e, const std::vector<L2Job> &jobs, L2Job *djobs, nrsc5hip_l2_frame *dframes, uint8_t *dbytes, long long stride)
+{
+    const int n = (int)jobs.size();
+    if (dbytes && stride < L2_MAX_BYTES) {
+        for (const L2Job &j : jobs) if ((j.nbits - 22) / 8 > stride) FAIL(NRSC5HIP_EINVAL, "stride %lld too small for a %d-bit frame", stride, j.nbits);
+    }
+    HIPCHK(hipMemcpy(djobs, jobs.data(), sizeof(L2Job) * n, hipMemcpyHostToDevice));
+    launch_l2_index(djobs, n, dframes, dbytes, stride, e->main);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int nrsc5::l2_run(nrsc5hip_engine *e, const std::vector<L2Job> &jobs, nrsc5hip_l2_frame *out, uint8_t *pdu_bytes, long long stride)
 {
     const int n = (int)jobs.size();
-    if (pdu_bytes && stride < L2_MAX_BYTES) {
-        for (const L2Job &j : jobs) if ((j.nbits - 22) / 8 > stride) FAIL(NRSC5HIP_EINVAL, "stride %lld too small for a %d-bit frame", stride, j.nbits);
-    }
     DevTmp tj, to, tb;                                  // freed on every return path
     HIPCHK(hipMalloc(&tj.p, sizeof(L2Job) * n));
     HIPCHK(hipMalloc(&to.p, sizeof(nrsc5hip_l2_frame) * n));
     if (pdu_bytes) HIPCHK(hipMalloc(&tb.p, (size_t)stride * n));
-    L2Job *djobs = (L2Job *)tj.p; nrsc5hip_l2_frame *dout = (nrsc5hip_l2_frame *)to.p; uint8_t *dbytes = (uint8_t *)tb.p;
-    HIPCHK(hipMemcpy(djobs, jobs.data(), sizeof(L2Job) * n, hipMemcpyHostToDevice));
-    launch_l2_index(djobs, n, dout, dbytes, stride, e->main);
-    HIPCHK(hipGetLastError());
+    nrsc5hip_l2_frame *dout = (nrsc5hip_l2_frame *)to.p; uint8_t *dbytes = (uint8_t *)tb.p;
+    int rc = l2_launch(e, jobs, (L2Job *)tj.p, dout, dbytes, stride); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(e->main));
     HIPCHK(hipMemcpy(out, dout, sizeof(nrsc5hip_l2_frame) * n, hipMemcpyDeviceToHost));
     if (pdu_bytes) HIPCHK(hipMemcpy(pdu_bytes, dbytes, (size_t)stride * n, hipMemcpyDeviceToHost));
     return 0;
 }
 
-extern "C" int nrsc5hip_l2_index(nrsc5hip_engine *e, int njobs, const nrsc5hip_l2_job *jobs, nrsc5hip_l2_frame *out, uint8_t *pdu_bytes, long long stride)
+// every slot / channel / length the jobs name, checked against the engine's rings; -> the frames' words in device memory
+int nrsc5::l2_resolve(nrsc5hip_engine *e, int njobs, const nrsc5hip_l2_job *jobs, std::vector<L2Job> &dj)
 {
-    ON_ENGINE_DEVICE(e);
-    if (!e || !jobs || !out || njobs < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
-    std::vector<L2Job> dj((size_t)njobs);
+    dj.resize((size_t)njobs);
     for (int k = 0; k < njobs; k++) {
         const nrsc5hip_l2_job &j = jobs[k];
         int rc = check_stream(e, j.stream); if (rc) return rc;
@@ -363,6 +371,15 @@ extern "C" int nrsc5hip_l2_index(nrsc5hip_engine *e, int njobs, const nrsc5hip_l
         } else FAIL(NRSC5HIP_EINVAL, "job %d: unknown kind %d", k, j.kind);
         dj[k] = L2Job{words, j.nbits, 0};
     }
+    return 0;
+}
+
+extern "C" int nrsc5hip_l2_index(nrsc5hip_engine *e, int njobs, const nrsc5hip_l2_job *jobs, nrsc5hip_l2_frame *out, uint8_t *pdu_bytes, long long stride)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!e || !jobs || !out || njobs < 1) FAIL(NRSC5HIP_EINVAL, "bad argument");
+    std::vector<L2Job> dj;
+    int rc = l2_resolve(e, njobs, jobs, dj); if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());                 // the frames may still be in flight on a decode stream
     return l2_run(e, dj, out, pdu_bytes, stride);
 }

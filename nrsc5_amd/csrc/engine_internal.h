@@ -20,6 +20,8 @@ int leave_mirror(nrsc5hip_engine *e, int n, const int *ids);   // engine_batch.h
 int upload_ids(nrsc5hip_engine *e, int n, const int *ids, const uint32_t *counts, const int **ids_dev);
 int patch_am_ber(nrsc5hip_engine *e, int stream, nrsc5hip_record *recs, int n, const float *ber_row);
 int l2_run(nrsc5hip_engine *e, const std::vector<L2Job> &jobs, nrsc5hip_l2_frame *out, uint8_t *pdu_bytes, long long stride);
+int l2_launch(nrsc5hip_engine *e, const std::vector<L2Job> &jobs, L2Job *djobs, nrsc5hip_l2_frame *dframes, uint8_t *dbytes, long long stride);   // device half of l2_run
+int l2_resolve(nrsc5hip_engine *e, int njobs, const nrsc5hip_l2_job *jobs, std::vector<L2Job> &dj);
 int run_steps(nrsc5hip_engine *e, int n, const int *ids_dev, unsigned long long set_sig, int max_steps, int check_every, int *steps_done);   // engine_steps.hip
 int run_steps_am(nrsc5hip_engine *e, int n, const int *ids_dev, int max_steps, int check_every, int *steps_done);
 void prof_collect(nrsc5hip_engine *e);                         // engine.hip

@@ -17,6 +17,7 @@
 #include <new>
 #include <vector>
 #include "nrsc5hip.h"
+#include "record_jobs.h"
 
 namespace {
 
@@ -224,32 +225,10 @@ extern "C" int nrsc5hip_hdc_advance(nrsc5hip_hdc *h, int stream, int mode, nrsc5
 
 int nrsc5_engine_max_streams(const nrsc5hip_engine *e);         // engine.hip
 
+using nrsc5::record_jobs;                                       // record_jobs.h: the logical frames one record announces
 namespace {
-
-constexpr uint32_t REC_PROCESSED = NRSC5HIP_REC_PROCESSED, REC_TO_FINE = NRSC5HIP_REC_TO_FINE, REC_P1 = NRSC5HIP_REC_P1, REC_P3 = NRSC5HIP_REC_P3,
-                   REC_P4 = NRSC5HIP_REC_P4;
-
-// the logical frames one record announces, in frame_push's order (decode.c:393-437, 507-554); -> how many; job / lc may be null (count only)
-int record_jobs(const nrsc5hip_record &r, int stream, int mode, nrsc5hip_l2_job *job, int *lc)
-{
-    int n = 0;
-    auto add = [&](int slot, int kind, int which, int nbits, int channel) {
-        if (job) { job[n] = nrsc5hip_l2_job{stream, slot, kind, which, nbits}; lc[n] = channel; }
-        n++;
-    };
-    if (mode == NRSC5HIP_MODE_AM) {
-        if (r.flags & REC_P1) add(r.p1_slot, NRSC5HIP_L2_AM, r.bc_decoded, 3750, 0);
-        if (r.flags & REC_P3) add(r.p1_slot, NRSC5HIP_L2_AM, 8, r.psmi == 2 ? 30000 : 24000, 1);
-    } else {
-        const int px_bits = r.psmi == 2 ? 2304 : 4608;
-        if (r.flags & REC_P1) add(r.p1_slot, NRSC5HIP_L2_FM_P1, 0, 146176, 0);
-        if (r.flags & REC_P3) add((int)r.sis, NRSC5HIP_L2_FM_PX, 0, px_bits, 1);
-        if (r.flags & REC_P4) add((int)r.sis, NRSC5HIP_L2_FM_PX, 1, px_bits, 2);
-    }
-    return n;
+constexpr uint32_t REC_PROCESSED = NRSC5HIP_REC_PROCESSED, REC_TO_FINE = NRSC5HIP_REC_TO_FINE;
 }
-
-}  // namespace
 
 // A loss of sync needs nothing here: input_set_sync_state (input.c:172-188) only reports it.  The reference keeps its elastic buffers and
 // audio offsets (output_reset runs on nrsc5_set_mode and at start-up only, nrsc5.c:549, output.c:240-245) and output_advance goes on with

@@ -176,6 +176,26 @@ void launch_l2_index_px_window(const DevBuffers &db, int nstreams, const int *st
 void launch_l2_index_am_window(const DevBuffers &db, int nstreams, const int *stream_ids, int parity, hipStream_t st);
 void launch_l2_index_am_step(const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st);
 
+// ---- PSD transport (k_psd.hip): HDLC de-framing of the PSD spans the L2 index marks, one wave64 workgroup per stream ------------
+constexpr int PSD_MAX_AAS = 8212;                                   // MAX_AAS_LEN, frame.h:5: raw bytes of one open HDLC frame
+constexpr int PSD_PROGRAMS = 8;
+constexpr int PSD_STATS = 9;                                        // device counters per stream: nrsc5hip_psd_stats [0..8]
+struct PsdJob { int frame; int keep; int reset; int pad; };         // frame: index into frames / bytes (-1: none); keep: PDUs walked at most; reset: close all
+                                                                    // eight programs of the stream before this job (frame_reset)
+struct PsdStream { int target; int first; int count; int pos; };    // consumer stream, its jobs [first, first + count), position in the caller's list
+struct PsdArenaHdr { unsigned used, npackets, overflow, pad; };
+// a packet in the arena: PsdPacket, then `len` data bytes (what follows port and seq), padded to a multiple of 4
+struct PsdPacket { uint32_t pos; uint16_t port, seq, len; uint8_t program, pad; };
+struct PsdArgs {
+    const PsdStream *streams; const PsdJob *jobs; int njobs;
+    const nrsc5hip_l2_frame *frames; const uint8_t *bytes; long long stride; int nframes;
+    uint8_t *bufs;                   // [consumer streams][8][PSD_MAX_AAS]  frame_t.psd_buf
+    int *idx;                        // [consumer streams][8]               frame_t.psd_idx, -1 = closed
+    unsigned long long *stats;       // [consumer streams][PSD_STATS]
+    PsdArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
+};
+void launch_psd(const PsdArgs &a, int nstreams, hipStream_t st);
+
 // ---- stage-level entry points (parity tests) ---------------------------------------------------
 // scratch of the stage-level K=7 decode (end lanes, chunk maps, packed soft words, segment metadata): owned by the engine that calls it
 struct VitScratch { int *endlane = nullptr; int cap = 0; uint8_t *gmap = nullptr; size_t gcap = 0; int *soft = nullptr; size_t scap = 0; int *meta = nullptr; int mcap = 0; };

@@ -117,6 +117,8 @@ def l2_frame_to_dict(fr: L2Frame) -> dict:
 
 
 HDC_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint, ctypes.c_uint)
+AAS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)   # nrsc5hip_aas_cb
+PSD_STATS = ("pdus", "span_bytes", "closed", "empty", "bad_fcs", "wrong_protocol", "truncated_escape", "overflows", "delivered", "d2h_bytes")   # nrsc5hip_psd_stats
 
 
 class Nrsc5HipError(RuntimeError):
@@ -216,6 +218,14 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_hdc_host_bytes.argtypes = [vp]
     lib.nrsc5hip_hdc_host_bytes.restype = ctypes.c_size_t
     lib.nrsc5hip_hdc_feed.argtypes = [vp, vp, ci, vp, vp, vp, vp, ci, HDC_CB, vp]
+    lib.nrsc5hip_psd_create.argtypes = [vp, ci, ctypes.POINTER(vp)]
+    lib.nrsc5hip_psd_destroy.argtypes = [vp]
+    lib.nrsc5hip_psd_destroy.restype = None
+    lib.nrsc5hip_psd_reset.argtypes = [vp, ci]
+    lib.nrsc5hip_psd_feed.argtypes = [vp, vp, ci, vp, vp, vp, vp, ci, AAS_CB, vp]
+    lib.nrsc5hip_psd_stats.argtypes = [vp, ci, vp]
+    lib.nrsc5hip_stage_psd.argtypes = [vp, vp, ci, vp, ci, ci, ci, AAS_CB, vp]
+    lib.nrsc5hip_stage_psd_streams.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, AAS_CB, vp]
     ll = ctypes.c_longlong
     lib.nrsc5hip_chan_create.argtypes = [ctypes.POINTER(_ChanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_chan_destroy.argtypes = [vp]
@@ -253,6 +263,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_hdc_create", "nrsc5hip_hdc_destroy", "nrsc5hip_hdc_reset", "nrsc5hip_hdc_push_frame", "nrsc5hip_hdc_advance",
     "nrsc5hip_hdc_adts", "nrsc5hip_hdc_host_bytes", "nrsc5hip_hdc_fixed_audio_end", "nrsc5hip_l2_apply_audio_end", "nrsc5hip_hdc_frame_reset",
     "nrsc5hip_hdc_feed",
+    "nrsc5hip_psd_create", "nrsc5hip_psd_destroy", "nrsc5hip_psd_reset", "nrsc5hip_psd_feed", "nrsc5hip_psd_stats", "nrsc5hip_stage_psd", "nrsc5hip_stage_psd_streams",
     "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
     "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed",
     "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",
@@ -1029,6 +1040,97 @@ def feed_hdc_batch(engine: Engine, consumer: HdcConsumer, stream_ids, recs_per_s
         err.code = rc
         raise err
     return rc
+
+
+class PsdConsumer:
+    """PSD transport on the device (nrsc5hip_psd_*): HDLC de-framing of the PSD spans of `nstreams` streams in HBM; only finished AAS
+    packets reach the host.  They land in `packets` as (stream, program, port, seq, data), data = what follows port and seq."""
+
+    def __init__(self, engine: "Engine", nstreams: int):
+        self.lib = engine.lib
+        self._engine = engine                                    # the consumer's device buffers live on the engine's device: keep it alive
+        self._h = ctypes.c_void_p()
+        rc = self.lib.nrsc5hip_psd_create(engine._h, nstreams, ctypes.byref(self._h))
+        if rc != 0:
+            raise Nrsc5HipError(f"nrsc5hip_psd_create failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
+        self.nstreams = nstreams
+        self.packets = []
+        self._cb = AAS_CB(self._on_packet)
+
+    def _on_packet(self, opaque, stream, program, port, seq, data, n):
+        self.packets.append((int(stream), int(program), int(port), int(seq), bytes(ctypes.string_at(data, n)) if n else b""))
+
+    def _result(self, rc: int, what: str) -> int:
+        if rc < 0:
+            err = Nrsc5HipError(f"{what} failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
+            err.code = rc
+            raise err
+        return rc
+
+    def reset(self, stream: int):
+        self._result(self.lib.nrsc5hip_psd_reset(self._h, stream), "nrsc5hip_psd_reset")
+
+    def stats(self, stream: int) -> dict:
+        v = (ctypes.c_longlong * 10)()
+        self._result(self.lib.nrsc5hip_psd_stats(self._h, stream, v), "nrsc5hip_psd_stats")
+        return dict(zip(PSD_STATS, (int(x) for x in v)))
+
+    def stage(self, stream: int, frames_bits: np.ndarray, lc: int = 0) -> int:
+        """nrsc5hip_stage_psd: frames as frame_push takes them ([nframes, nbits], one bit per byte), in order; -> packets delivered"""
+        b = np.ascontiguousarray(frames_bits, dtype=np.uint8)
+        if b.ndim == 1:
+            b = b[None, :]
+        return self._result(self.lib.nrsc5hip_stage_psd(self._h, self._engine._h, stream, b.ctypes.data, b.shape[1], b.shape[0], lc, self._cb, None),
+                            "nrsc5hip_stage_psd")
+
+    def stage_streams(self, targets, frames_per_stream, lcs, reset_at=None) -> list:
+        """nrsc5hip_stage_psd_streams: frames_per_stream[i] ([nframes, nbits] bits) go to consumer stream targets[i], all in one call (one k_psd
+        workgroup per stream); reset_at[i]: the frame in front of which the stream gets a REC_TO_FINE reset (None / negative: none).
+        -> the packets of this call, all of targets[0] first"""
+        n = len(targets)
+        arrs = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_per_stream]
+        arrs = [a[None, :] if a.ndim == 1 else a for a in arrs]
+        i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+        tg, nb, nf, lc = i32(targets), i32([a.shape[1] for a in arrs]), i32([a.shape[0] for a in arrs]), i32(lcs)
+        rs = None if reset_at is None else i32([-1 if r is None else r for r in reset_at])
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        first = len(self.packets)
+        rc = self._result(self.lib.nrsc5hip_stage_psd_streams(self._h, self._engine._h, n, tg.ctypes.data, ptrs, nb.ctypes.data, nf.ctypes.data, lc.ctypes.data,
+                                                              None if rs is None else rs.ctypes.data, self._cb, None), "nrsc5hip_stage_psd_streams")
+        out = self.packets[first:]
+        assert rc == len(out)
+        return out
+
+    def close(self):
+        if self._h:
+            self.lib.nrsc5hip_psd_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def feed_psd_batch(engine: Engine, consumer: PsdConsumer, stream_ids, recs_per_stream, targets=None, mode: int = MODE_FM) -> list:
+    """nrsc5hip_psd_feed: the records of many streams (as for feed_hdc_batch) replayed into the PSD consumer in one native call -- one
+    index launch, one k_psd launch, one copy of the finished packets.  -> [(stream, program, port, seq, data)] of this call, all of
+    stream_ids[0] first (they are appended to consumer.packets as well).  Call it while the ring slots the records name hold their frames."""
+    ids = np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
+    tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    n = int(ids.size)
+    if len(recs_per_stream) != n or (tg is not None and tg.size != n):
+        raise ValueError("stream_ids, recs_per_stream and targets must have one entry per stream")
+    arrs = [None if r is None else np.ascontiguousarray(r, dtype=RECORD_DTYPE) for r in recs_per_stream]       # kept alive over the call
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None or a.size == 0 else a.ctypes.data for a in arrs])
+    counts = np.array([0 if a is None else a.size for a in arrs], dtype=np.int32)
+    first = len(consumer.packets)
+    rc = consumer._result(consumer.lib.nrsc5hip_psd_feed(consumer._h, engine._h, n, ids.ctypes.data, None if tg is None else tg.ctypes.data, ptrs,
+                                                         counts.ctypes.data, mode, consumer._cb, None), "nrsc5hip_psd_feed")
+    out = consumer.packets[first:]
+    assert rc == len(out)
+    return out
 
 
 def l2_jobs_from_records(stream: int, recs: np.ndarray, mode: int = 0):

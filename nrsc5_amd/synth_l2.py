@@ -254,6 +254,42 @@ def hdlc_frame(payload: bytes) -> bytes:
     return bytes(out)
 
 
+# ---- AAS packets for a program's PSD stream: ID3v2.3 tags as output_id3 reads them (output.c:277-322), the AAS header, HDLC framing ----
+def id3_frame(fid: str, text: str, utf16: bool = False) -> bytes:
+    body = (b"\x01" + text.encode("utf-16")) if utf16 else (b"\x00" + text.encode("latin-1"))
+    return fid.encode() + len(body).to_bytes(4, "big") + b"\x00\x00" + body
+
+
+def id3_tag(title=None, artist=None, album=None, genre=None, utf16: bool = False) -> bytes:
+    body = b"".join(id3_frame(f, t, utf16) for f, t in (("TIT2", title), ("TPE1", artist), ("TALB", album), ("TCON", genre)) if t is not None)
+    n = len(body)
+    return b"ID3\x03\x00\x00" + bytes([(n >> 21) & 0x7f, (n >> 14) & 0x7f, (n >> 7) & 0x7f, n & 0x7f]) + body
+
+
+def aas_payload(port: int, seq: int, data: bytes, protocol: int = 0x21) -> bytes:
+    return bytes([protocol, port & 0xff, port >> 8, seq & 0xff, seq >> 8]) + data
+
+
+def hdlc(payload: bytes, or_escape: bool = False, bad_fcs: bool = False, trailing_escape: bool = False) -> bytes:
+    """0x7E, escaped payload + FCS, 0x7E.  or_escape: 0x7D travels as 7D 7D (valid under the reference's OR rule, frame.c:335), so that
+    runs of 0x7D longer than two appear; trailing_escape: an unpaired 0x7D in front of the closing flag."""
+    body = bytearray(payload + (fcs16(payload) ^ 0xFFFF).to_bytes(2, "little"))
+    if bad_fcs:
+        body[len(body) // 2] ^= 0x01 if body[len(body) // 2] not in (0x7C, 0x7F) else 0x10
+    out = bytearray([0x7E])
+    for b in body:
+        if b == 0x7E:
+            out += b"\x7d\x5e"
+        elif b == 0x7D:
+            out += b"\x7d\x7d" if or_escape else b"\x7d\x5d"
+        else:
+            out.append(b)
+    if trailing_escape:
+        out.append(0x7D)
+    out.append(0x7E)
+    return bytes(out)
+
+
 def psd_sequence(seed: int = 0, nbits: int = 146176, n_frames: int = 6):
     """Frames whose PDUs carry a PSD byte stream for two programs: AAS packets (protocol 0x21, good and bad FCS, escaped
     bytes) cut at arbitrary places so that HDLC frames span PDUs and logical frames, plus changing service parameters."""

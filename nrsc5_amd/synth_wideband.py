@@ -25,6 +25,7 @@ class Station:
     level: float = 1.0                   # rms amplitude relative to the other stations
     timing: int = 0                      # leading samples at 1 488 375 S/s before the transmission starts
     chan: object = None                  # channel.Impairments or None
+    psd: bytes | None = None             # program 0's PSD byte stream (synth_torch.payload_stream), None: flag bytes only
 
 
 @dataclass
@@ -80,7 +81,7 @@ def capture(stations, rate, fmt: str = "cs16", n_frames: int = 3, noise_rms: flo
     cap = WidebandCapture(None, rate, fmt, list(stations))
     fs_in = float(rate)
     for st in stations:
-        p1, pids, m = synth_torch.payload_stream(n_frames, seed=st.seed)
+        p1, pids, m = synth_torch.payload_stream(n_frames, seed=st.seed, psd_stream=st.psd)
         sig = synth_torch.modulate(m, dev)
         if st.chan is not None:
             from . import channel

@@ -4,7 +4,9 @@ and the batch engine decodes them (p1_async, l2_feedback).
     python -m nrsc5_amd.wideband FILE --format cs16 --rate 20000000 --offsets -800e3,0,400e3
     rtl_sdr -f 98.1e6 -s 2400000 - | python -m nrsc5_amd.wideband - --format cu8 --rate 2400000 --offsets -800e3,0,600e3
 
-prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  --dump-hdc DIR also records every station's
+prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  --metadata adds what every program is playing
+(one ID3 line per tag: title, artist, album, genre), de-framed on the device (nrsc5hip_psd_feed): no frame is copied to the host for it.
+--dump-hdc DIR also records every station's
 audio programs (the reference's NRSC5_EVENT_HDC packets, as `nrsc5 --dump-hdc` frames them: ADTS) into
 DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.  FILE may be `-` (standard input, read in
 --chunk pieces until it ends; --offsets is then required): the session may be of any length, the receiver gives FIFO space back as it
@@ -38,10 +40,15 @@ class WidebandReceiver:
     largest span a trim has left in a station's FIFO so far; trims: how many pushes had to trim.
     programs=True: the receiver also delivers every station's audio programs -- the reference's NRSC5_EVENT_HDC packets, in its order --
     through an HdcConsumer of its own: after the drains of a push, one eng.feed_hdc_batch call (nrsc5hip_hdc_feed) over all stations'
-    new records; packets[s] collects (program, flags, bytes) and on_packet(station, program, flags, data), if given, sees each one."""
+    new records; packets[s] collects (program, flags, bytes) and on_packet(station, program, flags, data), if given, sees each one.
+    metadata=True: the receiver also reassembles every station's program service data on the device (PsdConsumer: one eng.feed_psd_batch
+    call per push over all stations' new records; only finished AAS packets reach the host).  Packets on the PSD ports (0x5100,
+    0x5201..0x5207) that hold an ID3v2.3 tag become ("id3", {"program", "title", "artist", "album", "genre"}) events behind that station's
+    record events of the push, and now_playing[s][program] keeps the last tag; every other packet is kept raw in aas[s] as (program, port,
+    seq, data); on_aas(station, program, port, seq, data), if given, sees every packet, tags included.  With programs=True as well the frames are indexed twice per push, once by each consumer."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
-                 programs: bool = False, on_packet=None):
+                 programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -64,6 +71,28 @@ class WidebandReceiver:
         self.on_packet = on_packet
         self.packets = [[] for _ in range(self.k)]
         self.hdc = eng.HdcConsumer(self.k, lib=self.engine.lib) if self.programs else None
+        self.metadata = bool(metadata)
+        self.on_aas = on_aas
+        self.psd = eng.PsdConsumer(self.engine, self.k) if self.metadata else None
+        self.now_playing = [{} for _ in range(self.k)]
+        self.aas = [[] for _ in range(self.k)]
+
+    def _feed_metadata(self, fresh, events):
+        """fresh[s]: as for _feed_programs; events[s]: the station's events of this push, which the id3 events go behind"""
+        if not any(len(r) for r in fresh):
+            return
+        for s, program, port, seq, data in eng.feed_psd_batch(self.engine, self.psd, self.ids, fresh):
+            if self.on_aas is not None:
+                self.on_aas(s, program, port, seq, data)
+            tag = parse_id3(data) if is_psd_port(port) else None
+            if tag is None:
+                self.aas[s].append((program, port, seq, data))
+                continue
+            v = {"program": port & 7, **tag}                        # output.c:881: the port names the program
+            self.now_playing[s][port & 7] = tag
+            self.logs[s].append(("id3", v))
+            events[s].append((s, "id3", v))
+        self.psd.packets.clear()
 
     def _feed_programs(self, fresh):
         """fresh[s]: the records station s delivered in this push; their frames are still in the rings (nothing was processed since)"""
@@ -95,7 +124,7 @@ class WidebandReceiver:
         self.held += m
         self.pushes += 1
         self.engine.batch_process(self.k, stream_ids=self.ids)
-        new = []
+        new = [[] for _ in range(self.k)]
         fresh = [None] * self.k
         for s in range(self.k):
             recs = self.engine.drain(s)
@@ -104,10 +133,12 @@ class WidebandReceiver:
                 log = eng.records_to_log(self.engine, s, recs)          # frames are fetched now, while their ring slots hold them
                 self.logs[s] += log
                 self.records[s].append(recs)
-                new += [(s, kind, v) for kind, v in log]
+                new[s] += [(s, kind, v) for kind, v in log]
         if self.programs:
             self._feed_programs(fresh)
-        return new
+        if self.metadata:
+            self._feed_metadata(fresh, new)
+        return [ev for per in new for ev in per]
 
     def station_records(self, s: int) -> np.ndarray:
         return np.concatenate(self.records[s]) if self.records[s] else np.zeros(0, dtype=eng.RECORD_DTYPE)
@@ -115,8 +146,48 @@ class WidebandReceiver:
     def close(self):
         if self.hdc is not None:
             self.hdc.close()
+        if self.psd is not None:
+            self.psd.close()
         self.engine.close()
         self.chan.close()
+
+
+def is_psd_port(port: int) -> bool:
+    """the AAS ports that carry a program's ID3 tags (output.c:878)"""
+    return port == 0x5100 or 0x5201 <= port <= 0x5207
+
+
+_ID3_TEXT = {b"TIT2": "title", b"TPE1": "artist", b"TALB": "album", b"TCON": "genre"}
+
+
+def parse_id3(data: bytes) -> dict | None:
+    """The text frames TIT2 / TPE1 / TALB / TCON of an ID3v2.3 tag as output_id3 reads them (output.c:277-322): None unless the tag starts
+    "ID3" 3 0, flags 0, and its (sync-safe) length fits the data; the walk stops at a frame that runs over the tag.  Encoding 0 is Latin-1,
+    1 is UTF-16 with a byte-order mark, anything else gives ""; a text ends at its first NUL.  -> {"title", "artist", "album", "genre"},
+    each only if the tag holds it."""
+    data = bytes(data)
+    if len(data) < 10 or data[:5] != b"ID3\x03\x00" or data[5]:
+        return None
+    end = (((data[6] & 0x7f) << 21) | ((data[7] & 0x7f) << 14) | ((data[8] & 0x7f) << 7) | (data[9] & 0x7f)) + 10
+    if end > len(data):
+        return None
+    out, off = {}, 10
+    while off + 10 <= end:
+        n = int.from_bytes(data[off + 4:off + 8], "big")
+        if off + 10 + n > end:
+            break
+        key = _ID3_TEXT.get(data[off:off + 4])
+        if key is not None:
+            body = data[off + 10:off + 10 + n]
+            if n == 0 or body[0] > 1:
+                text = ""
+            elif body[0] == 0:
+                text = body[1:].decode("latin-1")
+            else:
+                text = body[1:len(body) - (len(body) - 1) % 2].decode("utf-16", errors="replace")
+            out[key] = text.split("\0", 1)[0]
+        off += 10 + n
+    return out
 
 
 CONFIRM_SECONDS = 1.0       # twice the largest first-PIDS time measured on the synthetic scenes, and not below 1 s (DESIGN.md (j))
@@ -234,6 +305,8 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} BER {v['cber']:.6f}"
     if kind == "lost_sync":
         return f"{head} LOST_SYNC"
+    if kind == "id3":
+        return f"{head} ID3 program {v['program']}" + "".join(f" {k}={v[k]!r}" for k in ("title", "artist", "album", "genre") if k in v)
     return None
 
 
@@ -292,6 +365,7 @@ def main(argv=None) -> int:
                     help="decimated samples of FIFO per station: at least %d + the outputs of one push, whatever the length of the session" % eng.TRIM_RETAIN_MAX)
     ap.add_argument("--dump-hdc", metavar="DIR", default=None,
                     help="write every station's audio programs as ADTS: DIR/station<k>_<offset in Hz>_p<program>.aac")
+    ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                  # "--offsets -800e3,0,400e3": a value that starts with '-' is still the value
         if argv[i] == "--offsets":
@@ -324,7 +398,7 @@ def main(argv=None) -> int:
                     print("no station found", file=sys.stderr)
                     return 1
         del head
-    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None)
+    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata)
     dump = None
     if a.dump_hdc is not None:
         dump = HdcDump(a.dump_hdc, offsets, rx.hdc.adts)
