@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 12   /* 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 13   /* 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -544,6 +544,31 @@ int nrsc5hip_stage_am_deinterleave(nrsc5hip_engine *e, int psmi, int nframes, co
 enum { NRSC5HIP_CODE_E1 = 1, NRSC5HIP_CODE_E2 = 2 };
 int nrsc5hip_stage_am_epilogue(nrsc5hip_engine *e, const int8_t *soft, const uint8_t *bits, int len, int code, int threads, int *errors,
                                uint8_t *bits_out, uint32_t *words_out);
+/* ---- coarse acquisition on caller data (ABI 13; tests/acq_checks.py) ------------------------------------------------------------------
+ * Each hook runs the PRODUCTION launch -- launch_acquire (k_acq_list, k_acq_decimate, k_acq_fir, k_acq_corr, k_acq_peak) on streams 0 .. n-1 of the
+ * engine, or launch_am_step (k_am_block, whose first section is the AM acquisition) on stream 0 -- once, on freshly reset streams into which it
+ * wrote the caller's window, the acquisition filter's 31-sample history and the sync state, and returns what the kernels left, raw.  Everything
+ * they may write is filled with 0xA5 bytes first (int16 -23131, the float with the bits 0xA5A5A5A5, samperr 0xA5A5A5A5): a stream the
+ * acquisition must skip -- one that is FINE, or short of a window -- still shows the fill, and its history is what went in.  The streams are left
+ * freshly reset.  state: 0 NONE, 1 COARSE, 2 FINE.  All arrays are HOST arrays, [n] leading; c16 samples as int16 [.][2].
+ * NRSC5HIP_EINVAL with nothing launched: a null pointer; n < 1 or n > max_streams; q15_capacity below a window; a state outside the three; a
+ * stream in the other mode; a fill outside 0 .. window; (am_acquire) an engine without am_enable; (acquire_raw) an engine without
+ * batch_zero_copy, nbytes % 4 != 0, rd < 0 or 4 * (rd + 71280) > nbytes.
+ * acquire: the FIFO seam.  win [n][71280][2] goes to the start of each stream's FIFO slab, fill[n] (<= 71280) is its write position: below 71280
+ *   the stream has no complete window.  -> filt [n][71280][2] (acq_filt), sums float [n][2160][2] (acq_sums), samperr [n], peak float [n][2]
+ *   (coarse_samperr, coarse_re / coarse_im), hist_out [n][31][2] (fir_hist afterwards). */
+int nrsc5hip_stage_acquire(nrsc5hip_engine *e, int n, const int16_t *win, const int16_t *hist, const int *state, const int *fill,
+                           int16_t *filt, float *sums, int *samperr, float *peak, int16_t *hist_out);
+/* acquire_raw: the zero-copy seam (engine with batch_zero_copy).  iq [n][nbytes]: cu8 captures, uploaded and attached the way
+ *   nrsc5hip_batch_append_cu8 attaches them (stride nbytes); rd[n]: the read position, in decimated samples, the window starts at -- k_acq_decimate
+ *   produces it.  Additionally -> acq_win [n][71280][2], the decimated window. */
+int nrsc5hip_stage_acquire_raw(nrsc5hip_engine *e, int n, const uint8_t *iq, long long nbytes, const long long *rd, const int16_t *hist, const int *state,
+                               int16_t *acq_win, int16_t *filt, float *sums, int *samperr, float *peak, int16_t *hist_out);
+/* am_acquire: stream 0 of an am_enable engine, in AM mode.  win [8910][2], hist [31][2], fill <= 8910.  One whole block step: k_am_block<256> on an
+ *   engine without p1_async, k_am_block<512> (window pipeline: parity 0, slot 0, window 0) on one with it.  The filtered window and the sums live in
+ *   LDS and stay unobserved; nothing behind the acquisition section writes coarse_samperr / coarse_re / coarse_im / fir_hist, so they are read from the
+ *   stream state after the step: -> *samperr, peak [2], hist_out [31][2]. */
+int nrsc5hip_stage_am_acquire(nrsc5hip_engine *e, const int16_t *win, const int16_t *hist, int state, int fill, int *samperr, float *peak, int16_t *hist_out);
 /* one frame, also returning the len+64 survivor-decision words of the forward pass */
 int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out);
 /* micro-benchmark of the Viterbi kernel on random frames: phases bit0 = forward, bit1 = traceback */

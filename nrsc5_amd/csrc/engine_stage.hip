@@ -450,6 +450,123 @@ extern "C" int nrsc5hip_stage_am_epilogue(nrsc5hip_engine *e, const int8_t *soft
     return 0;
 }
 
+// ---- coarse acquisition on caller data (include/nrsc5hip.h; tests/acq_checks.py) --------------------------------------------------------------
+// launch_acquire / launch_am_step unchanged on freshly reset streams whose FIFO window (or attached capture), FIR history and sync state the hook
+// wrote; everything the kernels leave is filled with ACQ_FILL bytes first, so a buffer a stream must not touch shows it.  Nothing of the arithmetic lives here.
+constexpr int ACQ_FILL = 0xA5;
+
+static int acq_check_common(nrsc5hip_engine *e, int n, const int *state, int mode, long long window)
+{
+    if (n < 1 || n > e->cfg.max_streams) FAIL(NRSC5HIP_EINVAL, "%d streams: 1 .. max_streams (%d)", n, e->cfg.max_streams);
+    if (e->db.q15_cap < window) FAIL(NRSC5HIP_EINVAL, "q15_capacity %lld is smaller than a window (%lld)", e->db.q15_cap, window);
+    for (int s = 0; s < n; s++) {
+        if (state[s] != SYNC_NONE && state[s] != SYNC_COARSE && state[s] != SYNC_FINE) FAIL(NRSC5HIP_EINVAL, "stream %d: sync state %d: 0 (NONE), 1 (COARSE) or 2 (FINE)", s, state[s]);
+        if (e->mode_host[s] != mode) FAIL(NRSC5HIP_EINVAL, "stream %d must be in %s mode", s, mode == MODE_AM ? "AM" : "FM");
+    }
+    return 0;
+}
+
+// history, sync state and the fill pattern over the three coarse_* words of stream s
+static int acq_poke(nrsc5hip_engine *e, int s, const int16_t *hist, int state)
+{
+    char *st = (char *)(e->db.state + s);
+    static_assert(offsetof(StreamState, coarse_im) - offsetof(StreamState, coarse_samperr) == 8, "coarse_samperr, coarse_re, coarse_im are three adjacent words");
+    HIPCHK(hipMemcpy(st + offsetof(StreamState, fir_hist), hist, 31 * sizeof(c16), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(st + offsetof(StreamState, sync_state), &state, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(st + offsetof(StreamState, coarse_samperr), ACQ_FILL, 12));
+    return 0;
+}
+
+static int acq_peek(nrsc5hip_engine *e, int s, int *samperr, float *peak, int16_t *hist_out)
+{
+    const char *st = (const char *)(e->db.state + s);
+    HIPCHK(hipMemcpy(samperr, st + offsetof(StreamState, coarse_samperr), sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(peak, st + offsetof(StreamState, coarse_re), 2 * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hist_out, st + offsetof(StreamState, fir_hist), 31 * sizeof(c16), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the FM launch and what it left, for streams 0 .. n-1 (acq_win: the zero-copy seam's decimated windows, or null)
+static int acq_run_fm(nrsc5hip_engine *e, int n, int16_t *acq_win, int16_t *filt, float *sums, int *samperr, float *peak, int16_t *hist_out)
+{
+    HIPCHK(hipMemset(e->db.acq_filt, ACQ_FILL, (size_t)n * WIN_N * sizeof(c16)));
+    HIPCHK(hipMemset(e->db.acq_sums, ACQ_FILL, (size_t)n * SYM_N * sizeof(float2)));
+    if (acq_win) HIPCHK(hipMemset(e->db.acq_win, ACQ_FILL, (size_t)n * WIN_N * sizeof(c16)));
+    launch_acquire(e->tb, e->db, n, nullptr, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(filt, e->db.acq_filt, (size_t)n * WIN_N * sizeof(c16), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sums, e->db.acq_sums, (size_t)n * SYM_N * sizeof(float2), hipMemcpyDeviceToHost));
+    if (acq_win) HIPCHK(hipMemcpy(acq_win, e->db.acq_win, (size_t)n * WIN_N * sizeof(c16), hipMemcpyDeviceToHost));
+    for (int s = 0; s < n; s++) { int rc = acq_peek(e, s, samperr + s, peak + 2 * s, hist_out + (size_t)s * 62); if (rc) return rc; }
+    for (int s = 0; s < n; s++) { int rc = nrsc5hip_stream_fresh(e, s); if (rc) return rc; }
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_acquire(nrsc5hip_engine *e, int n, const int16_t *win, const int16_t *hist, const int *state, const int *fill,
+                                      int16_t *filt, float *sums, int *samperr, float *peak, int16_t *hist_out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!win || !hist || !state || !fill || !filt || !sums || !samperr || !peak || !hist_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    int rc = acq_check_common(e, n, state, MODE_FM, WIN_N); if (rc) return rc;
+    for (int s = 0; s < n; s++) if (fill[s] < 0 || fill[s] > WIN_N) FAIL(NRSC5HIP_EINVAL, "stream %d: fill %d: 0 .. %d samples", s, fill[s], WIN_N);
+    for (int s = 0; s < n; s++) if ((rc = nrsc5hip_stream_fresh(e, s))) return rc;
+    for (int s = 0; s < n; s++) {
+        HIPCHK(hipMemcpy(e->db.q15 + (size_t)s * e->db.q15_cap, win + (size_t)s * WIN_N * 2, (size_t)WIN_N * sizeof(c16), hipMemcpyHostToDevice));
+        POKE(e->db.state + s, StreamState, wr, (long long)fill[s]);
+        if ((rc = acq_poke(e, s, hist + (size_t)s * 62, state[s]))) return rc;
+    }
+    return acq_run_fm(e, n, nullptr, filt, sums, samperr, peak, hist_out);
+}
+
+extern "C" int nrsc5hip_stage_acquire_raw(nrsc5hip_engine *e, int n, const uint8_t *iq, long long nbytes, const long long *rd, const int16_t *hist, const int *state,
+                                          int16_t *acq_win, int16_t *filt, float *sums, int *samperr, float *peak, int16_t *hist_out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!iq || !rd || !hist || !state || !acq_win || !filt || !sums || !samperr || !peak || !hist_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!e->cfg.batch_zero_copy || !e->db.acq_win) FAIL(NRSC5HIP_EINVAL, "engine was created without batch_zero_copy");
+    int rc = acq_check_common(e, n, state, MODE_FM, WIN_N); if (rc) return rc;
+    if (nbytes < 4 || nbytes % 4 || nbytes > (1LL << 30)) FAIL(NRSC5HIP_EINVAL, "bad capture length %lld", nbytes);
+    // decimated sample a reads the dwords a - 7 .. a of the capture (in front of it: history, never memory): the window's last sample bounds every read
+    for (int s = 0; s < n; s++) if (rd[s] < 0 || 4 * (rd[s] + WIN_N) > nbytes) FAIL(NRSC5HIP_EINVAL, "stream %d: the window at %lld reaches beyond the %lld raw dwords", s, rd[s], nbytes / 4);
+    DevTmp draw;
+    HIPCHK(hipMalloc(&draw.p, (size_t)n * (size_t)nbytes));
+    HIPCHK(hipMemcpy(draw.p, iq, (size_t)n * (size_t)nbytes, hipMemcpyHostToDevice));
+    for (int s = 0; s < n; s++) if ((rc = nrsc5hip_stream_fresh(e, s))) return rc;
+    std::vector<unsigned> counts((size_t)n, (unsigned)nbytes);
+    HIPCHK(hipMemcpy(e->nbytes_dev, counts.data(), counts.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    launch_attach_raw(e->db, n, nullptr, (const uint8_t *)draw.p, nbytes, e->nbytes_dev, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    for (int s = 0; s < n; s++) {
+        POKE(e->db.state + s, StreamState, rd, rd[s]);
+        if ((rc = acq_poke(e, s, hist + (size_t)s * 62, state[s]))) return rc;
+    }
+    return acq_run_fm(e, n, acq_win, filt, sums, samperr, peak, hist_out);      // (the reset detaches the captures before draw is freed)
+}
+
+extern "C" int nrsc5hip_stage_am_acquire(nrsc5hip_engine *e, const int16_t *win, const int16_t *hist, int state, int fill, int *samperr, float *peak, int16_t *hist_out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!win || !hist || !samperr || !peak || !hist_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!e->db.am) FAIL(NRSC5HIP_EINVAL, "engine was created without am_enable");
+    int rc = acq_check_common(e, 1, &state, MODE_AM, AM_WIN); if (rc) return rc;
+    if (fill < 0 || fill > AM_WIN) FAIL(NRSC5HIP_EINVAL, "fill %d: 0 .. %d samples", fill, AM_WIN);
+    if ((rc = nrsc5hip_stream_fresh(e, 0))) return rc;
+    DevBuffers db = e->db;                                                     // without the consumers a stage run must not feed (stage_stream0)
+    db.l2_ring = nullptr; db.l2_px_ring = nullptr; db.l2_am_ring = nullptr; db.p1_mirror = nullptr;
+    HIPCHK(hipMemcpy(db.q15, win, (size_t)AM_WIN * sizeof(c16), hipMemcpyHostToDevice));
+    POKE(db.state, StreamState, wr, (long long)fill);
+    if ((rc = acq_poke(e, 0, hist, state))) return rc;
+    HIPCHK(hipMemsetAsync(db.counters, 0, 4 * sizeof(int), e->main));
+    // the launch form follows the engine, as in run_steps_am: k_am_block<512> for the window pipeline (p1_async; window 0, slot 0), k_am_block<256> in order
+    launch_am_step(e->tb, db, 1, nullptr, e->main, e->cfg.l2_feedback, e->cfg.p1_async ? 0 : -1, 0, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    if ((rc = acq_peek(e, 0, samperr, peak, hist_out))) return rc;
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
 extern "C" int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out)
 {
     ON_ENGINE_DEVICE(e);

@@ -102,6 +102,7 @@ MATH_REF_SINCOSF, MATH_REF_ATAN2F, MATH_FAST_SINCOS, MATH_FAST_SINCOS_REDUCED, M
 HB_ACQ, HB_SYM128, HB_SYM256 = range(3)     # NRSC5HIP_HB_*: the forms of the fused half-band (csrc/halfband_raw.h)
 CODE_E1, CODE_E2 = 1, 2                     # NRSC5HIP_CODE_*: the two K=9 codes of the AM path
 HB_SYM_N = 2160                             # decimated samples of one symbol
+ACQ_WIN_FM, ACQ_SYM_FM, ACQ_WIN_AM, ACQ_SYM_AM = 71280, 2160, 8910, 270   # acquisition window (33 symbols) and symbol, FM / AM
 L2_STATUS = ("end", "no_audio", "fixed_data", "header_rs", "bad_locators", "too_many_pdus", "hef_overrun", "bad_stream", "bad_length", "audio_end")
 
 
@@ -185,6 +186,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_stage_px_interleave.argtypes = [vp, ci, ci, vp, vp, vp]
     lib.nrsc5hip_stage_am_deinterleave.argtypes = [vp, ci, ci, vp, vp, vp]
     lib.nrsc5hip_stage_am_epilogue.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    lib.nrsc5hip_stage_acquire.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.nrsc5hip_stage_acquire_raw.argtypes = [vp, ci, vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.nrsc5hip_stage_am_acquire.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
     lib.nrsc5hip_debug_poison_results.argtypes = [vp]
     lib.nrsc5hip_debug_seam_totals.argtypes = [vp, ci]
     lib.nrsc5hip_debug_seam_totals.restype = None
@@ -256,7 +260,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
-    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
+    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
     "nrsc5hip_stream_set_mode", "nrsc5hip_am_frame_bits", "nrsc5hip_stage_viterbi_k9", "nrsc5hip_px_frame_bits",
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
@@ -740,6 +744,51 @@ class Engine:
         out, words, err = np.zeros(max(length, 0), dtype=np.uint8), np.zeros((max(length, 0) + 31) // 32, dtype=np.uint32), ctypes.c_int(-1)
         self._check(self.lib.nrsc5hip_stage_am_epilogue(self._h, _ptr(soft), _ptr(bits), length, code, threads, ctypes.byref(err), out.ctypes.data, words.ctypes.data))
         return err.value, out, words
+
+    # coarse acquisition: the production launches on caller windows (tests/acq_checks.py).  None for an array stays None: the hook rejects it
+    def _acq_outputs(self, n, raw=False):
+        n = max(n, 0)
+        out = dict(filt=np.zeros((n, ACQ_WIN_FM, 2), dtype=np.int16), sums=np.zeros((n, ACQ_SYM_FM, 2), dtype=np.float32), samperr=np.zeros(n, dtype=np.int32),
+                   peak=np.zeros((n, 2), dtype=np.float32), hist_out=np.zeros((n, 31, 2), dtype=np.int16))
+        if raw:
+            out["acq_win"] = np.zeros((n, ACQ_WIN_FM, 2), dtype=np.int16)
+        return out
+
+    def stage_acquire(self, win, hist, state, fill, n: int | None = None) -> dict:
+        """nrsc5hip_stage_acquire: launch_acquire on streams 0 .. n-1.  win int16 [n, 71280, 2], hist int16 [n, 31, 2], state / fill int [n] ->
+        dict(filt [n, 71280, 2], sums float32 [n, 2160, 2], samperr [n], peak float32 [n, 2], hist_out [n, 31, 2])"""
+        n = len(state) if n is None else n
+        m = max(n, 0)
+        win, hist = _exact(win, np.int16, m * ACQ_WIN_FM * 2), _exact(hist, np.int16, m * 62)
+        state, fill = _exact(state, np.int32, m), _exact(fill, np.int32, m)
+        o = self._acq_outputs(n)
+        self._check(self.lib.nrsc5hip_stage_acquire(self._h, n, _ptr(win), _ptr(hist), _ptr(state), _ptr(fill), o["filt"].ctypes.data, o["sums"].ctypes.data,
+                                                    o["samperr"].ctypes.data, o["peak"].ctypes.data, o["hist_out"].ctypes.data))
+        return o
+
+    def stage_acquire_raw(self, iq, rd, hist, state, n: int | None = None) -> dict:
+        """nrsc5hip_stage_acquire_raw (batch_zero_copy engine): iq uint8 [n, nbytes] attached as captures, rd int64 [n] -> as stage_acquire, plus
+        acq_win [n, 71280, 2], the window k_acq_decimate made"""
+        n = len(state) if n is None else n
+        m = max(n, 0)
+        nbytes = 0
+        if iq is not None:
+            iq = np.ascontiguousarray(iq, dtype=np.uint8)
+            nbytes = iq.size // max(m, 1)
+            iq = iq.reshape(-1)
+        rd, hist, state = _exact(rd, np.int64, m), _exact(hist, np.int16, m * 62), _exact(state, np.int32, m)
+        o = self._acq_outputs(n, raw=True)
+        self._check(self.lib.nrsc5hip_stage_acquire_raw(self._h, n, _ptr(iq), nbytes, _ptr(rd), _ptr(hist), _ptr(state), o["acq_win"].ctypes.data, o["filt"].ctypes.data,
+                                                        o["sums"].ctypes.data, o["samperr"].ctypes.data, o["peak"].ctypes.data, o["hist_out"].ctypes.data))
+        return o
+
+    def stage_am_acquire(self, win, hist, state: int, fill: int = ACQ_WIN_AM) -> dict:
+        """nrsc5hip_stage_am_acquire: one launch_am_step on stream 0 (AM mode).  win int16 [8910, 2], hist int16 [31, 2] ->
+        dict(samperr, peak float32 [2], hist_out [31, 2]) read from the stream state after the step"""
+        win, hist = _exact(win, np.int16, ACQ_WIN_AM * 2), _exact(hist, np.int16, 62)
+        se, peak, hist_out = ctypes.c_int(0), np.zeros(2, dtype=np.float32), np.zeros((31, 2), dtype=np.int16)
+        self._check(self.lib.nrsc5hip_stage_am_acquire(self._h, _ptr(win), _ptr(hist), state, fill, ctypes.byref(se), peak.ctypes.data, hist_out.ctypes.data))
+        return dict(samperr=np.array([se.value], dtype=np.int32), peak=peak[None], hist_out=hist_out[None])
 
     def stage_selftest(self) -> int:
         n = ctypes.c_int(-1)

@@ -159,7 +159,7 @@ static inline float complex q15_to_cf_conj(orc_c16 v)   /* defines.h:111 */
 }
 static inline float norm2(float complex v) { float a = crealf(v), b = cimagf(v); return a * a + b * b; }
 
-static void cp_correlate(const float complex *buf, int *samperr_out, float complex *peak)
+static void cp_correlate(const float complex *buf, int *samperr_out, float complex *peak, float complex *sums_out, float *mag_out)
 {
     static __thread float complex sums[SYM_N];
     float complex max_v = 0;
@@ -174,17 +174,19 @@ static void cp_correlate(const float complex *buf, int *samperr_out, float compl
         for (int j = 0; j < CP_N; ++j)
             v += sums[(i + j) % SYM_N] * shape_fm[j] * shape_fm[j + FFT_N];
         float mag = norm2(v);
+        if (mag_out) mag_out[i] = mag;
         if (mag > max_mag) { max_mag = mag; max_v = v; samperr = (i + SYM_N - 15) % SYM_N; }
     }
     *samperr_out = samperr; *peak = max_v;
+    if (sums_out) memcpy(sums_out, sums, sizeof(sums));        /* sums_out, mag_out: stage tests only, the whole path passes NULL */
 }
 
-void orc_cp_correlate_fm(const orc_c16 *filtered, int *samperr, float peak[2])
+void orc_cp_correlate_fm(const orc_c16 *filtered, int *samperr, float peak[2], float *sums, float *mag)
 {
     build_tables();
     float complex *buf = malloc(sizeof(float complex) * WIN_N), pk;
     for (int i = 0; i < WIN_N; i++) buf[i] = q15_to_cf_conj(filtered[i]);
-    cp_correlate(buf, samperr, &pk);
+    cp_correlate(buf, samperr, &pk, (float complex *)sums, mag);
     peak[0] = crealf(pk); peak[1] = cimagf(pk);
     free(buf);
 }
@@ -771,7 +773,7 @@ static void process_window(orc_stream *s)
         float complex peak;
         orc_fir32_fm(s->fir_hist, s->ring, WIN_N, filt);
         for (int i = 0; i < WIN_N; i++) buf[i] = q15_to_cf_conj(filt[i]);
-        cp_correlate(buf, &samperr, &peak);
+        cp_correlate(buf, &samperr, &peak, NULL, NULL);
         angle_diff = cargf(peak * cexpf(I * -s->prev_angle));
         angle_factor = (s->prev_angle) ? 0.25 : 1.0;
         angle = s->prev_angle + (angle_diff * angle_factor);

@@ -50,7 +50,8 @@ void orc_fir32_fm(orc_c16 hist[31], const orc_c16 *in, size_t n, orc_c16 *out);
 
 /* K2b acquire.c:122-157.  Cyclic-prefix correlation over a 33-symbol Q15 window already
  * FIR-filtered; returns samperr and the correlation value at the peak. */
-void orc_cp_correlate_fm(const orc_c16 *filtered /*71280*/, int *samperr, float peak[2]);
+void orc_cp_correlate_fm(const orc_c16 *filtered /*71280*/, int *samperr, float peak[2], float *sums /* [2160][2] per-offset correlation sums, or NULL */,
+                         float *mag /* [2160] |sliding sum|^2 per candidate, or NULL */);
 
 /* K6  decode.c:296-342: gather + depuncture of one L1 frame / one block. */
 void orc_deinterleave_p1(const int8_t *pm /*16*23040*/, int8_t *out /*438528*/);
@@ -138,6 +139,8 @@ size_t orc_am_decimate_cu8(orc_am_decim *d, const uint8_t *iq, size_t nbytes, or
 
 /* K2a-AM firdecim_q15.c:95-109 with the acquire.c:63-96 taps */
 void orc_am_fir32(orc_c16 hist[31], const orc_c16 *in, size_t n, orc_c16 *out);
+/* K2b-AM acquire.c:129-151 with the AM geometry (270-sample symbols, lag 256, 14-tap sliding sum), no conjugation of the input (defines.h:106) */
+void orc_cp_correlate_am(const orc_c16 *filtered /*8910*/, int *samperr, float peak[2], float *sums /* [270][2], or NULL */, float *mag /* [270], or NULL */);
 
 /* K6-AM  interleaver_ma1 (decode.c:74-231) incl. the 3-frame diversity delay lines (54000 bits each, updated in
  * place), and the PIDS bit gather of decode_process_pids_am (decode.c:476-501) */

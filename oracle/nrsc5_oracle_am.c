@@ -520,7 +520,7 @@ void orc_am_fir32(orc_c16 hist[31], const orc_c16 *in, size_t n, orc_c16 *out)
 }
 
 /* acquire.c:129-151 with the AM geometry */
-static void cp_correlate(const float complex *buf, int *samperr_out, float complex *peak)
+static void cp_correlate(const float complex *buf, int *samperr_out, float complex *peak, float complex *sums_out, float *mag_out)
 {
     float complex sums[SYM_A], max_v = 0;
     float max_mag = -1.0f;
@@ -534,9 +534,22 @@ static void cp_correlate(const float complex *buf, int *samperr_out, float compl
         for (int j = 0; j < CP_A; ++j)
             v += sums[(i + j) % SYM_A] * shape_am[j] * shape_am[j + FFT_A];
         float mag = norm2(v);
+        if (mag_out) mag_out[i] = mag;
         if (mag > max_mag) { max_mag = mag; max_v = v; samperr = (i + SYM_A - 15) % SYM_A; }
     }
     *samperr_out = samperr; *peak = max_v;
+    if (sums_out) memcpy(sums_out, sums, sizeof(sums));        /* sums_out, mag_out: stage tests only, the whole path passes NULL */
+}
+
+/* the AM acquisition's correlation on a filtered 33-symbol window (8910 samples): what process_window runs behind orc_am_fir32 */
+void orc_cp_correlate_am(const orc_c16 *filtered, int *samperr, float peak[2], float *sums, float *mag)
+{
+    build_tables();
+    float complex *buf = malloc(sizeof(float complex) * WIN_A), pk;
+    for (int i = 0; i < WIN_A; i++) buf[i] = q15_to_cf(filtered[i]);
+    cp_correlate(buf, samperr, &pk, (float complex *)sums, mag);
+    peak[0] = crealf(pk); peak[1] = cimagf(pk);
+    free(buf);
 }
 
 /* mix one 270-sample symbol down with the running NCO, fold the cyclic prefix (rotated by 121 samples so that
@@ -575,7 +588,7 @@ static void process_window(orc_am_stream *s)
         float complex peak;
         orc_am_fir32(s->fir_hist, s->ring, WIN_A, filt);
         for (int i = 0; i < WIN_A; i++) buf[i] = q15_to_cf(filt[i]);
-        cp_correlate(buf, &samperr, &peak);
+        cp_correlate(buf, &samperr, &peak, NULL, NULL);
         angle_diff = cargf(peak * cexpf(I * -s->prev_angle));
         angle_factor = (s->prev_angle) ? 0.25 : 1.0;
         angle = s->prev_angle + (angle_diff * angle_factor);

@@ -91,7 +91,7 @@ class Oracle:
         L.orc_halfband_fm_cu8.argtypes = [vp, vp, sz, vp]
         L.orc_halfband_fm_cu8.restype = sz
         L.orc_fir32_fm.argtypes = [vp, vp, sz, vp]
-        L.orc_cp_correlate_fm.argtypes = [vp, ctypes.POINTER(ctypes.c_int), vp]
+        L.orc_cp_correlate_fm.argtypes = [vp, ctypes.POINTER(ctypes.c_int), vp, vp, vp]
         L.orc_deinterleave_p1.argtypes = [vp, vp]
         L.orc_deinterleave_pids.argtypes = [vp, ctypes.c_uint, vp]
         L.orc_interleave_px.argtypes = [vp, vp, vp, vp, vp, ctypes.c_uint, vp]
@@ -123,6 +123,8 @@ class Oracle:
         L.orc_am_deinterleave.argtypes = [ctypes.c_int] + [vp] * 10
         L.orc_am_deinterleave_pids.argtypes = [vp, ctypes.c_int, vp]
         L.orc_bit_errors.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int]
+        L.orc_am_fir32.argtypes = [vp, vp, sz, vp]
+        L.orc_cp_correlate_am.argtypes = [vp, ctypes.POINTER(ctypes.c_int), vp, vp, vp]
 
     # ---- stage functions -------------------------------------------------------------
     def halfband_fm_cu8(self, iq: np.ndarray, hist: np.ndarray | None = None):
@@ -139,13 +141,29 @@ class Oracle:
         self.lib.orc_fir32_fm(h.ctypes.data, x.ctypes.data, x.shape[0], out.ctypes.data)
         return out, h
 
-    def cp_correlate_fm(self, filtered: np.ndarray):
+    def _cp_correlate(self, fn, nwin, nsym, filtered, sums):
         f = np.ascontiguousarray(filtered, dtype=np.int16)
-        assert f.shape == (71280, 2)
+        assert f.shape == (nwin, 2)
         se = ctypes.c_int()
         pk = np.zeros(2, dtype=np.float32)
-        self.lib.orc_cp_correlate_fm(f.ctypes.data, ctypes.byref(se), pk.ctypes.data)
-        return se.value, complex(pk[0], pk[1])
+        sm, mag = (np.zeros((nsym, 2), dtype=np.float32), np.zeros(nsym, dtype=np.float32)) if sums else (None, None)
+        fn(f.ctypes.data, ctypes.byref(se), pk.ctypes.data, sm.ctypes.data if sums else None, mag.ctypes.data if sums else None)
+        return (se.value, pk, sm, mag) if sums else (se.value, complex(pk[0], pk[1]))
+
+    def cp_correlate_fm(self, filtered: np.ndarray, sums: bool = False):
+        """-> (samperr, peak); with sums -> (samperr, peak float32 [2], the 2160 correlation sums float32 [2160, 2], |sliding sum|^2 per candidate [2160])"""
+        return self._cp_correlate(self.lib.orc_cp_correlate_fm, 71280, 2160, filtered, sums)
+
+    def am_fir32(self, x: np.ndarray, hist: np.ndarray | None = None):
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        h = np.zeros((31, 2), dtype=np.int16) if hist is None else np.ascontiguousarray(hist, dtype=np.int16).copy()
+        out = np.zeros_like(x)
+        self.lib.orc_am_fir32(h.ctypes.data, x.ctypes.data, x.shape[0], out.ctypes.data)
+        return out, h
+
+    def cp_correlate_am(self, filtered: np.ndarray, sums: bool = False):
+        """the same for the AM geometry: window of 8910 samples, 270 candidates"""
+        return self._cp_correlate(self.lib.orc_cp_correlate_am, 8910, 270, filtered, sums)
 
     def deinterleave_p1(self, pm: np.ndarray) -> np.ndarray:
         pm = np.ascontiguousarray(pm, dtype=np.int8)
