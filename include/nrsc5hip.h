@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 13   /* 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 14   /* 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -471,6 +471,77 @@ int nrsc5hip_stage_psd(nrsc5hip_psd *p, nrsc5hip_engine *e, int stream, const ui
  * or behind the last frame when reset_at[i] == nframes[i] (a record that announces no frame). */
 int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits,
                                const int *nbits, const int *nframes, const int *lcs, const int *reset_at, nrsc5hip_aas_cb cb, void *opaque);
+
+/* ---- SIS: station id, names, slogan, message, location, service descriptors, alerts (device side: csrc/k_sis.hip) -------------
+ * Every block record carries its 80-bit PIDS frame; the reference turns these frames into station information in pids_frame_push ->
+ * sis_decode (pids.c).  This consumer does that on the device: per consumer stream it keeps pids_t (pids.h:41-96, 1.4 KB) in device
+ * memory, one k_sis launch serves a whole feed (a wave64 workgroup per listed stream: CRC-12, payload walk and field extraction one lane
+ * per frame, then the extracted fields applied to the state frame by frame), and only events are copied back: one per state change the
+ * reference reports through nrsc5_report_station_id / _name / _slogan / _message / _location / _asd / _dsd / _emergency_alert /
+ * _leap_second_offset / _local_time / _exciter_info / _importer_info, in the reference's callback order.  The aggregated, deprecated
+ * NRSC5_EVENT_SIS is not an event: it is the snapshot nrsc5hip_sis_get returns.
+ * Text is delivered raw with its encoding (0: ISO-8859-1, 4: UCS-2, anything else: the reference reports a NULL string), cut at the first
+ * NUL where the reference uses strlen (short name, universal short name, long name); latitude and longitude are the signed 22-bit
+ * integers, degrees * 8192.  Alerts carry the control bytes and the text bytes; categories and location lists are not decoded.
+ * Deviations: where the reference's completeness loops run past one of its have_frame arrays -- message_len >= 191, slogan_len >= 96,
+ * alert_len >= 382, lengths no set of frames can carry -- the item is never complete and a counter says so.  A frame 0 with the same seq may rewrite
+ * the length of an item that is displayed (the reference's report() then reads past its arrays): the snapshot shows at most the 190 / 95 / 381 bytes
+ * the buffers hold, and the control data within the alert. */
+enum {
+    NRSC5HIP_SIS_STATION_ID = 1,       /* v[0] facility id; data: the two country-code characters */
+    NRSC5HIP_SIS_STATION_NAME,         /* data: the name ("-FM" appended where the frames say so), enc */
+    NRSC5HIP_SIS_STATION_SLOGAN,       /* data: the slogan, or the long name (enc 0) */
+    NRSC5HIP_SIS_STATION_MESSAGE,      /* v[0] priority; data, enc */
+    NRSC5HIP_SIS_STATION_LOCATION,     /* v[0] latitude * 8192, v[1] longitude * 8192, v[2] altitude */
+    NRSC5HIP_SIS_AUDIO_SERVICE,        /* v[0] program, v[1] access, v[2] type, v[3] sound_exp */
+    NRSC5HIP_SIS_DATA_SERVICE,         /* v[0] access, v[1] type, v[2] mime_type */
+    NRSC5HIP_SIS_ALERT,                /* v[0] control data length, data: control bytes then text bytes, enc; v[0] = -1, no data: the alert timed out */
+    NRSC5HIP_SIS_LEAP_SECOND,          /* v[0] pending offset, v[1] current offset, v[2] pending ALFN (unsigned) */
+    NRSC5HIP_SIS_LOCAL_TIME,           /* v[0] UTC offset in minutes, v[1] dst_regional, v[2] dst_local, v[3] dst_schedule */
+    NRSC5HIP_SIS_EXCITER,              /* v[0..3] parameters 4..7 as transmitted (pids.c:698-719 says what they hold) */
+    NRSC5HIP_SIS_IMPORTER              /* v[0..3] parameters 8..11 (pids.c:725-744) */
+};
+#define NRSC5HIP_SIS_NSTATS 31
+typedef struct nrsc5hip_sis nrsc5hip_sis;
+/* frame: index of the firing frame in the stream's list of this call (records with NRSC5HIP_REC_PIDS, in order; stage hook: frames) */
+typedef void (*nrsc5hip_sis_cb)(void *opaque, int stream, int frame, int kind, const int32_t v[8], int enc, const uint8_t *data, unsigned len);
+/* what report() (pids.c:284-383) would pass: lengths < 0 mean "none" */
+typedef struct nrsc5hip_sis_info {
+    char country_code[4]; int32_t fcc_facility_id;                       /* "" and -1: none yet */
+    int32_t name_enc, name_len; uint8_t name[16];
+    int32_t slogan_enc, slogan_len; uint8_t slogan[96];
+    int32_t message_enc, message_len; uint8_t message[192];
+    int32_t alert_enc, alert_len, alert_cnt_len; uint8_t alert[384];    /* control bytes [0, alert_cnt_len), then the text */
+    int32_t have_location, latitude, longitude, altitude;
+    int32_t n_audio, audio[8][4];                                        /* program, access, type, sound_exp */
+    int32_t n_data, data[16][3];                                         /* access, type, mime_type */
+} nrsc5hip_sis_info;
+/* nstreams consumer streams on the engine's device; destroy the consumer before its engine */
+int nrsc5hip_sis_create(nrsc5hip_engine *e, int nstreams, nrsc5hip_sis **out);
+void nrsc5hip_sis_destroy(nrsc5hip_sis *s);
+int nrsc5hip_sis_reset(nrsc5hip_sis *s, int stream);                     /* the state pids_init leaves */
+/* records[i][0 .. counts[i]) of consumer stream targets[i] (NULL: stream i), FM or AM records alike: every record with NRSC5HIP_REC_PIDS
+ * gives one frame, a record with NRSC5HIP_REC_TO_FINE resets the stream's state in front of its frame (decode_reset, sync.c:407).  16 bytes
+ * per record go up, ONE k_sis launch runs, the arena header and the events come back.  Events are delivered through cb (may be NULL: count
+ * only) inside the call, all of targets[0] first, each stream's in frame order and within a frame in the reference's callback order.
+ * Returns the number of events or a negative error.  A target out of range, a stream listed twice and NULL records with a count > 0 are
+ * NRSC5HIP_EINVAL and leave everything untouched.  NRSC5HIP_EOVERFLOW: the event arena, sized from host-known bounds, was too small
+ * (never a silent drop); the states have advanced, the events of the call are lost. */
+int nrsc5hip_sis_feed(nrsc5hip_sis *s, int nstreams, const int *targets, const nrsc5hip_record *const *records, const int *counts,
+                      nrsc5hip_sis_cb cb, void *opaque);
+int nrsc5hip_sis_get(nrsc5hip_sis *s, int stream, nrsc5hip_sis_info *out);
+/* Counters of one consumer stream since its creation: [0] frames, [1] CRC-12 good, [2] SIS type, [3] LLDS type, [4 + id] payloads decoded by
+ * message id (0..15), [20] walks ended by an unknown id (11..15), [21] by a payload with no room, [22] [23] [24] never-complete attempts
+ * (message, slogan, alert), [25] bad message checksum, [26] bad alert crc7, [27] bad alert control-data length, [28] bad control-data
+ * CRC, [29] events; [30] bytes the feeds copied device -> host, total over the consumer. */
+int nrsc5hip_sis_stats(nrsc5hip_sis *s, int stream, long long stats[NRSC5HIP_SIS_NSTATS]);
+/* stage hook, through the production kernel: frames[i] = nframes[i] frames of 80 bits, one per byte, exactly as handed to pids_frame_push,
+ * for consumer stream targets[i]; reset_at as in nrsc5hip_stage_psd_streams (NULL / < 0: none; == nframes[i]: behind the last frame) */
+int nrsc5hip_stage_sis(nrsc5hip_sis *s, int nstreams, const int *targets, const uint8_t *const *frames, const int *nframes,
+                       const int *reset_at, nrsc5hip_sis_cb cb, void *opaque);
+/* TEST HOOK, not for callers (tests/sis_checks.py provokes NRSC5HIP_EOVERFLOW with it): the event arena of the following calls holds at most
+ * `bytes` (0: sized from the host-known bounds again) */
+int nrsc5hip_sis_debug_arena(nrsc5hip_sis *s, long long bytes);
 
 /* ---- stage-level entry points (host buffers): parity tests of single kernels against the oracle ---- */
 int nrsc5hip_stage_halfband_fm_cu8(nrsc5hip_engine *e, const uint8_t *iq, uint32_t nbytes, int16_t *out /* [nbytes/4][2] */);

@@ -196,6 +196,42 @@ struct PsdArgs {
 };
 void launch_psd(const PsdArgs &a, int nstreams, hipStream_t st);
 
+// ---- SIS (k_sis.hip): pids_frame_push / sis_decode over the PIDS frames of the block records, one wave64 workgroup per stream ----
+constexpr int SIS_STATS = 30;                                       // device counters per stream: nrsc5hip_sis_stats [0..29]
+enum { SIS_C_FRAMES = 0, SIS_C_CRC, SIS_C_SIS, SIS_C_LLDS, SIS_C_ID0 /* .. + 15 */, SIS_C_UNKNOWN = 20, SIS_C_NOROOM, SIS_C_NC_MESSAGE, SIS_C_NC_SLOGAN,
+       SIS_C_NC_ALERT, SIS_C_BAD_CHECKSUM, SIS_C_BAD_CRC7, SIS_C_BAD_CNT_LEN, SIS_C_BAD_CNT_CRC, SIS_C_EVENTS };
+// an entry of a stream's list: the frame as the record holds it (bit i at w[i / 32] bit i % 32), flags bit 0: decode_reset in front of it,
+// bit 1: no frame (a REC_TO_FINE record without REC_PIDS)
+struct SisFrame { uint32_t w[3]; uint32_t flags; };
+struct SisStream { int target; int first; int count; int pos; };    // consumer stream, its entries [first, first + count), position in the caller's list
+struct SisArenaHdr { unsigned used, nevents, overflow, pad; };
+// an event in the arena: SisEvent, then `len` data bytes padded to a multiple of 4
+struct SisEvent { uint32_t pos, entry; uint16_t kind, len; int32_t enc; int32_t v[8]; };
+// pids_t (pids.h:41-96) without the pointer; floats as the signed 22-bit integers they are made from and a flag for "not NaN"
+struct SisState {
+    int cc, fcc;                                                    // country code: two chars, 0 = none
+    uint8_t short_name[8];
+    int long_seq, long_displayed;
+    int lat, lon, have_lat, have_lon, altitude;
+    int msg_seq, msg_priority, msg_enc, msg_len, msg_checksum, msg_displayed;
+    int asd[8][3], dsd[16][3], params[13];
+    int usn_enc, usn_append, usn_len, usn_displayed;
+    int slogan_enc, slogan_len, slogan_displayed;
+    int alert_seq, alert_enc, alert_len, alert_crc, alert_cnt_len, alert_displayed, alert_timeout;
+    uint8_t long_have[8], msg_have[32], usn_have[4], slogan_have[16], alert_have[64];
+    uint8_t long_name[60], usn[16], usn_final[16], slogan[96], message[192], alert[384];
+};
+static_assert(sizeof(SisState) % 4 == 0, "SisState is moved as words");
+struct SisArgs {
+    const SisStream *streams; const SisFrame *frames; int nentries;
+    SisState *state;                 // [consumer streams]
+    int nstreams;                    // consumer streams: a target outside [0, nstreams) is not walked
+    unsigned long long *stats;       // [consumer streams][SIS_STATS]
+    SisArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
+};
+void sis_state_init(SisState &s);                                   // pids_init, pids.c:1052-1102 (host)
+void launch_sis(const SisArgs &a, int nstreams, hipStream_t st);
+
 // ---- stage-level entry points (parity tests) ---------------------------------------------------
 // scratch of the stage-level K=7 decode (end lanes, chunk maps, packed soft words, segment metadata): owned by the engine that calls it
 struct VitScratch { int *endlane = nullptr; int cap = 0; uint8_t *gmap = nullptr; size_t gcap = 0; int *soft = nullptr; size_t scap = 0; int *meta = nullptr; int mcap = 0; };

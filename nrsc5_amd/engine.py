@@ -122,6 +122,26 @@ AAS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ct
 PSD_STATS = ("pdus", "span_bytes", "closed", "empty", "bad_fcs", "wrong_protocol", "truncated_escape", "overflows", "delivered", "d2h_bytes")   # nrsc5hip_psd_stats
 
 
+SIS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                          ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)                                     # nrsc5hip_sis_cb
+SIS_KINDS = (None, "station_id", "station_name", "station_slogan", "station_message", "station_location", "audio_service", "data_service", "alert",
+             "leap_second", "local_time", "exciter", "importer")                                         # NRSC5HIP_SIS_*
+SIS_STATS = (("frames", "crc_good", "sis", "llds") + tuple("id%d" % k for k in range(16)) +
+             ("unknown_id", "no_room", "never_complete_message", "never_complete_slogan", "never_complete_alert", "bad_checksum", "bad_crc7",
+              "bad_cnt_len", "bad_cnt_crc", "events", "d2h_bytes"))                                       # nrsc5hip_sis_stats
+SIS_EVENT_HEADER = 48                    # bytes of an event in the arena in front of its text (padded to 4); the arena header is 16
+
+
+class SisInfo(ctypes.Structure):         # nrsc5hip_sis_info
+    _fields_ = [("country_code", ctypes.c_char * 4), ("fcc_facility_id", ctypes.c_int32),
+                ("name_enc", ctypes.c_int32), ("name_len", ctypes.c_int32), ("name", ctypes.c_uint8 * 16),
+                ("slogan_enc", ctypes.c_int32), ("slogan_len", ctypes.c_int32), ("slogan", ctypes.c_uint8 * 96),
+                ("message_enc", ctypes.c_int32), ("message_len", ctypes.c_int32), ("message", ctypes.c_uint8 * 192),
+                ("alert_enc", ctypes.c_int32), ("alert_len", ctypes.c_int32), ("alert_cnt_len", ctypes.c_int32), ("alert", ctypes.c_uint8 * 384),
+                ("have_location", ctypes.c_int32), ("latitude", ctypes.c_int32), ("longitude", ctypes.c_int32), ("altitude", ctypes.c_int32),
+                ("n_audio", ctypes.c_int32), ("audio", (ctypes.c_int32 * 4) * 8), ("n_data", ctypes.c_int32), ("data", (ctypes.c_int32 * 3) * 16)]
+
+
 class Nrsc5HipError(RuntimeError):
     pass
 
@@ -230,6 +250,15 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_psd_stats.argtypes = [vp, ci, vp]
     lib.nrsc5hip_stage_psd.argtypes = [vp, vp, ci, vp, ci, ci, ci, AAS_CB, vp]
     lib.nrsc5hip_stage_psd_streams.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, AAS_CB, vp]
+    lib.nrsc5hip_sis_create.argtypes = [vp, ci, ctypes.POINTER(vp)]
+    lib.nrsc5hip_sis_destroy.argtypes = [vp]
+    lib.nrsc5hip_sis_destroy.restype = None
+    lib.nrsc5hip_sis_reset.argtypes = [vp, ci]
+    lib.nrsc5hip_sis_feed.argtypes = [vp, ci, vp, vp, vp, SIS_CB, vp]
+    lib.nrsc5hip_sis_get.argtypes = [vp, ci, ctypes.POINTER(SisInfo)]
+    lib.nrsc5hip_sis_stats.argtypes = [vp, ci, vp]
+    lib.nrsc5hip_stage_sis.argtypes = [vp, ci, vp, vp, vp, vp, SIS_CB, vp]
+    lib.nrsc5hip_sis_debug_arena.argtypes = [vp, ctypes.c_longlong]
     ll = ctypes.c_longlong
     lib.nrsc5hip_chan_create.argtypes = [ctypes.POINTER(_ChanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_chan_destroy.argtypes = [vp]
@@ -268,6 +297,8 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_hdc_adts", "nrsc5hip_hdc_host_bytes", "nrsc5hip_hdc_fixed_audio_end", "nrsc5hip_l2_apply_audio_end", "nrsc5hip_hdc_frame_reset",
     "nrsc5hip_hdc_feed",
     "nrsc5hip_psd_create", "nrsc5hip_psd_destroy", "nrsc5hip_psd_reset", "nrsc5hip_psd_feed", "nrsc5hip_psd_stats", "nrsc5hip_stage_psd", "nrsc5hip_stage_psd_streams",
+    "nrsc5hip_sis_create", "nrsc5hip_sis_destroy", "nrsc5hip_sis_reset", "nrsc5hip_sis_feed", "nrsc5hip_sis_get", "nrsc5hip_sis_stats", "nrsc5hip_stage_sis",
+    "nrsc5hip_sis_debug_arena",
     "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
     "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed",
     "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",
@@ -1178,6 +1209,172 @@ def feed_psd_batch(engine: Engine, consumer: PsdConsumer, stream_ids, recs_per_s
     rc = consumer._result(consumer.lib.nrsc5hip_psd_feed(consumer._h, engine._h, n, ids.ctypes.data, None if tg is None else tg.ctypes.data, ptrs,
                                                          counts.ctypes.data, mode, consumer._cb, None), "nrsc5hip_psd_feed")
     out = consumer.packets[first:]
+    assert rc == len(out)
+    return out
+
+
+def sis_utf8(enc: int, data: bytes) -> bytes | None:
+    """The C string the reference reports for `data` in encoding `enc` (utf8_encode, pids.c:272-282; unicode.c): 0 = ISO-8859-1, 4 = UCS-2 with an
+    optional byte-order mark (little endian without one; an odd last byte is dropped); any other encoding gives None (a NULL string).  The result is
+    cut at its first NUL, as a C string is.  (UCS-2 of length 0 is "": the reference's loop bound wraps there.)"""
+    data = bytes(data)
+    if enc == 0:
+        out = data.decode("latin-1").encode("utf-8")
+    elif enc == 4:
+        big = data[:2] == b"\xfe\xff"
+        body = data[2:] if data[:2] in (b"\xfe\xff", b"\xff\xfe") else data
+        body = body[:len(body) - len(body) % 2]
+        out = bytearray()
+        for k in range(0, len(body), 2):
+            ch = (body[k] << 8 | body[k + 1]) if big else (body[k] | body[k + 1] << 8)
+            if ch < 0x80:
+                out.append(ch)
+            elif ch < 0x800:
+                out += bytes((0xc0 | ch >> 6, 0x80 | ch & 0x3f))
+            else:
+                out += bytes((0xe0 | ch >> 12, 0x80 | (ch >> 6) & 0x3f, 0x80 | ch & 0x3f))     # (surrogates too: the reference does not pair them)
+        out = bytes(out)
+    else:
+        return None
+    return out.split(b"\0", 1)[0]
+
+
+def sis_text(enc: int, data: bytes) -> str | None:
+    raw = sis_utf8(enc, data)
+    return None if raw is None else raw.decode("utf-8", errors="replace")
+
+
+def _sis_device_info(p) -> dict:
+    """manufacturer id, versions and status of parameters 4..7 / 8..11 (pids.c:698-744)"""
+    ver = lambda a, b: [(a >> 11) & 0x1f, (a >> 6) & 0x1f, (a >> 1) & 0x1f, b]
+    return {"manufacturer_id": bytes(((p[0] >> 8) & 0x7f, p[0] & 0x7f)).split(b"\0", 1)[0].decode("latin-1"),
+            "core_version": ver(p[1], (p[3] >> 11) & 0x1f), "manufacturer_version": ver(p[2], (p[3] >> 6) & 0x1f),
+            "core_status": (p[3] >> 3) & 7, "manufacturer_status": p[3] & 7}
+
+
+def sis_event_fields(kind: str, v, enc: int, data: bytes) -> dict:
+    """An event of k_sis as the fields the reference's callback reports; text as sis_text gives it (None: an encoding the reference cannot convert)"""
+    if kind == "station_id":
+        return {"country": data.decode("latin-1"), "fcc": v[0]}
+    if kind == "station_name":
+        return {"name": sis_text(enc, data)}
+    if kind == "station_slogan":
+        return {"slogan": sis_text(enc, data)}
+    if kind == "station_message":
+        return {"message": sis_text(enc, data), "priority": v[0]}
+    if kind == "station_location":
+        return {"latitude": float(np.float32(v[0]) / np.float32(8192)), "longitude": float(np.float32(v[1]) / np.float32(8192)), "altitude": v[2]}
+    if kind == "audio_service":
+        return {"program": v[0], "access": v[1], "type": v[2], "sound_exp": v[3]}
+    if kind == "data_service":
+        return {"access": v[0], "type": v[1], "mime_type": v[2]}
+    if kind == "alert":
+        if v[0] < 0:
+            return {"message": None, "control_data": None}
+        return {"message": sis_text(enc, data[v[0]:]), "control_data": data[:v[0]]}
+    if kind == "leap_second":
+        return {"pending_offset": v[0], "current_offset": v[1], "pending_alfn": v[2] & 0xffffffff}
+    if kind == "local_time":
+        return {"utc_offset": v[0], "dst_regional": v[1], "dst_local": v[2], "dst_schedule": v[3]}
+    if kind == "exciter":
+        return {**_sis_device_info(v), "importer_connected": (v[0] >> 7) & 1}
+    if kind == "importer":
+        return _sis_device_info(v)
+    raise ValueError(kind)
+
+
+class SisConsumer:
+    """SIS on the device (nrsc5hip_sis_*): pids_frame_push / sis_decode over the PIDS frames of `nstreams` streams, their state in HBM; only
+    events reach the host.  They land in `events` as (stream, frame, kind, fields) -- frame: index of the firing frame in the stream's list of
+    that call -- and, raw, in `raw` as (stream, frame, kind, v[8], enc, data)."""
+
+    def __init__(self, engine: "Engine", nstreams: int):
+        self.lib = engine.lib
+        self._engine = engine                                    # the consumer's device buffers live on the engine's device: keep it alive
+        self._h = ctypes.c_void_p()
+        rc = self.lib.nrsc5hip_sis_create(engine._h, nstreams, ctypes.byref(self._h))
+        if rc != 0:
+            raise Nrsc5HipError(f"nrsc5hip_sis_create failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
+        self.nstreams = nstreams
+        self.events, self.raw = [], []
+        self._cb = SIS_CB(self._on_event)
+
+    def _on_event(self, opaque, stream, frame, kind, v, enc, data, n):
+        vals, body = [int(v[k]) for k in range(8)], bytes(ctypes.string_at(data, n)) if n else b""
+        name = SIS_KINDS[kind]
+        self.raw.append((int(stream), int(frame), name, vals, int(enc), body))
+        self.events.append((int(stream), int(frame), name, sis_event_fields(name, vals, int(enc), body)))
+
+    _result = PsdConsumer._result
+
+    def reset(self, stream: int):
+        self._result(self.lib.nrsc5hip_sis_reset(self._h, stream), "nrsc5hip_sis_reset")
+
+    def stats(self, stream: int) -> dict:
+        v = (ctypes.c_longlong * len(SIS_STATS))()
+        self._result(self.lib.nrsc5hip_sis_stats(self._h, stream, v), "nrsc5hip_sis_stats")
+        return dict(zip(SIS_STATS, (int(x) for x in v)))
+
+    def info(self, stream: int) -> dict:
+        """nrsc5hip_sis_get: the snapshot, i.e. what the reference's aggregated SIS event would hold"""
+        s = SisInfo()
+        self._result(self.lib.nrsc5hip_sis_get(self._h, stream, ctypes.byref(s)), "nrsc5hip_sis_get")
+        text = lambda enc, buf, n: None if n < 0 else sis_text(enc, bytes(buf[:n]))
+        return {"country": s.country_code.decode("latin-1") or None, "fcc": s.fcc_facility_id,
+                "name": text(s.name_enc, s.name, s.name_len), "slogan": text(s.slogan_enc, s.slogan, s.slogan_len),
+                "message": text(s.message_enc, s.message, s.message_len),
+                "alert": None if s.alert_len < 0 else sis_text(s.alert_enc, bytes(s.alert[s.alert_cnt_len:s.alert_len])),
+                "alert_control_data": None if s.alert_len < 0 else bytes(s.alert[:s.alert_cnt_len]),
+                "location": None if not s.have_location else (float(np.float32(s.latitude) / np.float32(8192)),
+                                                                float(np.float32(s.longitude) / np.float32(8192)), s.altitude),
+                "audio_services": [tuple(s.audio[k]) for k in range(s.n_audio)], "data_services": [tuple(s.data[k]) for k in range(s.n_data)]}
+
+    def debug_arena(self, nbytes: int):
+        self._result(self.lib.nrsc5hip_sis_debug_arena(self._h, nbytes), "nrsc5hip_sis_debug_arena")
+
+    def stage(self, targets, frames_per_stream, reset_at=None) -> list:
+        """nrsc5hip_stage_sis: frames_per_stream[i] ([nframes, 80] bits as handed to pids_frame_push; may be empty) go to consumer stream targets[i],
+        all in one call (one k_sis workgroup per stream); reset_at[i]: the frame in front of which the stream's state is reset (None / negative:
+        none; == nframes: behind the last).  -> the events of this call, all of targets[0] first"""
+        n = len(targets)
+        arrs = [np.ascontiguousarray(f, dtype=np.uint8).reshape(-1, 80) for f in frames_per_stream]
+        i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+        tg, nf = i32(targets), i32([a.shape[0] for a in arrs])
+        rs = None if reset_at is None else i32([-1 if r is None else r for r in reset_at])
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        first = len(self.events)
+        rc = self._result(self.lib.nrsc5hip_stage_sis(self._h, n, tg.ctypes.data, ptrs, nf.ctypes.data, None if rs is None else rs.ctypes.data, self._cb, None),
+                          "nrsc5hip_stage_sis")
+        out = self.events[first:]
+        assert rc == len(out)
+        return out
+
+    def close(self):
+        if self._h:
+            self.lib.nrsc5hip_sis_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def feed_sis_batch(sis: SisConsumer, targets, fresh) -> list:
+    """nrsc5hip_sis_feed: the records of many streams (fresh[i]: the RECORD_DTYPE array for consumer stream targets[i], FM or AM; may be empty or None)
+    in one native call -- one upload of 16 bytes per record, one k_sis launch, one copy of the events.  -> [(stream, frame, kind, fields)] of this
+    call, all of targets[0] first (they are appended to sis.events as well)."""
+    tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    n = int(tg.size)
+    if len(fresh) != n:
+        raise ValueError("targets and fresh must have one entry per stream")
+    arrs = [None if r is None else np.ascontiguousarray(r, dtype=RECORD_DTYPE) for r in fresh]       # kept alive over the call
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None or a.size == 0 else a.ctypes.data for a in arrs])
+    counts = np.array([0 if a is None else a.size for a in arrs], dtype=np.int32)
+    first = len(sis.events)
+    rc = sis._result(sis.lib.nrsc5hip_sis_feed(sis._h, n, tg.ctypes.data, ptrs, counts.ctypes.data, sis._cb, None), "nrsc5hip_sis_feed")
+    out = sis.events[first:]
     assert rc == len(out)
     return out
 

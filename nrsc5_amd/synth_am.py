@@ -282,11 +282,12 @@ class AmCapture:
     seed: int
 
 
-def am_ma1_signal(n_frames: int, seed: int = 1, fmt: str = "cs16", mode: str = "MA1", rdbi: int = 0):
+def am_ma1_signal(n_frames: int, seed: int = 1, fmt: str = "cs16", mode: str = "MA1", rdbi: int = 0, pids=None):
     """The clean transmission of am_ma1_capture (no CFO, offset, noise): complex128 baseband at the capture's sample rate and
     the transmitted truth (P1 frames, P3 frames, PIDS frames).  bench.py puts many receivers' channels on one such signal
     (synth_torch.channel_am)."""
     oversample = 1 if fmt == "cs16" else 32
+    pids_given = pids
     coded_p1, coded_p3, p1_list, p3_list, pids_list, chunks = [], [], [], [], [], []
     ma3 = mode == "MA3"
     for f in range(n_frames):
@@ -307,6 +308,8 @@ def am_ma1_signal(n_frames: int, seed: int = 1, fmt: str = "cs16", mode: str = "
             p3 = frame_bits(pdu3, P3_BITS_MA3, 120, 1240, 24)
             coded_p3.append(_split_p1(_puncture(conv_encode_k9(p3 ^ _SCR, GENS_E1), PUNCT_E1)))
         pids = np.stack([synth.pids_frame_bits(prng) for _ in range(BLOCKS_PER_FRAME)])
+        if pids_given is not None:                                          # the PIDS frames to transmit, one per block, cycled
+            pids = np.stack([np.asarray(pids_given[(BLOCKS_PER_FRAME * f + b) % len(pids_given)], dtype=np.uint8) for b in range(BLOCKS_PER_FRAME)])
 
         pl = np.zeros(8 * 32 * 25, dtype=np.uint8); pu = np.zeros_like(pl)
         s = np.zeros_like(pl); t = np.zeros_like(pl)
@@ -334,13 +337,14 @@ def am_ma1_signal(n_frames: int, seed: int = 1, fmt: str = "cs16", mode: str = "
 
 def am_ma1_capture(n_frames: int, seed: int = 1, cfo_hz: float = 3.0, offset: int = 1000, noise: float = 0.5,
                    fmt: str = "cs16", tail_samples: int = 1080, unit_lsb: float | None = None, mode: str = "MA1",
-                   burst: tuple | None = None, rdbi: int = 0, chan=None) -> AmCapture:
+                   burst: tuple | None = None, rdbi: int = 0, chan=None, pids=None) -> AmCapture:
     """Hybrid-AM MA1 capture of n_frames L1 frames (8 blocks x 32 symbols each).  `noise` = per-sample complex
-    noise sigma in primary QAM64 grid units; `unit_lsb` = LSBs per grid unit (default 100 for cs16, 0.8 for cu8)."""
+    noise sigma in primary QAM64 grid units; `unit_lsb` = LSBs per grid unit (default 100 for cs16, 0.8 for cu8).  `pids`: the PIDS frames to
+    transmit ([n, 80] bits, synth.sis_frame), one per block, cycled."""
     rng = np.random.default_rng(seed)
     oversample = 1 if fmt == "cs16" else 32
     fs = FS_CS16 if fmt == "cs16" else FS_CU8
-    sig, p1_list, p3_list, pids_list = am_ma1_signal(n_frames, seed, fmt, mode, rdbi)
+    sig, p1_list, p3_list, pids_list = am_ma1_signal(n_frames, seed, fmt, mode, rdbi, pids=pids)
     if chan is not None and chan.active():                     # channel.Impairments: sample-clock error, echoes, fading
         from . import channel
         sig = channel.apply(sig, fs, chan)

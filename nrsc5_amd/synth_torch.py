@@ -12,15 +12,19 @@ import torch
 from . import synth
 
 
-def payload_stream(n_frames: int, seed: int, psd_stream: bytes | None = None):
+def payload_stream(n_frames: int, seed: int, psd_stream: bytes | None = None, pids=None):
     """Truth + coded-bit matrix of one transmission: (p1 [F,146176] u8, pids [16F,80] u8, M [16F,23040] u8).  psd_stream: program 0's PSD
-    byte stream, synth.PSD_PER_FRAME bytes of it per frame (None: three flag bytes per frame, as ever)."""
+    byte stream, synth.PSD_PER_FRAME bytes of it per frame (None: three flag bytes per frame, as ever).  pids: the PIDS frames to transmit ([n, 80]
+    bits as handed to pids_frame_push), one per block, cycled (None: the reserved-id frames, as ever)."""
+    pids_given = pids
     p1s, pidss, ms = [], [], []
     for f in range(n_frames):
         prng = np.random.default_rng(0xBEEF00 + 7919 * seed + f)
         pdu, _ = synth.make_audio_pdu(f, prng, psd=None if psd_stream is None else psd_stream[synth.PSD_PER_FRAME * f:synth.PSD_PER_FRAME * (f + 1)])
         p1 = synth.p1_frame_bits(pdu)
         pids = np.stack([synth.pids_frame_bits(prng) for _ in range(16)])
+        if pids_given is not None:
+            pids = np.stack([np.asarray(pids_given[(16 * f + b) % len(pids_given)], dtype=np.uint8) for b in range(16)])
         ms.append(synth.encode_l1_frame(p1, pids).reshape(16, synth.PM_BLOCK))
         p1s.append(p1)
         pidss.append(pids)

@@ -26,6 +26,7 @@ class Station:
     timing: int = 0                      # leading samples at 1 488 375 S/s before the transmission starts
     chan: object = None                  # channel.Impairments or None
     psd: bytes | None = None             # program 0's PSD byte stream (synth_torch.payload_stream), None: flag bytes only
+    pids: object = None                  # the PIDS frames to transmit, cycled ([n, 80] bits, synth.sis_frame), None: reserved-id frames only
 
 
 @dataclass
@@ -81,7 +82,7 @@ def capture(stations, rate, fmt: str = "cs16", n_frames: int = 3, noise_rms: flo
     cap = WidebandCapture(None, rate, fmt, list(stations))
     fs_in = float(rate)
     for st in stations:
-        p1, pids, m = synth_torch.payload_stream(n_frames, seed=st.seed, psd_stream=st.psd)
+        p1, pids, m = synth_torch.payload_stream(n_frames, seed=st.seed, psd_stream=st.psd, pids=st.pids)
         sig = synth_torch.modulate(m, dev)
         if st.chan is not None:
             from . import channel

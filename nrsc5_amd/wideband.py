@@ -6,6 +6,8 @@ and the batch engine decodes them (p1_async, l2_feedback).
 
 prints one line per station event (SYNC with its frequency offset, MER, BER, LOST_SYNC).  --metadata adds what every program is playing
 (one ID3 line per tag: title, artist, album, genre), de-framed on the device (nrsc5hip_psd_feed): no frame is copied to the host for it.
+--sis adds who every station is (one line per station id, name, slogan, message, location, service descriptor, alert and time / exciter / importer
+parameter as it arrives), decoded from the PIDS frames on the device (nrsc5hip_sis_feed); with a scan, every `found` line then carries the call sign.
 --dump-hdc DIR also records every station's
 audio programs (the reference's NRSC5_EVENT_HDC packets, as `nrsc5 --dump-hdc` frames them: ADTS) into
 DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.  FILE may be `-` (standard input, read in
@@ -45,10 +47,15 @@ class WidebandReceiver:
     call per push over all stations' new records; only finished AAS packets reach the host).  Packets on the PSD ports (0x5100,
     0x5201..0x5207) that hold an ID3v2.3 tag become ("id3", {"program", "title", "artist", "album", "genre"}) events behind that station's
     record events of the push, and now_playing[s][program] keeps the last tag; every other packet is kept raw in aas[s] as (program, port,
-    seq, data); on_aas(station, program, port, seq, data), if given, sees every packet, tags included.  With programs=True as well the frames are indexed twice per push, once by each consumer."""
+    seq, data); on_aas(station, program, port, seq, data), if given, sees every packet, tags included.  With programs=True as well the frames are indexed twice per push, once by each consumer.
+    sis=True: the receiver also decodes every station's station information service on the device (SisConsumer: one eng.feed_sis_batch call per push over
+    all stations' new records; 16 bytes per record go up, only events come back).  Every state change the reference reports becomes an event
+    (eng.SIS_KINDS: "station_id", "station_name", "station_slogan", "station_message", "station_location", "audio_service", "data_service", "alert",
+    "leap_second", "local_time", "exciter", "importer"; fields as eng.sis_event_fields) behind that station's record (and id3) events of the push, and
+    station_info[s] is the station's snapshot (SisConsumer.info: country, fcc, name, slogan, message, alert, location, services)."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
-                 programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None):
+                 programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -76,6 +83,22 @@ class WidebandReceiver:
         self.psd = eng.PsdConsumer(self.engine, self.k) if self.metadata else None
         self.now_playing = [{} for _ in range(self.k)]
         self.aas = [[] for _ in range(self.k)]
+        self.sis = eng.SisConsumer(self.engine, self.k) if sis else None
+
+    @property
+    def station_info(self) -> list:
+        """per station, the SIS snapshot (None without sis=True)"""
+        return [None if self.sis is None else self.sis.info(s) for s in range(self.k)]
+
+    def _feed_sis(self, fresh, events):
+        """fresh[s], events[s]: as for _feed_metadata"""
+        if not any(len(r) for r in fresh):
+            return
+        for s, _, kind, v in eng.feed_sis_batch(self.sis, self.ids, fresh):
+            self.logs[s].append((kind, v))
+            events[s].append((s, kind, v))
+        self.sis.events.clear()
+        self.sis.raw.clear()
 
     def _feed_metadata(self, fresh, events):
         """fresh[s]: as for _feed_programs; events[s]: the station's events of this push, which the id3 events go behind"""
@@ -138,6 +161,8 @@ class WidebandReceiver:
             self._feed_programs(fresh)
         if self.metadata:
             self._feed_metadata(fresh, new)
+        if self.sis is not None:
+            self._feed_sis(fresh, new)
         return [ev for per in new for ev in per]
 
     def station_records(self, s: int) -> np.ndarray:
@@ -148,6 +173,8 @@ class WidebandReceiver:
             self.hdc.close()
         if self.psd is not None:
             self.psd.close()
+        if self.sis is not None:
+            self.sis.close()
         self.engine.close()
         self.chan.close()
 
@@ -192,6 +219,7 @@ def parse_id3(data: bytes) -> dict | None:
 
 CONFIRM_SECONDS = 1.0       # twice the largest first-PIDS time measured on the synthetic scenes, and not below 1 s
 CONFIRM_MAX = 64            # nominations decoded by one confirmation pass, highest score first
+NAME_SECONDS = 9.3          # scan(names=True): twice the largest first-name time measured on the synthetic scenes, 4.65 s
 
 
 @dataclass
@@ -205,6 +233,10 @@ class FoundStation:
     psmi: int | None = None
     pids_ok: int | None = None           # PIDS frames with a good CRC-12 inside the confirmation window
     first_pids_s: float | None = None    # capture time at the end of the push that delivered the first of them
+    name: str | None = None              # scan(names=True): the station's name (SIS short or universal short name), e.g. "WXYZ-FM"
+    country: str | None = None           # ... its country code and FCC facility id (SIS station id)
+    facility_id: int | None = None
+    first_name_s: float | None = None    # capture time at the end of the push that delivered the name
 
 
 def _device_samples(raw, fmt: int, device: int):
@@ -236,9 +268,11 @@ def survey(raw, rate, fmt: str, *, seconds: float | None = None, nfft: int = 0, 
 
 
 def confirm_stations(raw, rate, fmt: str, found, *, confirm_seconds: float = CONFIRM_SECONDS, chunk: int = 1 << 22, device: int = 0,
-                     lib_path: str | None = None) -> list:
+                     lib_path: str | None = None, names: bool = False, name_seconds: float | None = None) -> list:
     """decode the nominated centres (the CONFIRM_MAX best scores) over the first confirm_seconds of the capture in one engine; keep
-    those whose stream reaches fine sync and delivers at least one PIDS frame with a good CRC-12"""
+    those whose stream reaches fine sync and delivers at least one PIDS frame with a good CRC-12.  names=True: the decode runs a SisConsumer
+    and goes on behind the confirmation window, up to name_seconds (default NAME_SECONDS) of the capture, until every kept station has a name;
+    name, country and facility_id of the stations are filled in from their SIS snapshots (None where none arrived in time)."""
     cands = sorted(found, key=lambda s: -s.score_db)[:CONFIRM_MAX]
     if not cands:
         return []
@@ -246,17 +280,26 @@ def confirm_stations(raw, rate, fmt: str, found, *, confirm_seconds: float = CON
     code = eng.IQ_FORMATS[fmt]
     x = _device_samples(raw, code, device)
     n = min(x.numel() // 2, int(confirm_seconds * fs))
-    q15 = int(n / fs * 744187.5) + 4 * 71280
-    rx = WidebandReceiver(rate, fmt, [s.offset_hz for s in cands], device=device, q15_capacity=q15, lib_path=lib_path)
+    n_names = max(n, min(x.numel() // 2, int((NAME_SECONDS if name_seconds is None else name_seconds) * fs))) if names else n
+    q15 = int(n_names / fs * 744187.5) + 4 * 71280
+    rx = WidebandReceiver(rate, fmt, [s.offset_hz for s in cands], device=device, q15_capacity=q15, lib_path=lib_path, sis=names)
+
+    def push(p, limit):
+        end = min(limit, p + chunk)
+        rx.push(x[2 * p:2 * end])
+        for k, s in enumerate(cands):
+            if s.first_pids_s is None and rx.records[k]:
+                fl = rx.records[k][-1]["flags"]
+                if np.any(((fl & eng.REC_PIDS) != 0) & ((fl & eng.REC_PIDS_CRC) != 0)):
+                    s.first_pids_s = end / fs
+            if names and s.name is None:
+                info = rx.sis.info(k)
+                if info["name"] is not None:
+                    s.name, s.first_name_s = info["name"], end / fs
+        return end
     try:
         for p in range(0, n, chunk):
-            end = min(n, p + chunk)
-            rx.push(x[2 * p:2 * end])
-            for k, s in enumerate(cands):
-                if s.first_pids_s is None and rx.records[k]:
-                    fl = rx.records[k][-1]["flags"]
-                    if np.any(((fl & eng.REC_PIDS) != 0) & ((fl & eng.REC_PIDS_CRC) != 0)):
-                        s.first_pids_s = end / fs
+            push(p, n)
         kept = []
         for k, s in enumerate(cands):
             recs = rx.station_records(k)
@@ -266,26 +309,35 @@ def confirm_stations(raw, rate, fmt: str, found, *, confirm_seconds: float = CON
             if fine.size and good:
                 s.freq_offset_hz, s.psmi, s.pids_ok = float(recs["freq_offset"][fine[0]]), int(recs["psmi"][fine[0]]), good
                 kept.append(s)
+        p = n
+        while names and p < n_names and any(s.name is None for s in kept):
+            p = push(p, n_names)
+        if names:
+            for k, s in enumerate(cands):
+                info = rx.sis.info(k)
+                s.country, s.facility_id = info["country"], (info["fcc"] if info["fcc"] >= 0 else None)
     finally:
         rx.close()
     return sorted(kept, key=lambda s: s.offset_hz)
 
 
 def scan(raw, rate, fmt: str, *, seconds: float | None = None, confirm: bool = True, confirm_seconds: float = CONFIRM_SECONDS,
-         threshold_db: float = 6.0, device: int = 0, lib_path: str | None = None) -> list:
+         threshold_db: float = 6.0, device: int = 0, lib_path: str | None = None, names: bool = False, name_seconds: float | None = None) -> list:
     """Find the HD stations of a capture.  raw: interleaved samples (numpy array, or torch tensor on the device) in `fmt` at `rate` S/s.
     The spectrum is taken over the first `seconds` (None: everything); confirm=False returns the detector's nominations, confirm=True
-    only those that decode (fine sync and a PIDS frame with a good CRC) within the first confirm_seconds.  -> [FoundStation, ...] by
-    ascending offset."""
+    only those that decode (fine sync and a PIDS frame with a good CRC) within the first confirm_seconds.  names=True: the confirmation decode
+    also reads the stations' SIS and keeps decoding a confirmed station until its name arrived, up to name_seconds (default NAME_SECONDS) of the
+    capture: FoundStation.name / country / facility_id.  -> [FoundStation, ...] by ascending offset."""
     _, _, found = survey(raw, rate, fmt, seconds=seconds, threshold_db=threshold_db, device=device, lib_path=lib_path)
     if not confirm:
         return found
-    return confirm_stations(raw, rate, fmt, found, confirm_seconds=confirm_seconds, device=device, lib_path=lib_path)
+    return confirm_stations(raw, rate, fmt, found, confirm_seconds=confirm_seconds, device=device, lib_path=lib_path, names=names, name_seconds=name_seconds)
 
 
 def format_found(s: FoundStation) -> str:
     line = f"found {s.offset_hz / 1e3:+.1f} kHz score {s.score_db:.1f} dB lower {s.lower_db:.1f} upper {s.upper_db:.1f}"
-    return line + (f" psmi {s.psmi}" if s.psmi is not None else "")
+    line += f" psmi {s.psmi}" if s.psmi is not None else ""
+    return line + (f" name {s.name}" if s.name is not None else "")
 
 
 def write_spectrum_csv(path: str, freqs, psd):
@@ -307,7 +359,31 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} LOST_SYNC"
     if kind == "id3":
         return f"{head} ID3 program {v['program']}" + "".join(f" {k}={v[k]!r}" for k in ("title", "artist", "album", "genre") if k in v)
+    if kind in _SIS_LINES:
+        return f"{head} " + _SIS_LINES[kind](v)
     return None
+
+
+def _device_line(what):
+    return lambda v: (f"{what} {v['manufacturer_id']!r} core {'.'.join(map(str, v['core_version']))}-{v['core_status']} "
+                      f"manufacturer {'.'.join(map(str, v['manufacturer_version']))}-{v['manufacturer_status']}"
+                      + (f" importer_connected={v['importer_connected']}" if "importer_connected" in v else ""))
+
+
+_SIS_LINES = {
+    "station_id": lambda v: f"STATION_ID country={v['country']} facility_id={v['fcc']}",
+    "station_name": lambda v: f"STATION_NAME {v['name']!r}",
+    "station_slogan": lambda v: f"STATION_SLOGAN {v['slogan']!r}",
+    "station_message": lambda v: f"STATION_MESSAGE {v['message']!r}",
+    "station_location": lambda v: f"STATION_LOCATION latitude={v['latitude']:.4f} longitude={v['longitude']:.4f} altitude={v['altitude']} m",
+    "audio_service": lambda v: f"AUDIO_SERVICE program={v['program']} access={v['access']} type={v['type']} sound_exp={v['sound_exp']}",
+    "data_service": lambda v: f"DATA_SERVICE access={v['access']} type={v['type']} mime_type={v['mime_type']:03x}",
+    "alert": lambda v: "ALERT ended" if v["control_data"] is None else f"ALERT {v['message']!r} control_data={v['control_data'].hex()}",
+    "leap_second": lambda v: f"LEAP_SECOND pending_offset={v['pending_offset']} current_offset={v['current_offset']} pending_alfn={v['pending_alfn']}",
+    "local_time": lambda v: f"LOCAL_TIME utc_offset={v['utc_offset']} min dst_regional={v['dst_regional']} dst_local={v['dst_local']} dst_schedule={v['dst_schedule']}",
+    "exciter": _device_line("EXCITER"),
+    "importer": _device_line("IMPORTER"),
+}
 
 
 class HdcDump:
@@ -366,6 +442,7 @@ def main(argv=None) -> int:
     ap.add_argument("--dump-hdc", metavar="DIR", default=None,
                     help="write every station's audio programs as ADTS: DIR/station<k>_<offset in Hz>_p<program>.aac")
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
+    ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                  # "--offsets -800e3,0,400e3": a value that starts with '-' is still the value
         if argv[i] == "--offsets":
@@ -381,13 +458,13 @@ def main(argv=None) -> int:
     if stdin and (do_scan or a.spectrum):
         ap.error("standard input cannot be scanned (the scan reads the head of a real file): give --offsets, without --scan / --spectrum")
     if do_scan or a.spectrum:
-        head = np.fromfile(a.file, dtype=dtype, count=2 * int(a.scan_seconds * float(rate)))
+        head = np.fromfile(a.file, dtype=dtype, count=2 * int(max(a.scan_seconds, NAME_SECONDS if a.sis else 0.0) * float(rate)))
         head = _device_samples(head, fmt, a.device)
-        freqs, psd, found = survey(head, rate, a.format, threshold_db=a.threshold_db, device=a.device)
+        freqs, psd, found = survey(head, rate, a.format, seconds=a.scan_seconds, threshold_db=a.threshold_db, device=a.device)
         if a.spectrum:
             write_spectrum_csv(a.spectrum, freqs, psd)
         if do_scan:
-            found = confirm_stations(head, rate, a.format, found, confirm_seconds=a.scan_seconds, device=a.device)
+            found = confirm_stations(head, rate, a.format, found, confirm_seconds=a.scan_seconds, device=a.device, names=a.sis)
             for s in found:
                 print(format_found(s), flush=True)
             if a.scan_only:
@@ -398,7 +475,7 @@ def main(argv=None) -> int:
                     print("no station found", file=sys.stderr)
                     return 1
         del head
-    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata)
+    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis)
     dump = None
     if a.dump_hdc is not None:
         dump = HdcDump(a.dump_hdc, offsets, rx.hdc.adts)
