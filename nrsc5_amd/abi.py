@@ -1,0 +1,124 @@
+"""What include/nrsc5hip.h declares, as Python: constants, ctypes structures, callback types and the error every binding raises.  A leaf module:
+engine.py and consumers.py both import it, and it imports neither."""
+from __future__ import annotations
+
+import ctypes
+import numpy as np
+
+
+SYNC_NONE, SYNC_COARSE, SYNC_FINE = 0, 1, 2
+REC_PROCESSED, REC_TO_COARSE, REC_TO_FINE, REC_MER, REC_PIDS, REC_P1 = 1, 2, 4, 8, 16, 32
+REC_P3, REC_P4 = 128, 256
+REC_LOST_SYNC = 64
+REC_PIDS_CRC = 512
+REC_DISCARDED = 1024      # never delivered by drain / batch_fetch* (replay, k_replay.hip)
+PX_WORDS = 144
+MODE_FM, MODE_AM = 0, 1
+AM_P1_BITS, AM_P1_WORDS, AM_P3_WORD0 = 3750, 118, 944
+P1_BITS, P1_WORDS, PIDS_BITS = 146176, 4568, 80
+
+RECORD_DTYPE = np.dtype([
+    ("flags", "<u4"), ("state_before", "<i4"), ("state_after", "<i4"), ("samperr", "<i4"), ("cfo", "<i4"),
+    ("keep", "<i4"), ("bc", "<i4"), ("psmi", "<i4"), ("cfo_wait", "<i4"), ("next_samperr", "<i4"),
+    ("prev_angle", "<f4"), ("phase_re", "<f4"), ("phase_im", "<f4"), ("next_angle", "<f4"),
+    ("freq_offset", "<f4"), ("mer_lb", "<f4"), ("mer_ub", "<f4"), ("ber", "<f4"),
+    ("p1_slot", "<i4"), ("bc_decoded", "<i4"), ("pids", "<u4", (3,)), ("sis", "<u4")])
+assert RECORD_DTYPE.itemsize == 96
+
+
+class _Config(ctypes.Structure):
+    _fields_ = [("device", ctypes.c_int), ("max_streams", ctypes.c_int), ("q15_capacity", ctypes.c_longlong),
+                ("record_capacity", ctypes.c_int), ("p1_slots", ctypes.c_int), ("p1_async", ctypes.c_int),
+                ("l2_feedback", ctypes.c_int), ("am_enable", ctypes.c_int), ("batch_zero_copy", ctypes.c_int), ("l2_index", ctypes.c_int)]
+
+
+class L2Pdu(ctypes.Structure):
+    """nrsc5hip_l2_pdu (include/nrsc5hip.h)"""
+    _fields_ = ([("start", ctypes.c_uint32), ("psd_off", ctypes.c_uint32), ("psd_len", ctypes.c_int32), ("audio_off", ctypes.c_uint32),
+                 ("crc_bad_lo", ctypes.c_uint32), ("crc_bad_hi", ctypes.c_uint32), ("pdu_marker", ctypes.c_uint32),
+                 ("hef_pdu_len", ctypes.c_uint16), ("loc", ctypes.c_uint16 * 64)] +
+                [(n, ctypes.c_uint8) for n in ("codec_mode", "stream_id", "pdu_seq", "blend_control", "per_stream_delay", "common_delay",
+                                               "latency", "pfirst", "plast", "seq", "nop", "hef", "la_location", "rs_corrections",
+                                               "class_ind", "prog_num", "access", "prog_type", "applied_services", "elastic_seq",
+                                               "align_offset", "skipped")])
+
+
+class L2Frame(ctypes.Structure):
+    """nrsc5hip_l2_frame"""
+    _fields_ = [("pci", ctypes.c_uint32), ("nbytes", ctypes.c_uint32), ("n_pdu", ctypes.c_uint32), ("status", ctypes.c_uint32),
+                ("end_offset", ctypes.c_uint32), ("lost_sync", ctypes.c_uint32), ("pdu", L2Pdu * 16)]
+
+
+class L2Job(ctypes.Structure):
+    """nrsc5hip_l2_job"""
+    _fields_ = [("stream", ctypes.c_int32), ("slot", ctypes.c_int32), ("kind", ctypes.c_int32), ("which", ctypes.c_int32),
+                ("nbits", ctypes.c_int32)]
+
+
+class _ChanConfig(ctypes.Structure):
+    """nrsc5hip_chan_config"""
+    _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("nchan", ctypes.c_int), ("rate_num", ctypes.c_longlong),
+                ("rate_den", ctypes.c_longlong), ("offset_hz", ctypes.c_void_p), ("gain", ctypes.c_void_p)]
+
+
+class _ScanConfig(ctypes.Structure):
+    """nrsc5hip_scan_config"""
+    _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("rate_num", ctypes.c_longlong), ("rate_den", ctypes.c_longlong),
+                ("nfft", ctypes.c_int)]
+
+
+class ScanParams(ctypes.Structure):
+    """nrsc5hip_scan_params"""
+    _fields_ = [("threshold_db", ctypes.c_double), ("min_separation_hz", ctypes.c_double)]
+
+
+class ScanStation(ctypes.Structure):
+    """nrsc5hip_scan_station"""
+    _fields_ = [("offset_hz", ctypes.c_double), ("score_db", ctypes.c_float), ("lower_db", ctypes.c_float), ("upper_db", ctypes.c_float),
+                ("floor_db", ctypes.c_float)]
+
+
+IQ_CU8, IQ_CS16, IQ_CF32 = 0, 1, 2
+IQ_FORMATS = {"cu8": IQ_CU8, "cs16": IQ_CS16, "cf32": IQ_CF32}
+IQ_DTYPES = {IQ_CU8: np.uint8, IQ_CS16: np.int16, IQ_CF32: np.float32}
+EINVAL, ENOMEM, EHIP, EOVERFLOW = -1, -2, -3, -4
+TRIM_RETAIN_MAX = (8 * 16 + 1) * 71280      # NRSC5HIP_TRIM_RETAIN_MAX: what Engine.batch_trim can retain per FM stream (pipeline depth, include/nrsc5hip.h)
+TRIM_RETAIN_MAX_AM = (8 * 8 + 1) * 8910     # NRSC5HIP_TRIM_RETAIN_MAX_AM: ... per AM stream
+
+L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
+TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
+MATH_REF_SINCOSF, MATH_REF_ATAN2F, MATH_FAST_SINCOS, MATH_FAST_SINCOS_REDUCED, MATH_FAST_ATAN2, MATH_SMALL_COS_SIN, MATH_SMALL_ATAN = range(7)   # NRSC5HIP_MATH_*
+HB_ACQ, HB_SYM128, HB_SYM256 = range(3)     # NRSC5HIP_HB_*: the forms of the fused half-band (csrc/halfband_raw.h)
+CODE_E1, CODE_E2 = 1, 2                     # NRSC5HIP_CODE_*: the two K=9 codes of the AM path
+HB_SYM_N = 2160                             # decimated samples of one symbol
+ACQ_WIN_FM, ACQ_SYM_FM, ACQ_WIN_AM, ACQ_SYM_AM = 71280, 2160, 8910, 270   # acquisition window (33 symbols) and symbol, FM / AM
+L2_STATUS = ("end", "no_audio", "fixed_data", "header_rs", "bad_locators", "too_many_pdus", "hef_overrun", "bad_stream", "bad_length", "audio_end")
+
+
+HDC_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint, ctypes.c_uint)
+AAS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)   # nrsc5hip_aas_cb
+PSD_STATS = ("pdus", "span_bytes", "closed", "empty", "bad_fcs", "wrong_protocol", "truncated_escape", "overflows", "delivered", "d2h_bytes")   # nrsc5hip_psd_stats
+
+
+SIS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                          ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)                                     # nrsc5hip_sis_cb
+SIS_KINDS = (None, "station_id", "station_name", "station_slogan", "station_message", "station_location", "audio_service", "data_service", "alert",
+             "leap_second", "local_time", "exciter", "importer")                                         # NRSC5HIP_SIS_*
+SIS_STATS = (("frames", "crc_good", "sis", "llds") + tuple("id%d" % k for k in range(16)) +
+             ("unknown_id", "no_room", "never_complete_message", "never_complete_slogan", "never_complete_alert", "bad_checksum", "bad_crc7",
+              "bad_cnt_len", "bad_cnt_crc", "events", "d2h_bytes"))                                       # nrsc5hip_sis_stats
+SIS_EVENT_HEADER = 48                    # bytes of an event in the arena in front of its text (padded to 4); the arena header is 16
+
+
+class SisInfo(ctypes.Structure):         # nrsc5hip_sis_info
+    _fields_ = [("country_code", ctypes.c_char * 4), ("fcc_facility_id", ctypes.c_int32),
+                ("name_enc", ctypes.c_int32), ("name_len", ctypes.c_int32), ("name", ctypes.c_uint8 * 16),
+                ("slogan_enc", ctypes.c_int32), ("slogan_len", ctypes.c_int32), ("slogan", ctypes.c_uint8 * 96),
+                ("message_enc", ctypes.c_int32), ("message_len", ctypes.c_int32), ("message", ctypes.c_uint8 * 192),
+                ("alert_enc", ctypes.c_int32), ("alert_len", ctypes.c_int32), ("alert_cnt_len", ctypes.c_int32), ("alert", ctypes.c_uint8 * 384),
+                ("have_location", ctypes.c_int32), ("latitude", ctypes.c_int32), ("longitude", ctypes.c_int32), ("altitude", ctypes.c_int32),
+                ("n_audio", ctypes.c_int32), ("audio", (ctypes.c_int32 * 4) * 8), ("n_data", ctypes.c_int32), ("data", (ctypes.c_int32 * 3) * 16)]
+
+
+class Nrsc5HipError(RuntimeError):
+    pass

@@ -15,7 +15,7 @@
 //
 // Bounds: every span is clamped to the frame's nbytes and to the stride of the byte buffer; a job's frame index is checked against the
 // frame count; idx stays in [-1, 8212] by construction (a piece is cut at the room left); the arena is bump-allocated with the size
-// checked before the first byte is written (too small: PsdArenaHdr::overflow, which the host turns into an error).
+// checked before the first byte is written (too small: ArenaHdr::overflow, which the host turns into an error).
 // Deviations from the reference: a frame whose last raw byte is an unpaired 0x7D is dropped (the reference ORs one stale byte of its
 // buffer into the frame; such a frame fails its FCS in practice); a packet shorter than port + seq (4 bytes), for which the reference's
 // output_aas_push reads past the packet, is dropped as "wrong protocol".
@@ -35,7 +35,7 @@ struct PsdCount { unsigned long long v[PSD_STATS]; };
 enum { PSD_C_PDUS = 0, PSD_C_BYTES, PSD_C_CLOSED, PSD_C_EMPTY, PSD_C_FCS, PSD_C_PROTOCOL, PSD_C_TRUNCATED, PSD_C_OVERFLOW, PSD_C_DELIVERED };
 
 // aas_push on the raw frame buf[0, n), n >= 0; wave-uniform
-__device__ inline void psd_close(PsdSmem &sm, const PsdArgs &a, const PsdStream &s, const uint8_t *buf, int n, unsigned program, PsdCount &c)
+__device__ inline void psd_close(PsdSmem &sm, const PsdArgs &a, const ArenaStream &s, const uint8_t *buf, int n, unsigned program, PsdCount &c)
 {
     const int lane = (int)threadIdx.x;
     const unsigned long long low = (1ull << lane) - 1ull;
@@ -69,15 +69,15 @@ __device__ inline void psd_close(PsdSmem &sm, const PsdArgs &a, const PsdStream 
     const unsigned len = (unsigned)outn - 7u;                   // protocol byte, port, seq in front; FCS behind
     const unsigned rec = (unsigned)sizeof(PsdPacket) + ((len + 3u) & ~3u);
     unsigned at = 0;
-    if (lane == 0) at = atomicAdd(&a.hdr->used, rec);
+    if (lane == 0) at = arena_reserve(a.hdr, a.arena_cap, rec);
     at = __shfl(at, 0);
-    if (at > a.arena_cap || rec > a.arena_cap - at) { if (lane == 0) atomicOr(&a.hdr->overflow, 1u); return; }
+    if (at == ARENA_FULL) return;
     if (lane == 0) {
         PsdPacket p;
         p.pos = (uint32_t)s.pos; p.port = (uint16_t)(sm.out[1] | (sm.out[2] << 8)); p.seq = (uint16_t)(sm.out[3] | (sm.out[4] << 8));
         p.len = (uint16_t)len; p.program = (uint8_t)program; p.pad = 0;
         *(PsdPacket *)(a.arena + at) = p;
-        atomicAdd(&a.hdr->npackets, 1u);
+        atomicAdd(&a.hdr->count, 1u);
     }
     for (unsigned i = (unsigned)lane; i < len; i += 64u) a.arena[at + (unsigned)sizeof(PsdPacket) + i] = sm.out[5u + i];
     c.v[PSD_C_DELIVERED]++;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(64) void k_psd(PsdArgs a)
 {
     __shared__ PsdSmem sm;
     const int lane = (int)threadIdx.x;
-    const PsdStream s = a.streams[blockIdx.x];
+    const ArenaStream s = a.streams[blockIdx.x];
     for (int k = lane; k < 256; k += 64) {                      // the table of frame.c:92-125: reflected 0x8408
         unsigned v = (unsigned)k;
         for (int j = 0; j < 8; j++) v = (v & 1u) ? (v >> 1) ^ 0x8408u : v >> 1;

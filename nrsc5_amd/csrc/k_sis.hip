@@ -14,7 +14,7 @@
 //   HBM by all lanes).  Deliberately serial and plain: at most 16 frames per L1 frame and stream arrive, the stores are single bytes, and the
 //   completeness loops are at most 64 steps.
 // Events go to a packet arena as in k_psd: SisEvent, then the raw text bytes padded to 4; bump-allocated with the size checked before the first
-// byte is written (too small: SisArenaHdr::overflow, which the host turns into NRSC5HIP_EOVERFLOW).  Text is not converted here: the event carries
+// byte is written (too small: ArenaHdr::overflow, which the host turns into NRSC5HIP_EOVERFLOW).  Text is not converted here: the event carries
 // the encoding and the bytes (strlen-cut where the reference uses strlen), the host decodes.
 // Bounds: every index into the text buffers is bounded by the width of the field it is made from (long name 7 * 7 + 6 = 55 < 60, message
 // 31 * 6 + 3 = 189 < 192, universal short name frame < 2, slogan 15 * 6 + 4 = 94 < 96, alert 63 * 6 + 2 = 380 < 384); entries outside the list and
@@ -154,15 +154,15 @@ __device__ static void sis_emit(SisCtx &c, int kind, int enc, const int *v, int 
 {
     const SisArgs &a = *c.a;
     const unsigned rec = (unsigned)sizeof(SisEvent) + (((unsigned)len + 3u) & ~3u);
-    const unsigned at = atomicAdd(&a.hdr->used, rec);
-    if (at > a.arena_cap || rec > a.arena_cap - at) { atomicOr(&a.hdr->overflow, 1u); return; }
+    const unsigned at = arena_reserve(a.hdr, a.arena_cap, rec);
+    if (at == ARENA_FULL) return;
     SisEvent e;
     e.pos = c.pos; e.entry = c.entry; e.kind = (uint16_t)kind; e.len = (uint16_t)len; e.enc = enc;
     for (int k = 0; k < 8; k++) e.v[k] = k < nv ? v[k] : 0;
     *(SisEvent *)(a.arena + at) = e;
     uint8_t *d = a.arena + at + (unsigned)sizeof(SisEvent);
     for (unsigned k = 0; k < (((unsigned)len + 3u) & ~3u); k++) d[k] = k < (unsigned)len ? data[k] : (uint8_t)0;
-    atomicAdd(&a.hdr->nevents, 1u);
+    atomicAdd(&a.hdr->count, 1u);
     c.sm->cnt[SIS_C_EVENTS]++;
 }
 
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(64) void k_sis(SisArgs a)
 {
     __shared__ SisSmem sm;
     const int lane = (int)threadIdx.x;
-    const SisStream s = a.streams[blockIdx.x];
+    const ArenaStream s = a.streams[blockIdx.x];
     if (s.target < 0 || s.target >= a.nstreams) return;          // (wave-uniform: the whole workgroup leaves)
     uint32_t *gs = (uint32_t *)(a.state + s.target), *ls = (uint32_t *)&sm.st;
     for (unsigned k = (unsigned)lane; k < sizeof(SisState) / 4; k += 64u) ls[k] = gs[k];

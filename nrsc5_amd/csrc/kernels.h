@@ -176,23 +176,35 @@ void launch_l2_index_px_window(const DevBuffers &db, int nstreams, const int *st
 void launch_l2_index_am_window(const DevBuffers &db, int nstreams, const int *stream_ids, int parity, hipStream_t st);
 void launch_l2_index_am_step(const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st);
 
+// ---- arena consumers (k_psd.hip, k_sis.hip; host side: arena_consumer.h): one wave64 workgroup per listed consumer stream walks that stream's jobs and leaves
+// records in a bump-allocated arena: a record header (its first word: `pos`), then `len` bytes padded to a multiple of 4
+struct ArenaStream { int target; int first; int count; int pos; };  // consumer stream, its jobs [first, first + count), position in the caller's list
+struct ArenaHdr { unsigned used, count, overflow, pad; };           // bytes reserved (may exceed the capacity: then overflow is set), records stored
+static_assert(sizeof(ArenaStream) == 16 && sizeof(ArenaHdr) == 16, "the plan and the arena header are moved as 16-byte entries");
+constexpr unsigned ARENA_FULL = 0xffffffffu;
+// room for a record of `rec` bytes (one lane calls this) -> its offset, or ARENA_FULL with the overflow flag set: nothing of the record may be written then
+__device__ inline unsigned arena_reserve(ArenaHdr *hdr, unsigned cap, unsigned rec)
+{
+    const unsigned at = atomicAdd(&hdr->used, rec);
+    if (at > cap || rec > cap - at) { atomicOr(&hdr->overflow, 1u); return ARENA_FULL; }
+    return at;
+}
+
 // ---- PSD transport (k_psd.hip): HDLC de-framing of the PSD spans the L2 index marks, one wave64 workgroup per stream ------------
 constexpr int PSD_MAX_AAS = 8212;                                   // MAX_AAS_LEN, frame.h:5: raw bytes of one open HDLC frame
 constexpr int PSD_PROGRAMS = 8;
 constexpr int PSD_STATS = 9;                                        // device counters per stream: nrsc5hip_psd_stats [0..8]
 struct PsdJob { int frame; int keep; int reset; int pad; };         // frame: index into frames / bytes (-1: none); keep: PDUs walked at most; reset: close all
                                                                     // eight programs of the stream before this job (frame_reset)
-struct PsdStream { int target; int first; int count; int pos; };    // consumer stream, its jobs [first, first + count), position in the caller's list
-struct PsdArenaHdr { unsigned used, npackets, overflow, pad; };
 // a packet in the arena: PsdPacket, then `len` data bytes (what follows port and seq), padded to a multiple of 4
 struct PsdPacket { uint32_t pos; uint16_t port, seq, len; uint8_t program, pad; };
 struct PsdArgs {
-    const PsdStream *streams; const PsdJob *jobs; int njobs;
+    const ArenaStream *streams; const PsdJob *jobs; int njobs;
     const nrsc5hip_l2_frame *frames; const uint8_t *bytes; long long stride; int nframes;
     uint8_t *bufs;                   // [consumer streams][8][PSD_MAX_AAS]  frame_t.psd_buf
     int *idx;                        // [consumer streams][8]               frame_t.psd_idx, -1 = closed
     unsigned long long *stats;       // [consumer streams][PSD_STATS]
-    PsdArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
+    ArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
 };
 void launch_psd(const PsdArgs &a, int nstreams, hipStream_t st);
 
@@ -203,8 +215,6 @@ enum { SIS_C_FRAMES = 0, SIS_C_CRC, SIS_C_SIS, SIS_C_LLDS, SIS_C_ID0 /* .. + 15 
 // an entry of a stream's list: the frame as the record holds it (bit i at w[i / 32] bit i % 32), flags bit 0: decode_reset in front of it,
 // bit 1: no frame (a REC_TO_FINE record without REC_PIDS)
 struct SisFrame { uint32_t w[3]; uint32_t flags; };
-struct SisStream { int target; int first; int count; int pos; };    // consumer stream, its entries [first, first + count), position in the caller's list
-struct SisArenaHdr { unsigned used, nevents, overflow, pad; };
 // an event in the arena: SisEvent, then `len` data bytes padded to a multiple of 4
 struct SisEvent { uint32_t pos, entry; uint16_t kind, len; int32_t enc; int32_t v[8]; };
 // pids_t (pids.h:41-96) without the pointer; floats as the signed 22-bit integers they are made from and a flag for "not NaN"
@@ -223,11 +233,11 @@ struct SisState {
 };
 static_assert(sizeof(SisState) % 4 == 0, "SisState is moved as words");
 struct SisArgs {
-    const SisStream *streams; const SisFrame *frames; int nentries;
+    const ArenaStream *streams; const SisFrame *frames; int nentries;
     SisState *state;                 // [consumer streams]
     int nstreams;                    // consumer streams: a target outside [0, nstreams) is not walked
     unsigned long long *stats;       // [consumer streams][SIS_STATS]
-    SisArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
+    ArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
 };
 void sis_state_init(SisState &s);                                   // pids_init, pids.c:1052-1102 (host)
 void launch_sis(const SisArgs &a, int nstreams, hipStream_t st);

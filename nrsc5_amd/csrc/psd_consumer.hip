@@ -7,42 +7,21 @@
 #include <algorithm>
 #include <memory>
 #include "engine_internal.h"
+#include "arena_consumer.h"
 #include "record_jobs.h"
-
-namespace {
-
-struct DevGrow {                                                // a device buffer that only ever grows; kept between calls
-    void *p = nullptr; size_t cap = 0;
-    ~DevGrow() { if (p) (void)hipFree(p); }
-    int need(size_t n)
-    {
-        if (n <= cap) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        n += n / 4;
-        hipError_t err = hipMalloc(&p, n);
-        if (err != hipSuccess) { p = nullptr; FAIL(NRSC5HIP_ENOMEM, "hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(err)); }
-        cap = n;
-        return 0;
-    }
-};
-
-}  // namespace
 
 struct nrsc5hip_psd {
     int device = 0, nstreams = 0;
-    uint8_t *bufs = nullptr; int *idx = nullptr; unsigned long long *stats = nullptr;       // device: PsdArgs
+    DevFixed<uint8_t> bufs; DevFixed<int> idx; DevFixed<unsigned long long> stats;          // device: PsdArgs
     nrsc5hip_hdc *ccc = nullptr;                                // process_fixed_data's state per stream and logical channel, nothing else of it is used
-    long long d2h = 0;                                          // bytes the feeds copied device -> host
-    DevGrow words, ljobs, frames, bytes, plan, arena;
+    DevGrow words, ljobs, frames, bytes;
+    ArenaHost ar;
 };
 
 static void psd_free(nrsc5hip_psd *p)
 {
     if (!p) return;
     nrsc5::DeviceGuard g(p->device);
-    if (p->bufs) (void)hipFree(p->bufs);
-    if (p->idx) (void)hipFree(p->idx);
-    if (p->stats) (void)hipFree(p->stats);
     nrsc5hip_hdc_destroy(p->ccc);
     delete p;
 }
@@ -56,11 +35,11 @@ extern "C" int nrsc5hip_psd_create(nrsc5hip_engine *e, int nstreams, nrsc5hip_ps
     p->device = e->cfg.device; p->nstreams = nstreams;
     const size_t S = (size_t)nstreams;
     if (nrsc5hip_hdc_create(nstreams, &p->ccc) != 0) { psd_free(p); return NRSC5HIP_ENOMEM; }
-    HIPCHK_OR(hipMalloc((void **)&p->bufs, S * PSD_PROGRAMS * PSD_MAX_AAS), psd_free(p));
-    HIPCHK_OR(hipMalloc((void **)&p->idx, S * PSD_PROGRAMS * sizeof(int)), psd_free(p));
-    HIPCHK_OR(hipMalloc((void **)&p->stats, S * PSD_STATS * sizeof(unsigned long long)), psd_free(p));
-    HIPCHK_OR(hipMemset(p->idx, 0xff, S * PSD_PROGRAMS * sizeof(int)), psd_free(p));        // -1: closed (frame_reset)
-    HIPCHK_OR(hipMemset(p->stats, 0, S * PSD_STATS * sizeof(unsigned long long)), psd_free(p));
+    HIPCHK_OR(hipMalloc((void **)&p->bufs.p, S * PSD_PROGRAMS * PSD_MAX_AAS), psd_free(p));
+    HIPCHK_OR(hipMalloc((void **)&p->idx.p, S * PSD_PROGRAMS * sizeof(int)), psd_free(p));
+    HIPCHK_OR(hipMalloc((void **)&p->stats.p, S * PSD_STATS * sizeof(unsigned long long)), psd_free(p));
+    HIPCHK_OR(hipMemset(p->idx.p, 0xff, S * PSD_PROGRAMS * sizeof(int)), psd_free(p));        // -1: closed (frame_reset)
+    HIPCHK_OR(hipMemset(p->stats.p, 0, S * PSD_STATS * sizeof(unsigned long long)), psd_free(p));
     HIPCHK_OR(hipDeviceSynchronize(), psd_free(p));
     *out = p;
     return NRSC5HIP_OK;
@@ -72,7 +51,7 @@ extern "C" int nrsc5hip_psd_reset(nrsc5hip_psd *p, int stream)
 {
     if (!p || stream < 0 || stream >= p->nstreams) FAIL(NRSC5HIP_EINVAL, "bad consumer / stream");
     nrsc5::DeviceGuard g(p->device);
-    HIPCHK(hipMemset(p->idx + (size_t)stream * PSD_PROGRAMS, 0xff, PSD_PROGRAMS * sizeof(int)));
+    HIPCHK(hipMemset(p->idx.p + (size_t)stream * PSD_PROGRAMS, 0xff, PSD_PROGRAMS * sizeof(int)));
     HIPCHK(hipDeviceSynchronize());
     return NRSC5HIP_OK;
 }
@@ -81,16 +60,12 @@ extern "C" int nrsc5hip_psd_stats(nrsc5hip_psd *p, int stream, long long stats[1
 {
     if (!p || !stats || stream < 0 || stream >= p->nstreams) FAIL(NRSC5HIP_EINVAL, "bad consumer / stream");
     nrsc5::DeviceGuard g(p->device);
-    unsigned long long v[PSD_STATS];
-    HIPCHK(hipMemcpy(v, p->stats + (size_t)stream * PSD_STATS, sizeof(v), hipMemcpyDeviceToHost));
-    for (int k = 0; k < PSD_STATS; k++) stats[k] = (long long)v[k];
-    stats[PSD_STATS] = p->d2h;
-    return NRSC5HIP_OK;
+    return read_stats<PSD_STATS>(p->stats.p + (size_t)stream * PSD_STATS, p->ar.d2h, stats);
 }
 
 // The device work of one call and the delivery: dj[k] = frame k's words in device memory, lcs[k] its logical channel; streams / jobs: what k_psd walks
 // (PsdJob::keep is filled in here).  Nothing of the consumer's device state has been touched when this returns an error in front of the k_psd launch.
-static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job> &dj, const std::vector<int> &lcs, std::vector<PsdStream> &streams,
+static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job> &dj, const std::vector<int> &lcs, std::vector<ArenaStream> &streams,
                    std::vector<PsdJob> &jobs, nrsc5hip_aas_cb cb, void *opaque)
 {
     const size_t n = dj.size(), ns = streams.size();
@@ -108,10 +83,10 @@ static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job>
         HIPCHK(hipMemcpy2DAsync(pci.data(), sizeof(uint32_t), (const char *)p->frames.p + offsetof(nrsc5hip_l2_frame, pci), sizeof(nrsc5hip_l2_frame),
                                 sizeof(uint32_t), n, hipMemcpyDeviceToHost, e->main));
         HIPCHK(hipStreamSynchronize(e->main));
-        p->d2h += (long long)(n * sizeof(uint32_t));
+        p->ar.d2h += (long long)(n * sizeof(uint32_t));
         std::unique_ptr<nrsc5hip_l2_frame> ix;
         std::vector<uint8_t> by;
-        for (const PsdStream &s : streams)
+        for (const ArenaStream &s : streams)
             for (int j = s.first; j < s.first + s.count; j++) {
                 PsdJob &job = jobs[j];
                 if (job.reset) (void)nrsc5hip_hdc_frame_reset(p->ccc, s.target);          // sync.c:405-409
@@ -123,7 +98,7 @@ static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job>
                 HIPCHK(hipMemcpy(ix.get(), (const nrsc5hip_l2_frame *)p->frames.p + job.frame, sizeof(nrsc5hip_l2_frame), hipMemcpyDeviceToHost));
                 const unsigned nb = ix->nbytes <= (unsigned)stride ? ix->nbytes : (unsigned)stride;
                 HIPCHK(hipMemcpy(by.data(), (const uint8_t *)p->bytes.p + (size_t)job.frame * (size_t)stride, nb, hipMemcpyDeviceToHost));
-                p->d2h += (long long)sizeof(nrsc5hip_l2_frame) + nb;
+                p->ar.d2h += (long long)sizeof(nrsc5hip_l2_frame) + nb;
                 // PCI_FIXED frames carry no audio, but frame_process runs process_fixed_data on them first (nrsc5hip_hdc_push_frame does the same)
                 const unsigned audio_end = nrsc5hip_hdc_fixed_audio_end(p->ccc, s.target, lcs[job.frame], by.data(), nb);
                 if (fixed_only) continue;
@@ -135,51 +110,21 @@ static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job>
     // the plan (streams, jobs) and the arena: sized from what the host knows -- at most 16 PDUs x 255 bytes of new PSD per frame and the 8 x 8212 bytes a
     // stream may carry; a packet of `len` data bytes took len + 8 raw bytes at least (flag, protocol, port, seq, FCS) and takes 12 + len + 3 at most
     size_t raw = 0;
-    for (const PsdStream &s : streams) raw += (size_t)PSD_PROGRAMS * PSD_MAX_AAS + (size_t)s.count * NRSC5HIP_L2_MAX_PDUS * 255;
-    const size_t arena_cap = 2 * raw, plan_streams = ns * sizeof(PsdStream), plan_bytes = plan_streams + jobs.size() * sizeof(PsdJob);
+    for (const ArenaStream &s : streams) raw += (size_t)PSD_PROGRAMS * PSD_MAX_AAS + (size_t)s.count * NRSC5HIP_L2_MAX_PDUS * 255;
+    const size_t arena_cap = 2 * raw;
     if (arena_cap > 0xfffffff0u) FAIL(NRSC5HIP_EINVAL, "too many frames for one call");
-    int rc;
-    if ((rc = p->plan.need(plan_bytes)) || (rc = p->arena.need(sizeof(PsdArenaHdr) + arena_cap))) return rc;
-    std::vector<uint8_t> plan(plan_bytes);
-    memcpy(plan.data(), streams.data(), plan_streams);
-    memcpy(plan.data() + plan_streams, jobs.data(), jobs.size() * sizeof(PsdJob));
-    HIPCHK(hipMemcpy(p->plan.p, plan.data(), plan_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemsetAsync(p->arena.p, 0, sizeof(PsdArenaHdr), e->main));
-    PsdArgs a;
-    a.streams = (const PsdStream *)p->plan.p; a.jobs = (const PsdJob *)((const uint8_t *)p->plan.p + plan_streams); a.njobs = (int)jobs.size();
-    a.frames = (const nrsc5hip_l2_frame *)p->frames.p; a.bytes = (const uint8_t *)p->bytes.p; a.stride = stride; a.nframes = (int)n;
-    a.bufs = p->bufs; a.idx = p->idx; a.stats = p->stats;
-    a.hdr = (PsdArenaHdr *)p->arena.p; a.arena = (uint8_t *)p->arena.p + sizeof(PsdArenaHdr); a.arena_cap = (unsigned)arena_cap;
-    launch_psd(a, (int)ns, e->main);
-    HIPCHK(hipGetLastError());
-    PsdArenaHdr hdr;
-    HIPCHK(hipMemcpyAsync(&hdr, p->arena.p, sizeof(hdr), hipMemcpyDeviceToHost, e->main));
-    HIPCHK(hipStreamSynchronize(e->main));
-    p->d2h += (long long)sizeof(hdr);
-    if (hdr.overflow || hdr.used > arena_cap) FAIL(NRSC5HIP_EOVERFLOW, "packet arena of %zu bytes too small (%u needed): packets of this call are lost", arena_cap, hdr.used);
-    if (hdr.used == 0) return 0;
-    std::vector<uint8_t> got(hdr.used);
-    HIPCHK(hipMemcpy(got.data(), a.arena, hdr.used, hipMemcpyDeviceToHost));
-    p->d2h += hdr.used;
-    // all of the first listed stream's packets first: the arena holds each stream's packets in order, the streams interleaved
-    std::vector<std::vector<size_t>> per(ns);
-    int delivered = 0;
-    for (size_t at = 0; at + sizeof(PsdPacket) <= got.size();) {
-        PsdPacket pk;
-        memcpy(&pk, got.data() + at, sizeof(pk));
-        const size_t rec = sizeof(PsdPacket) + (((size_t)pk.len + 3) & ~(size_t)3);
-        if (pk.pos >= ns || at + rec > got.size()) FAIL(NRSC5HIP_EHIP, "packet arena is not what k_psd writes (offset %zu)", at);
-        per[pk.pos].push_back(at);
-        at += rec;
-    }
-    for (size_t i = 0; i < ns; i++)
-        for (size_t at : per[i]) {
-            PsdPacket pk;
-            memcpy(&pk, got.data() + at, sizeof(pk));
-            if (cb) cb(opaque, streams[i].target, pk.program, pk.port, pk.seq, got.data() + at + sizeof(PsdPacket), pk.len);
-            delivered++;
-        }
-    return delivered;
+    auto launch = [&](const ArenaDev &d) {
+        PsdArgs a;
+        a.streams = d.streams; a.jobs = (const PsdJob *)d.jobs; a.njobs = (int)jobs.size();
+        a.frames = (const nrsc5hip_l2_frame *)p->frames.p; a.bytes = (const uint8_t *)p->bytes.p; a.stride = stride; a.nframes = (int)n;
+        a.bufs = p->bufs.p; a.idx = p->idx.p; a.stats = p->stats.p;
+        a.hdr = d.hdr; a.arena = d.arena; a.arena_cap = d.cap;
+        launch_psd(a, (int)ns, e->main);
+    };
+    return arena_round<PsdPacket>(p->ar, e->main, "packet", "k_psd", streams, jobs.data(), jobs.size() * sizeof(PsdJob), arena_cap, launch,
+                                  [](const PsdPacket &) { return true; }, [&](const ArenaStream &s, const PsdPacket &pk, const uint8_t *data) {
+                                      if (cb) cb(opaque, s.target, pk.program, pk.port, pk.seq, data, pk.len);
+                                  });
 }
 
 // A loss of sync changes nothing here either (see nrsc5hip_hdc_feed): psd_buf / psd_idx are cleared by frame_reset on the NEXT transition to fine sync.
@@ -192,19 +137,17 @@ extern "C" int nrsc5hip_psd_feed(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstrea
     if (nstreams == 0) return 0;
     if (!stream_ids || !records || !counts) FAIL(NRSC5HIP_EINVAL, "null argument");
     size_t nframes = 0;
-    std::vector<char> seen((size_t)p->nstreams, 0);
     for (int i = 0; i < nstreams; i++) {
         const int t = targets ? targets[i] : stream_ids[i];
         if (stream_ids[i] < 0 || stream_ids[i] >= e->cfg.max_streams || t < 0 || t >= p->nstreams) FAIL(NRSC5HIP_EINVAL, "stream id out of range");
         if (counts[i] < 0 || (counts[i] > 0 && !records[i])) FAIL(NRSC5HIP_EINVAL, "records of stream %d missing", stream_ids[i]);
-        if (seen[t]) FAIL(NRSC5HIP_EINVAL, "consumer stream %d listed twice", t);         // two workgroups would walk one state
-        seen[t] = 1;
         for (int k = 0; k < counts[i]; k++) nframes += (size_t)record_jobs(records[i][k], stream_ids[i], mode, nullptr, nullptr);
     }
+    int rc = check_targets(p->nstreams, nstreams, targets ? targets : stream_ids); if (rc) return rc;
     if (nframes > (size_t)INT32_MAX / 2) FAIL(NRSC5HIP_EINVAL, "too many frames for one call");
     std::vector<nrsc5hip_l2_job> l2(nframes);
     std::vector<int> lcs(nframes);
-    std::vector<PsdStream> streams;
+    std::vector<ArenaStream> streams;
     std::vector<PsdJob> jobs;
     size_t next = 0;
     for (int i = 0; i < nstreams; i++) {
@@ -217,12 +160,12 @@ extern "C" int nrsc5hip_psd_feed(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstrea
             for (int f = 0; f < nf; f++, next++) { jobs.push_back(PsdJob{(int)next, NRSC5HIP_L2_MAX_PDUS, reset, 0}); reset = 0; }
             if (reset) jobs.push_back(PsdJob{-1, 0, 1, 0});
         }
-        if ((int)jobs.size() > first) streams.push_back(PsdStream{t, first, (int)jobs.size() - first, (int)streams.size()});
+        if ((int)jobs.size() > first) streams.push_back(ArenaStream{t, first, (int)jobs.size() - first, (int)streams.size()});
     }
     std::vector<L2Job> dj;
     if (nframes) {
         // every slot / channel / length the records name, before the consumer is touched
-        int rc = l2_resolve(e, (int)nframes, l2.data(), dj); if (rc) return rc;
+        if ((rc = l2_resolve(e, (int)nframes, l2.data(), dj))) return rc;
         HIPCHK(hipDeviceSynchronize());                         // the frames may still be in flight on a decode stream
     }
     return psd_run(p, e, dj, lcs, streams, jobs, cb, opaque);
@@ -234,24 +177,22 @@ extern "C" int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, i
     ON_ENGINE_DEVICE(e);
     if (!p || nstreams < 1 || !targets || !bits || !nbits || !nframes || !lcs) FAIL(NRSC5HIP_EINVAL, "bad argument");
     if (p->device != e->cfg.device) FAIL(NRSC5HIP_EINVAL, "the consumer was created on another engine's device");
-    std::vector<char> seen((size_t)p->nstreams, 0);
     size_t total_words = 0, total_frames = 0;
     for (int i = 0; i < nstreams; i++) {
         if (targets[i] < 0 || targets[i] >= p->nstreams || !bits[i] || nbits[i] < 1 || nbits[i] > P1_LEN || nframes[i] < 1 || lcs[i] < 0 || lcs[i] > 2)
             FAIL(NRSC5HIP_EINVAL, "stream %d of the call: bad target / frames / length / channel", i);
         if (reset_at && reset_at[i] > nframes[i]) FAIL(NRSC5HIP_EINVAL, "stream %d of the call: reset behind the end", i);
-        if (seen[targets[i]]) FAIL(NRSC5HIP_EINVAL, "consumer stream %d listed twice", targets[i]);
-        seen[targets[i]] = 1;
         total_words += (size_t)((nbits[i] + 31) / 32) * nframes[i];
         total_frames += (size_t)nframes[i];
     }
+    int rc = check_targets(p->nstreams, nstreams, targets); if (rc) return rc;
     if (total_frames > (size_t)INT32_MAX / 2) FAIL(NRSC5HIP_EINVAL, "too many frames for one call");
     std::vector<uint32_t> w(total_words, 0u);
-    int rc = p->words.need(w.size() * sizeof(uint32_t)); if (rc) return rc;
+    if ((rc = p->words.need(w.size() * sizeof(uint32_t)))) return rc;
     std::vector<L2Job> dj;
     std::vector<int> lc;
     std::vector<PsdJob> jobs;
-    std::vector<PsdStream> streams;
+    std::vector<ArenaStream> streams;
     size_t at = 0;
     for (int i = 0; i < nstreams; i++) {
         const int words = (nbits[i] + 31) / 32, first = (int)jobs.size(), rst = reset_at ? reset_at[i] : -1;
@@ -262,7 +203,7 @@ extern "C" int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, i
             lc.push_back(lcs[i]);
         }
         if (rst == nframes[i]) jobs.push_back(PsdJob{-1, 0, 1, 0});          // as a REC_TO_FINE record that announces no frame
-        streams.push_back(PsdStream{targets[i], first, (int)jobs.size() - first, i});
+        streams.push_back(ArenaStream{targets[i], first, (int)jobs.size() - first, i});
     }
     HIPCHK(hipMemcpy(p->words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return psd_run(p, e, dj, lc, streams, jobs, cb, opaque);

@@ -4,34 +4,19 @@
 //   per call, device -> host: the arena header (16 bytes) and the used part of the arena (48 bytes + the text, padded to 4, per event)
 #include <algorithm>
 #include "engine_internal.h"
+#include "arena_consumer.h"
 
 struct nrsc5hip_sis {
     int device = 0, nstreams = 0;
-    SisState *state = nullptr; unsigned long long *stats = nullptr;     // device: SisArgs
-    void *plan = nullptr, *arena = nullptr; size_t plan_cap = 0, arena_cap = 0;
-    long long d2h = 0;                                              // bytes the feeds copied device -> host
+    DevFixed<SisState> state; DevFixed<unsigned long long> stats;      // device: SisArgs
+    ArenaHost ar;
     long long arena_limit = 0;                                      // test hook: 0 = the host-known bound
 };
-
-static int sis_need(void **p, size_t *cap, size_t n)
-{
-    if (n <= *cap) return 0;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    n += n / 4;
-    hipError_t err = hipMalloc(p, n);
-    if (err != hipSuccess) { *p = nullptr; FAIL(NRSC5HIP_ENOMEM, "hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(err)); }
-    *cap = n;
-    return 0;
-}
 
 static void sis_free(nrsc5hip_sis *s)
 {
     if (!s) return;
     nrsc5::DeviceGuard g(s->device);
-    if (s->state) (void)hipFree(s->state);
-    if (s->stats) (void)hipFree(s->stats);
-    if (s->plan) (void)hipFree(s->plan);
-    if (s->arena) (void)hipFree(s->arena);
     delete s;
 }
 
@@ -43,12 +28,12 @@ extern "C" int nrsc5hip_sis_create(nrsc5hip_engine *e, int nstreams, nrsc5hip_si
     if (!s) return NRSC5HIP_ENOMEM;
     s->device = e->cfg.device; s->nstreams = nstreams;
     const size_t S = (size_t)nstreams;
-    HIPCHK_OR(hipMalloc((void **)&s->state, S * sizeof(SisState)), sis_free(s));
-    HIPCHK_OR(hipMalloc((void **)&s->stats, S * SIS_STATS * sizeof(unsigned long long)), sis_free(s));
+    HIPCHK_OR(hipMalloc((void **)&s->state.p, S * sizeof(SisState)), sis_free(s));
+    HIPCHK_OR(hipMalloc((void **)&s->stats.p, S * SIS_STATS * sizeof(unsigned long long)), sis_free(s));
     std::vector<SisState> init(S);
     for (SisState &st : init) sis_state_init(st);
-    HIPCHK_OR(hipMemcpy(s->state, init.data(), S * sizeof(SisState), hipMemcpyHostToDevice), sis_free(s));
-    HIPCHK_OR(hipMemset(s->stats, 0, S * SIS_STATS * sizeof(unsigned long long)), sis_free(s));
+    HIPCHK_OR(hipMemcpy(s->state.p, init.data(), S * sizeof(SisState), hipMemcpyHostToDevice), sis_free(s));
+    HIPCHK_OR(hipMemset(s->stats.p, 0, S * SIS_STATS * sizeof(unsigned long long)), sis_free(s));
     HIPCHK_OR(hipDeviceSynchronize(), sis_free(s));
     *out = s;
     return NRSC5HIP_OK;
@@ -62,7 +47,7 @@ extern "C" int nrsc5hip_sis_reset(nrsc5hip_sis *s, int stream)
     nrsc5::DeviceGuard g(s->device);
     SisState st;
     sis_state_init(st);
-    HIPCHK(hipMemcpy(s->state + stream, &st, sizeof(st), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->state.p + stream, &st, sizeof(st), hipMemcpyHostToDevice));
     return NRSC5HIP_OK;
 }
 
@@ -77,11 +62,7 @@ extern "C" int nrsc5hip_sis_stats(nrsc5hip_sis *s, int stream, long long stats[N
 {
     if (!s || !stats || stream < 0 || stream >= s->nstreams) FAIL(NRSC5HIP_EINVAL, "bad consumer / stream");
     nrsc5::DeviceGuard g(s->device);
-    unsigned long long v[SIS_STATS];
-    HIPCHK(hipMemcpy(v, s->stats + (size_t)stream * SIS_STATS, sizeof(v), hipMemcpyDeviceToHost));
-    for (int k = 0; k < SIS_STATS; k++) stats[k] = (long long)v[k];
-    stats[SIS_STATS] = s->d2h;
-    return NRSC5HIP_OK;
+    return read_stats<SIS_STATS>(s->stats.p + (size_t)stream * SIS_STATS, s->ar.d2h, stats);
 }
 
 extern "C" int nrsc5hip_sis_get(nrsc5hip_sis *s, int stream, nrsc5hip_sis_info *out)
@@ -89,7 +70,7 @@ extern "C" int nrsc5hip_sis_get(nrsc5hip_sis *s, int stream, nrsc5hip_sis_info *
     if (!s || !out || stream < 0 || stream >= s->nstreams) FAIL(NRSC5HIP_EINVAL, "bad consumer / stream");
     nrsc5::DeviceGuard g(s->device);
     SisState st;
-    HIPCHK(hipMemcpy(&st, s->state + stream, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&st, s->state.p + stream, sizeof(st), hipMemcpyDeviceToHost));
     memset(out, 0, sizeof(*out));                               // report(), pids.c:284-383
     out->country_code[0] = (char)(st.cc & 0xff); out->country_code[1] = (char)((st.cc >> 8) & 0xff);
     out->fcc_facility_id = st.fcc;
@@ -115,7 +96,7 @@ extern "C" int nrsc5hip_sis_get(nrsc5hip_sis *s, int stream, nrsc5hip_sis_info *
 
 // The device work of one call and the delivery.  frame_of[k]: the frame index, within its stream's list, that entry k of `entries` reports as
 // (a reset-only entry never fires).  Nothing has been touched when this fails in front of the launch.
-static int sis_run(nrsc5hip_sis *s, std::vector<SisStream> &streams, const std::vector<SisFrame> &entries, const std::vector<int> &frame_of,
+static int sis_run(nrsc5hip_sis *s, std::vector<ArenaStream> &streams, const std::vector<SisFrame> &entries, const std::vector<int> &frame_of,
                    nrsc5hip_sis_cb cb, void *opaque)
 {
     const size_t ns = streams.size();
@@ -123,62 +104,21 @@ static int sis_run(nrsc5hip_sis *s, std::vector<SisStream> &streams, const std::
     // the arena, from what the host knows: a payload fires at most one event and adds at most 7 text bytes to what a later event can carry, a
     // frame has two payloads and may time the alert out; what the states hold already (56 + 190 + 15 + 95 + 381 bytes of text) can fire once
     size_t bound = 0;
-    for (const SisStream &st : streams) bound += (size_t)st.count * 3 * (sizeof(SisEvent) + 8) + 5 * sizeof(SisEvent) + 1024;
+    for (const ArenaStream &st : streams) bound += (size_t)st.count * 3 * (sizeof(SisEvent) + 8) + 5 * sizeof(SisEvent) + 1024;
     if (bound > 0xfffffff0u) FAIL(NRSC5HIP_EINVAL, "too many frames for one call");
     const size_t arena_cap = s->arena_limit ? std::min<size_t>(bound, (size_t)s->arena_limit) : bound;
-    const size_t plan_streams = ns * sizeof(SisStream), plan_bytes = plan_streams + entries.size() * sizeof(SisFrame);
-    int rc;
-    if ((rc = sis_need(&s->plan, &s->plan_cap, plan_bytes)) || (rc = sis_need(&s->arena, &s->arena_cap, sizeof(SisArenaHdr) + arena_cap))) return rc;
-    std::vector<uint8_t> plan(plan_bytes);
-    memcpy(plan.data(), streams.data(), plan_streams);
-    memcpy(plan.data() + plan_streams, entries.data(), entries.size() * sizeof(SisFrame));
-    HIPCHK(hipMemcpy(s->plan, plan.data(), plan_bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(s->arena, 0, sizeof(SisArenaHdr)));
-    SisArgs a;
-    a.streams = (const SisStream *)s->plan; a.frames = (const SisFrame *)((const uint8_t *)s->plan + plan_streams); a.nentries = (int)entries.size();
-    a.state = s->state; a.stats = s->stats; a.nstreams = s->nstreams;
-    a.hdr = (SisArenaHdr *)s->arena; a.arena = (uint8_t *)s->arena + sizeof(SisArenaHdr); a.arena_cap = (unsigned)arena_cap;
-    launch_sis(a, (int)ns, nullptr);
-    HIPCHK(hipGetLastError());
-    SisArenaHdr hdr;
-    HIPCHK(hipMemcpy(&hdr, s->arena, sizeof(hdr), hipMemcpyDeviceToHost));
-    s->d2h += (long long)sizeof(hdr);
-    if (hdr.overflow || hdr.used > arena_cap) FAIL(NRSC5HIP_EOVERFLOW, "event arena of %zu bytes too small (%u needed): events of this call are lost", arena_cap, hdr.used);
-    if (hdr.used == 0) return 0;
-    std::vector<uint8_t> got(hdr.used);
-    HIPCHK(hipMemcpy(got.data(), a.arena, hdr.used, hipMemcpyDeviceToHost));
-    s->d2h += hdr.used;
-    // all of the first listed stream's events first: the arena holds each stream's events in order, the streams interleaved
-    std::vector<std::vector<size_t>> per(ns);
-    for (size_t at = 0; at + sizeof(SisEvent) <= got.size();) {
-        SisEvent ev;
-        memcpy(&ev, got.data() + at, sizeof(ev));
-        const size_t rec = sizeof(SisEvent) + (((size_t)ev.len + 3) & ~(size_t)3);
-        if (ev.pos >= ns || at + rec > got.size() || ev.entry >= (unsigned)streams[ev.pos].count) FAIL(NRSC5HIP_EHIP, "event arena is not what k_sis writes (offset %zu)", at);
-        per[ev.pos].push_back(at);
-        at += rec;
-    }
-    int delivered = 0;
-    for (size_t i = 0; i < ns; i++)
-        for (size_t at : per[i]) {
-            SisEvent ev;
-            memcpy(&ev, got.data() + at, sizeof(ev));
-            if (cb) cb(opaque, streams[i].target, frame_of[(size_t)streams[i].first + ev.entry], ev.kind, ev.v, ev.enc, got.data() + at + sizeof(SisEvent), ev.len);
-            delivered++;
-        }
-    return delivered;
-}
-
-static int sis_targets(nrsc5hip_sis *s, int nstreams, const int *targets)
-{
-    std::vector<char> seen((size_t)s->nstreams, 0);
-    for (int i = 0; i < nstreams; i++) {
-        const int t = targets ? targets[i] : i;
-        if (t < 0 || t >= s->nstreams) FAIL(NRSC5HIP_EINVAL, "consumer stream %d out of range", t);
-        if (seen[t]) FAIL(NRSC5HIP_EINVAL, "consumer stream %d listed twice", t);      // two workgroups would walk one state
-        seen[t] = 1;
-    }
-    return 0;
+    auto launch = [&](const ArenaDev &d) {
+        SisArgs a;
+        a.streams = d.streams; a.frames = (const SisFrame *)d.jobs; a.nentries = (int)entries.size();
+        a.state = s->state.p; a.stats = s->stats.p; a.nstreams = s->nstreams;
+        a.hdr = d.hdr; a.arena = d.arena; a.arena_cap = d.cap;
+        launch_sis(a, (int)ns, nullptr);
+    };
+    return arena_round<SisEvent>(s->ar, nullptr, "event", "k_sis", streams, entries.data(), entries.size() * sizeof(SisFrame), arena_cap, launch,
+                                 [&](const SisEvent &ev) { return ev.entry < (unsigned)streams[ev.pos].count; },
+                                 [&](const ArenaStream &st, const SisEvent &ev, const uint8_t *data) {
+                                     if (cb) cb(opaque, st.target, frame_of[(size_t)st.first + ev.entry], ev.kind, ev.v, ev.enc, data, ev.len);
+                                 });
 }
 
 extern "C" int nrsc5hip_sis_feed(nrsc5hip_sis *s, int nstreams, const int *targets, const nrsc5hip_record *const *records, const int *counts,
@@ -188,14 +128,14 @@ extern "C" int nrsc5hip_sis_feed(nrsc5hip_sis *s, int nstreams, const int *targe
     if (nstreams == 0) return 0;
     if (!records || !counts) FAIL(NRSC5HIP_EINVAL, "null argument");
     nrsc5::DeviceGuard g(s->device);
-    int rc = sis_targets(s, nstreams, targets); if (rc) return rc;
+    int rc = check_targets(s->nstreams, nstreams, targets); if (rc) return rc;
     size_t total = 0;
     for (int i = 0; i < nstreams; i++) {
         if (counts[i] < 0 || (counts[i] > 0 && !records[i])) FAIL(NRSC5HIP_EINVAL, "records of stream %d of the call missing", i);
         total += (size_t)counts[i];
     }
     if (total > (size_t)INT32_MAX / 4) FAIL(NRSC5HIP_EINVAL, "too many records for one call");
-    std::vector<SisStream> streams;
+    std::vector<ArenaStream> streams;
     std::vector<SisFrame> entries;
     std::vector<int> frame_of;
     entries.reserve(total); frame_of.reserve(total);
@@ -213,7 +153,7 @@ extern "C" int nrsc5hip_sis_feed(nrsc5hip_sis *s, int nstreams, const int *targe
             frame_of.push_back(nf);
             if (pids) nf++;
         }
-        if ((int)entries.size() > first) streams.push_back(SisStream{targets ? targets[i] : i, first, (int)entries.size() - first, (int)streams.size()});
+        if ((int)entries.size() > first) streams.push_back(ArenaStream{targets ? targets[i] : i, first, (int)entries.size() - first, (int)streams.size()});
     }
     return sis_run(s, streams, entries, frame_of, cb, opaque);
 }
@@ -223,7 +163,7 @@ extern "C" int nrsc5hip_stage_sis(nrsc5hip_sis *s, int nstreams, const int *targ
 {
     if (!s || nstreams < 1 || !frames || !nframes) FAIL(NRSC5HIP_EINVAL, "bad argument");
     nrsc5::DeviceGuard g(s->device);
-    int rc = sis_targets(s, nstreams, targets); if (rc) return rc;
+    int rc = check_targets(s->nstreams, nstreams, targets); if (rc) return rc;
     size_t total = 0;
     for (int i = 0; i < nstreams; i++) {
         if (nframes[i] < 0 || (nframes[i] > 0 && !frames[i])) FAIL(NRSC5HIP_EINVAL, "stream %d of the call: frames missing", i);
@@ -231,7 +171,7 @@ extern "C" int nrsc5hip_stage_sis(nrsc5hip_sis *s, int nstreams, const int *targ
         total += (size_t)nframes[i] + 1;
     }
     if (total > (size_t)INT32_MAX / 4) FAIL(NRSC5HIP_EINVAL, "too many frames for one call");
-    std::vector<SisStream> streams;
+    std::vector<ArenaStream> streams;
     std::vector<SisFrame> entries;
     std::vector<int> frame_of;
     for (int i = 0; i < nstreams; i++) {
@@ -243,7 +183,7 @@ extern "C" int nrsc5hip_stage_sis(nrsc5hip_sis *s, int nstreams, const int *targ
             frame_of.push_back(f);
         }
         if (rst >= 0 && rst == nframes[i]) { entries.push_back(SisFrame{{0u, 0u, 0u}, 3u}); frame_of.push_back(nframes[i]); }   // as a REC_TO_FINE record without a frame
-        if ((int)entries.size() > first) streams.push_back(SisStream{targets ? targets[i] : i, first, (int)entries.size() - first, (int)streams.size()});
+        if ((int)entries.size() > first) streams.push_back(ArenaStream{targets ? targets[i] : i, first, (int)entries.size() - first, (int)streams.size()});
     }
     return sis_run(s, streams, entries, frame_of, cb, opaque);
 }

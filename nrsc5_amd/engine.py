@@ -17,93 +17,10 @@ if _AB_LIB:
     print(f"nrsc5_amd.engine: NRSC5HIP_AB_LIB={_AB_LIB}: running a library that is NOT built from this tree (A/B measurement)", file=_sys.stderr)
     DEFAULT_LIB = _AB_LIB
 
-SYNC_NONE, SYNC_COARSE, SYNC_FINE = 0, 1, 2
-REC_PROCESSED, REC_TO_COARSE, REC_TO_FINE, REC_MER, REC_PIDS, REC_P1 = 1, 2, 4, 8, 16, 32
-REC_P3, REC_P4 = 128, 256
-REC_LOST_SYNC = 64
-REC_PIDS_CRC = 512
-REC_DISCARDED = 1024      # never delivered by drain / batch_fetch* (replay, k_replay.hip)
-PX_WORDS = 144
-MODE_FM, MODE_AM = 0, 1
-AM_P1_BITS, AM_P1_WORDS, AM_P3_WORD0 = 3750, 118, 944
-P1_BITS, P1_WORDS, PIDS_BITS = 146176, 4568, 80
-
-RECORD_DTYPE = np.dtype([
-    ("flags", "<u4"), ("state_before", "<i4"), ("state_after", "<i4"), ("samperr", "<i4"), ("cfo", "<i4"),
-    ("keep", "<i4"), ("bc", "<i4"), ("psmi", "<i4"), ("cfo_wait", "<i4"), ("next_samperr", "<i4"),
-    ("prev_angle", "<f4"), ("phase_re", "<f4"), ("phase_im", "<f4"), ("next_angle", "<f4"),
-    ("freq_offset", "<f4"), ("mer_lb", "<f4"), ("mer_ub", "<f4"), ("ber", "<f4"),
-    ("p1_slot", "<i4"), ("bc_decoded", "<i4"), ("pids", "<u4", (3,)), ("sis", "<u4")])
-assert RECORD_DTYPE.itemsize == 96
-
-
-class _Config(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int), ("max_streams", ctypes.c_int), ("q15_capacity", ctypes.c_longlong),
-                ("record_capacity", ctypes.c_int), ("p1_slots", ctypes.c_int), ("p1_async", ctypes.c_int),
-                ("l2_feedback", ctypes.c_int), ("am_enable", ctypes.c_int), ("batch_zero_copy", ctypes.c_int), ("l2_index", ctypes.c_int)]
-
-
-class L2Pdu(ctypes.Structure):
-    """nrsc5hip_l2_pdu (include/nrsc5hip.h)"""
-    _fields_ = ([("start", ctypes.c_uint32), ("psd_off", ctypes.c_uint32), ("psd_len", ctypes.c_int32), ("audio_off", ctypes.c_uint32),
-                 ("crc_bad_lo", ctypes.c_uint32), ("crc_bad_hi", ctypes.c_uint32), ("pdu_marker", ctypes.c_uint32),
-                 ("hef_pdu_len", ctypes.c_uint16), ("loc", ctypes.c_uint16 * 64)] +
-                [(n, ctypes.c_uint8) for n in ("codec_mode", "stream_id", "pdu_seq", "blend_control", "per_stream_delay", "common_delay",
-                                               "latency", "pfirst", "plast", "seq", "nop", "hef", "la_location", "rs_corrections",
-                                               "class_ind", "prog_num", "access", "prog_type", "applied_services", "elastic_seq",
-                                               "align_offset", "skipped")])
-
-
-class L2Frame(ctypes.Structure):
-    """nrsc5hip_l2_frame"""
-    _fields_ = [("pci", ctypes.c_uint32), ("nbytes", ctypes.c_uint32), ("n_pdu", ctypes.c_uint32), ("status", ctypes.c_uint32),
-                ("end_offset", ctypes.c_uint32), ("lost_sync", ctypes.c_uint32), ("pdu", L2Pdu * 16)]
-
-
-class L2Job(ctypes.Structure):
-    """nrsc5hip_l2_job"""
-    _fields_ = [("stream", ctypes.c_int32), ("slot", ctypes.c_int32), ("kind", ctypes.c_int32), ("which", ctypes.c_int32),
-                ("nbits", ctypes.c_int32)]
-
-
-class _ChanConfig(ctypes.Structure):
-    """nrsc5hip_chan_config"""
-    _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("nchan", ctypes.c_int), ("rate_num", ctypes.c_longlong),
-                ("rate_den", ctypes.c_longlong), ("offset_hz", ctypes.c_void_p), ("gain", ctypes.c_void_p)]
-
-
-class _ScanConfig(ctypes.Structure):
-    """nrsc5hip_scan_config"""
-    _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("rate_num", ctypes.c_longlong), ("rate_den", ctypes.c_longlong),
-                ("nfft", ctypes.c_int)]
-
-
-class ScanParams(ctypes.Structure):
-    """nrsc5hip_scan_params"""
-    _fields_ = [("threshold_db", ctypes.c_double), ("min_separation_hz", ctypes.c_double)]
-
-
-class ScanStation(ctypes.Structure):
-    """nrsc5hip_scan_station"""
-    _fields_ = [("offset_hz", ctypes.c_double), ("score_db", ctypes.c_float), ("lower_db", ctypes.c_float), ("upper_db", ctypes.c_float),
-                ("floor_db", ctypes.c_float)]
-
-
-IQ_CU8, IQ_CS16, IQ_CF32 = 0, 1, 2
-IQ_FORMATS = {"cu8": IQ_CU8, "cs16": IQ_CS16, "cf32": IQ_CF32}
-IQ_DTYPES = {IQ_CU8: np.uint8, IQ_CS16: np.int16, IQ_CF32: np.float32}
-EINVAL, ENOMEM, EHIP, EOVERFLOW = -1, -2, -3, -4
-TRIM_RETAIN_MAX = (8 * 16 + 1) * 71280      # NRSC5HIP_TRIM_RETAIN_MAX: what Engine.batch_trim can retain per FM stream (pipeline depth, include/nrsc5hip.h)
-TRIM_RETAIN_MAX_AM = (8 * 8 + 1) * 8910     # NRSC5HIP_TRIM_RETAIN_MAX_AM: ... per AM stream
-
-L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
-TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
-MATH_REF_SINCOSF, MATH_REF_ATAN2F, MATH_FAST_SINCOS, MATH_FAST_SINCOS_REDUCED, MATH_FAST_ATAN2, MATH_SMALL_COS_SIN, MATH_SMALL_ATAN = range(7)   # NRSC5HIP_MATH_*
-HB_ACQ, HB_SYM128, HB_SYM256 = range(3)     # NRSC5HIP_HB_*: the forms of the fused half-band (csrc/halfband_raw.h)
-CODE_E1, CODE_E2 = 1, 2                     # NRSC5HIP_CODE_*: the two K=9 codes of the AM path
-HB_SYM_N = 2160                             # decimated samples of one symbol
-ACQ_WIN_FM, ACQ_SYM_FM, ACQ_WIN_AM, ACQ_SYM_AM = 71280, 2160, 8910, 270   # acquisition window (33 symbols) and symbol, FM / AM
-L2_STATUS = ("end", "no_audio", "fixed_data", "header_rs", "bad_locators", "too_many_pdus", "hef_overrun", "bad_stream", "bad_length", "audio_end")
+from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
+from .abi import _Config, _ChanConfig, _ScanConfig
+from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
+                        sis_utf8, sis_text, _sis_device_info, sis_event_fields)
 
 
 def l2_frame_to_dict(fr: L2Frame) -> dict:
@@ -115,35 +32,6 @@ def l2_frame_to_dict(fr: L2Frame) -> dict:
         d["loc"] = [int(x) for x in p.loc[:p.nop]]
         out["pdus"].append(d)
     return out
-
-
-HDC_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint, ctypes.c_uint)
-AAS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)   # nrsc5hip_aas_cb
-PSD_STATS = ("pdus", "span_bytes", "closed", "empty", "bad_fcs", "wrong_protocol", "truncated_escape", "overflows", "delivered", "d2h_bytes")   # nrsc5hip_psd_stats
-
-
-SIS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
-                          ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)                                     # nrsc5hip_sis_cb
-SIS_KINDS = (None, "station_id", "station_name", "station_slogan", "station_message", "station_location", "audio_service", "data_service", "alert",
-             "leap_second", "local_time", "exciter", "importer")                                         # NRSC5HIP_SIS_*
-SIS_STATS = (("frames", "crc_good", "sis", "llds") + tuple("id%d" % k for k in range(16)) +
-             ("unknown_id", "no_room", "never_complete_message", "never_complete_slogan", "never_complete_alert", "bad_checksum", "bad_crc7",
-              "bad_cnt_len", "bad_cnt_crc", "events", "d2h_bytes"))                                       # nrsc5hip_sis_stats
-SIS_EVENT_HEADER = 48                    # bytes of an event in the arena in front of its text (padded to 4); the arena header is 16
-
-
-class SisInfo(ctypes.Structure):         # nrsc5hip_sis_info
-    _fields_ = [("country_code", ctypes.c_char * 4), ("fcc_facility_id", ctypes.c_int32),
-                ("name_enc", ctypes.c_int32), ("name_len", ctypes.c_int32), ("name", ctypes.c_uint8 * 16),
-                ("slogan_enc", ctypes.c_int32), ("slogan_len", ctypes.c_int32), ("slogan", ctypes.c_uint8 * 96),
-                ("message_enc", ctypes.c_int32), ("message_len", ctypes.c_int32), ("message", ctypes.c_uint8 * 192),
-                ("alert_enc", ctypes.c_int32), ("alert_len", ctypes.c_int32), ("alert_cnt_len", ctypes.c_int32), ("alert", ctypes.c_uint8 * 384),
-                ("have_location", ctypes.c_int32), ("latitude", ctypes.c_int32), ("longitude", ctypes.c_int32), ("altitude", ctypes.c_int32),
-                ("n_audio", ctypes.c_int32), ("audio", (ctypes.c_int32 * 4) * 8), ("n_data", ctypes.c_int32), ("data", (ctypes.c_int32 * 3) * 16)]
-
-
-class Nrsc5HipError(RuntimeError):
-    pass
 
 
 def load_library(path: str | None = None) -> ctypes.CDLL:
@@ -1022,361 +910,6 @@ class Scanner:
         self._check(self.lib.nrsc5hip_scan_detect(self._h, ctypes.byref(ScanParams(threshold_db, min_separation_hz)), ctypes.addressof(out),
                                                   max_stations, ctypes.byref(n)))
         return _stations(out, min(n.value, max_stations))
-
-
-class HdcConsumer:
-    """Slim batch consumer of the L2 index (nrsc5hip_hdc_*): elastic buffers of `nstreams` streams in ~40 KB each instead of
-    one nrsc5_t per stream; delivers the reference's NRSC5_EVENT_HDC sequence."""
-
-    def __init__(self, nstreams: int, lib: ctypes.CDLL | None = None, lib_path: str | None = None):
-        self.lib = lib or load_library(lib_path)
-        self._h = ctypes.c_void_p()
-        if self.lib.nrsc5hip_hdc_create(nstreams, ctypes.byref(self._h)) != 0:
-            raise Nrsc5HipError("nrsc5hip_hdc_create failed")
-        self.events = []
-        self._cb = HDC_CB(self._on_packet)
-
-    def _on_packet(self, opaque, stream, program, data, count, flags):
-        self.events.append((int(stream), int(program), int(count), int(flags), bytes(ctypes.string_at(data, count)) if count else b""))
-
-    def push_frame(self, stream: int, frame: L2Frame, pdu_bytes: np.ndarray, lc: int = 0):
-        b = np.ascontiguousarray(pdu_bytes, dtype=np.uint8)
-        if self.lib.nrsc5hip_hdc_push_frame(self._h, stream, lc, ctypes.byref(frame), b.ctypes.data) != 0:
-            raise Nrsc5HipError("nrsc5hip_hdc_push_frame failed")
-
-    def fixed_audio_end(self, stream: int, lc: int, pdu_bytes: np.ndarray) -> int:
-        b = np.ascontiguousarray(pdu_bytes, dtype=np.uint8)
-        return int(self.lib.nrsc5hip_hdc_fixed_audio_end(self._h, stream, lc, b.ctypes.data, b.size))
-
-    def frame_reset(self, stream: int):
-        self.lib.nrsc5hip_hdc_frame_reset(self._h, stream)
-
-    def advance(self, stream: int, mode: int = MODE_FM) -> int:
-        return self.lib.nrsc5hip_hdc_advance(self._h, stream, mode, self._cb, None)
-
-    def reset(self, stream: int):
-        self.lib.nrsc5hip_hdc_reset(self._h, stream)
-
-    def host_bytes(self) -> int:
-        return int(self.lib.nrsc5hip_hdc_host_bytes(self._h))
-
-    def adts(self, data: bytes) -> bytes:
-        out = (ctypes.c_uint8 * (len(data) + 7))()
-        src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
-        n = self.lib.nrsc5hip_hdc_adts(src, len(data), out)
-        return bytes(out[:n])
-
-    def close(self):
-        if self._h:
-            self.lib.nrsc5hip_hdc_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def feed_hdc(engine: Engine, consumer: HdcConsumer, stream: int, recs: np.ndarray, mode: int = MODE_FM, target_stream: int | None = None):
-    """Replays one stream's block records into the consumer in the reference's order: output_advance at the top of every
-    processed block (acquire.c:108), then the frames that block delivers (frame_push -> frame_process)."""
-    t = stream if target_stream is None else target_stream
-    jobs_all = []
-    per_rec = []
-    for r in recs:
-        jobs = l2_jobs_from_records(stream, np.array([r], dtype=RECORD_DTYPE), mode)
-        per_rec.append((len(jobs_all), len(jobs)))
-        jobs_all += jobs
-    frames, by = engine.l2_index_raw(jobs_all) if jobs_all else (None, None)
-    for r, (first, n) in zip(recs, per_rec):
-        if int(r["flags"]) & REC_PROCESSED:
-            consumer.advance(t, mode)
-        if int(r["flags"]) & REC_TO_FINE:
-            consumer.frame_reset(t)                              # sync.c:405-409
-        for k in range(first, first + n):
-            kind, which = jobs_all[k][2], jobs_all[k][3]
-            lc = 0 if kind == L2_FM_P1 or (kind == L2_AM and which < 8) else (1 + which if kind == L2_FM_PX else 1)
-            consumer.push_frame(t, frames[k], by[k, :frames[k].nbytes], lc)
-
-
-def feed_hdc_batch(engine: Engine, consumer: HdcConsumer, stream_ids, recs_per_stream, mode: int = MODE_FM, targets=None) -> int:
-    """nrsc5hip_hdc_feed: what feed_hdc does, for many streams in one native call -- one L2 index launch and one copy for all their
-    frames, no Python per record.  recs_per_stream[i]: the RECORD_DTYPE array of engine stream stream_ids[i] (drained since the last
-    call; may be empty); targets[i]: the consumer's stream for it (None: the same ids).  The packets land in consumer.events, all of
-    stream_ids[0] first; -> how many.  Call it while the ring slots the records name still hold their frames."""
-    ids = np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
-    tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-    n = int(ids.size)
-    if len(recs_per_stream) != n or (tg is not None and tg.size != n):
-        raise ValueError("stream_ids, recs_per_stream and targets must have one entry per stream")
-    arrs = [None if r is None else np.ascontiguousarray(r, dtype=RECORD_DTYPE) for r in recs_per_stream]       # kept alive over the call
-    ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None or a.size == 0 else a.ctypes.data for a in arrs])
-    counts = np.array([0 if a is None else a.size for a in arrs], dtype=np.int32)
-    rc = consumer.lib.nrsc5hip_hdc_feed(consumer._h, engine._h, n, ids.ctypes.data, None if tg is None else tg.ctypes.data, ptrs,
-                                        counts.ctypes.data, mode, consumer._cb, None)
-    if rc < 0:
-        err = Nrsc5HipError(f"nrsc5hip_hdc_feed failed ({rc}): {consumer.lib.nrsc5hip_last_error().decode()}")
-        err.code = rc
-        raise err
-    return rc
-
-
-class PsdConsumer:
-    """PSD transport on the device (nrsc5hip_psd_*): HDLC de-framing of the PSD spans of `nstreams` streams in HBM; only finished AAS
-    packets reach the host.  They land in `packets` as (stream, program, port, seq, data), data = what follows port and seq."""
-
-    def __init__(self, engine: "Engine", nstreams: int):
-        self.lib = engine.lib
-        self._engine = engine                                    # the consumer's device buffers live on the engine's device: keep it alive
-        self._h = ctypes.c_void_p()
-        rc = self.lib.nrsc5hip_psd_create(engine._h, nstreams, ctypes.byref(self._h))
-        if rc != 0:
-            raise Nrsc5HipError(f"nrsc5hip_psd_create failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
-        self.nstreams = nstreams
-        self.packets = []
-        self._cb = AAS_CB(self._on_packet)
-
-    def _on_packet(self, opaque, stream, program, port, seq, data, n):
-        self.packets.append((int(stream), int(program), int(port), int(seq), bytes(ctypes.string_at(data, n)) if n else b""))
-
-    def _result(self, rc: int, what: str) -> int:
-        if rc < 0:
-            err = Nrsc5HipError(f"{what} failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
-            err.code = rc
-            raise err
-        return rc
-
-    def reset(self, stream: int):
-        self._result(self.lib.nrsc5hip_psd_reset(self._h, stream), "nrsc5hip_psd_reset")
-
-    def stats(self, stream: int) -> dict:
-        v = (ctypes.c_longlong * 10)()
-        self._result(self.lib.nrsc5hip_psd_stats(self._h, stream, v), "nrsc5hip_psd_stats")
-        return dict(zip(PSD_STATS, (int(x) for x in v)))
-
-    def stage(self, stream: int, frames_bits: np.ndarray, lc: int = 0) -> int:
-        """nrsc5hip_stage_psd: frames as frame_push takes them ([nframes, nbits], one bit per byte), in order; -> packets delivered"""
-        b = np.ascontiguousarray(frames_bits, dtype=np.uint8)
-        if b.ndim == 1:
-            b = b[None, :]
-        return self._result(self.lib.nrsc5hip_stage_psd(self._h, self._engine._h, stream, b.ctypes.data, b.shape[1], b.shape[0], lc, self._cb, None),
-                            "nrsc5hip_stage_psd")
-
-    def stage_streams(self, targets, frames_per_stream, lcs, reset_at=None) -> list:
-        """nrsc5hip_stage_psd_streams: frames_per_stream[i] ([nframes, nbits] bits) go to consumer stream targets[i], all in one call (one k_psd
-        workgroup per stream); reset_at[i]: the frame in front of which the stream gets a REC_TO_FINE reset (None / negative: none).
-        -> the packets of this call, all of targets[0] first"""
-        n = len(targets)
-        arrs = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_per_stream]
-        arrs = [a[None, :] if a.ndim == 1 else a for a in arrs]
-        i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
-        tg, nb, nf, lc = i32(targets), i32([a.shape[1] for a in arrs]), i32([a.shape[0] for a in arrs]), i32(lcs)
-        rs = None if reset_at is None else i32([-1 if r is None else r for r in reset_at])
-        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
-        first = len(self.packets)
-        rc = self._result(self.lib.nrsc5hip_stage_psd_streams(self._h, self._engine._h, n, tg.ctypes.data, ptrs, nb.ctypes.data, nf.ctypes.data, lc.ctypes.data,
-                                                              None if rs is None else rs.ctypes.data, self._cb, None), "nrsc5hip_stage_psd_streams")
-        out = self.packets[first:]
-        assert rc == len(out)
-        return out
-
-    def close(self):
-        if self._h:
-            self.lib.nrsc5hip_psd_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def feed_psd_batch(engine: Engine, consumer: PsdConsumer, stream_ids, recs_per_stream, targets=None, mode: int = MODE_FM) -> list:
-    """nrsc5hip_psd_feed: the records of many streams (as for feed_hdc_batch) replayed into the PSD consumer in one native call -- one
-    index launch, one k_psd launch, one copy of the finished packets.  -> [(stream, program, port, seq, data)] of this call, all of
-    stream_ids[0] first (they are appended to consumer.packets as well).  Call it while the ring slots the records name hold their frames."""
-    ids = np.ascontiguousarray(stream_ids, dtype=np.int32).reshape(-1)
-    tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-    n = int(ids.size)
-    if len(recs_per_stream) != n or (tg is not None and tg.size != n):
-        raise ValueError("stream_ids, recs_per_stream and targets must have one entry per stream")
-    arrs = [None if r is None else np.ascontiguousarray(r, dtype=RECORD_DTYPE) for r in recs_per_stream]       # kept alive over the call
-    ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None or a.size == 0 else a.ctypes.data for a in arrs])
-    counts = np.array([0 if a is None else a.size for a in arrs], dtype=np.int32)
-    first = len(consumer.packets)
-    rc = consumer._result(consumer.lib.nrsc5hip_psd_feed(consumer._h, engine._h, n, ids.ctypes.data, None if tg is None else tg.ctypes.data, ptrs,
-                                                         counts.ctypes.data, mode, consumer._cb, None), "nrsc5hip_psd_feed")
-    out = consumer.packets[first:]
-    assert rc == len(out)
-    return out
-
-
-def sis_utf8(enc: int, data: bytes) -> bytes | None:
-    """The C string the reference reports for `data` in encoding `enc` (utf8_encode, pids.c:272-282; unicode.c): 0 = ISO-8859-1, 4 = UCS-2 with an
-    optional byte-order mark (little endian without one; an odd last byte is dropped); any other encoding gives None (a NULL string).  The result is
-    cut at its first NUL, as a C string is.  (UCS-2 of length 0 is "": the reference's loop bound wraps there.)"""
-    data = bytes(data)
-    if enc == 0:
-        out = data.decode("latin-1").encode("utf-8")
-    elif enc == 4:
-        big = data[:2] == b"\xfe\xff"
-        body = data[2:] if data[:2] in (b"\xfe\xff", b"\xff\xfe") else data
-        body = body[:len(body) - len(body) % 2]
-        out = bytearray()
-        for k in range(0, len(body), 2):
-            ch = (body[k] << 8 | body[k + 1]) if big else (body[k] | body[k + 1] << 8)
-            if ch < 0x80:
-                out.append(ch)
-            elif ch < 0x800:
-                out += bytes((0xc0 | ch >> 6, 0x80 | ch & 0x3f))
-            else:
-                out += bytes((0xe0 | ch >> 12, 0x80 | (ch >> 6) & 0x3f, 0x80 | ch & 0x3f))     # (surrogates too: the reference does not pair them)
-        out = bytes(out)
-    else:
-        return None
-    return out.split(b"\0", 1)[0]
-
-
-def sis_text(enc: int, data: bytes) -> str | None:
-    raw = sis_utf8(enc, data)
-    return None if raw is None else raw.decode("utf-8", errors="replace")
-
-
-def _sis_device_info(p) -> dict:
-    """manufacturer id, versions and status of parameters 4..7 / 8..11 (pids.c:698-744)"""
-    ver = lambda a, b: [(a >> 11) & 0x1f, (a >> 6) & 0x1f, (a >> 1) & 0x1f, b]
-    return {"manufacturer_id": bytes(((p[0] >> 8) & 0x7f, p[0] & 0x7f)).split(b"\0", 1)[0].decode("latin-1"),
-            "core_version": ver(p[1], (p[3] >> 11) & 0x1f), "manufacturer_version": ver(p[2], (p[3] >> 6) & 0x1f),
-            "core_status": (p[3] >> 3) & 7, "manufacturer_status": p[3] & 7}
-
-
-def sis_event_fields(kind: str, v, enc: int, data: bytes) -> dict:
-    """An event of k_sis as the fields the reference's callback reports; text as sis_text gives it (None: an encoding the reference cannot convert)"""
-    if kind == "station_id":
-        return {"country": data.decode("latin-1"), "fcc": v[0]}
-    if kind == "station_name":
-        return {"name": sis_text(enc, data)}
-    if kind == "station_slogan":
-        return {"slogan": sis_text(enc, data)}
-    if kind == "station_message":
-        return {"message": sis_text(enc, data), "priority": v[0]}
-    if kind == "station_location":
-        return {"latitude": float(np.float32(v[0]) / np.float32(8192)), "longitude": float(np.float32(v[1]) / np.float32(8192)), "altitude": v[2]}
-    if kind == "audio_service":
-        return {"program": v[0], "access": v[1], "type": v[2], "sound_exp": v[3]}
-    if kind == "data_service":
-        return {"access": v[0], "type": v[1], "mime_type": v[2]}
-    if kind == "alert":
-        if v[0] < 0:
-            return {"message": None, "control_data": None}
-        return {"message": sis_text(enc, data[v[0]:]), "control_data": data[:v[0]]}
-    if kind == "leap_second":
-        return {"pending_offset": v[0], "current_offset": v[1], "pending_alfn": v[2] & 0xffffffff}
-    if kind == "local_time":
-        return {"utc_offset": v[0], "dst_regional": v[1], "dst_local": v[2], "dst_schedule": v[3]}
-    if kind == "exciter":
-        return {**_sis_device_info(v), "importer_connected": (v[0] >> 7) & 1}
-    if kind == "importer":
-        return _sis_device_info(v)
-    raise ValueError(kind)
-
-
-class SisConsumer:
-    """SIS on the device (nrsc5hip_sis_*): pids_frame_push / sis_decode over the PIDS frames of `nstreams` streams, their state in HBM; only
-    events reach the host.  They land in `events` as (stream, frame, kind, fields) -- frame: index of the firing frame in the stream's list of
-    that call -- and, raw, in `raw` as (stream, frame, kind, v[8], enc, data)."""
-
-    def __init__(self, engine: "Engine", nstreams: int):
-        self.lib = engine.lib
-        self._engine = engine                                    # the consumer's device buffers live on the engine's device: keep it alive
-        self._h = ctypes.c_void_p()
-        rc = self.lib.nrsc5hip_sis_create(engine._h, nstreams, ctypes.byref(self._h))
-        if rc != 0:
-            raise Nrsc5HipError(f"nrsc5hip_sis_create failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
-        self.nstreams = nstreams
-        self.events, self.raw = [], []
-        self._cb = SIS_CB(self._on_event)
-
-    def _on_event(self, opaque, stream, frame, kind, v, enc, data, n):
-        vals, body = [int(v[k]) for k in range(8)], bytes(ctypes.string_at(data, n)) if n else b""
-        name = SIS_KINDS[kind]
-        self.raw.append((int(stream), int(frame), name, vals, int(enc), body))
-        self.events.append((int(stream), int(frame), name, sis_event_fields(name, vals, int(enc), body)))
-
-    _result = PsdConsumer._result
-
-    def reset(self, stream: int):
-        self._result(self.lib.nrsc5hip_sis_reset(self._h, stream), "nrsc5hip_sis_reset")
-
-    def stats(self, stream: int) -> dict:
-        v = (ctypes.c_longlong * len(SIS_STATS))()
-        self._result(self.lib.nrsc5hip_sis_stats(self._h, stream, v), "nrsc5hip_sis_stats")
-        return dict(zip(SIS_STATS, (int(x) for x in v)))
-
-    def info(self, stream: int) -> dict:
-        """nrsc5hip_sis_get: the snapshot, i.e. what the reference's aggregated SIS event would hold"""
-        s = SisInfo()
-        self._result(self.lib.nrsc5hip_sis_get(self._h, stream, ctypes.byref(s)), "nrsc5hip_sis_get")
-        text = lambda enc, buf, n: None if n < 0 else sis_text(enc, bytes(buf[:n]))
-        return {"country": s.country_code.decode("latin-1") or None, "fcc": s.fcc_facility_id,
-                "name": text(s.name_enc, s.name, s.name_len), "slogan": text(s.slogan_enc, s.slogan, s.slogan_len),
-                "message": text(s.message_enc, s.message, s.message_len),
-                "alert": None if s.alert_len < 0 else sis_text(s.alert_enc, bytes(s.alert[s.alert_cnt_len:s.alert_len])),
-                "alert_control_data": None if s.alert_len < 0 else bytes(s.alert[:s.alert_cnt_len]),
-                "location": None if not s.have_location else (float(np.float32(s.latitude) / np.float32(8192)),
-                                                                float(np.float32(s.longitude) / np.float32(8192)), s.altitude),
-                "audio_services": [tuple(s.audio[k]) for k in range(s.n_audio)], "data_services": [tuple(s.data[k]) for k in range(s.n_data)]}
-
-    def debug_arena(self, nbytes: int):
-        self._result(self.lib.nrsc5hip_sis_debug_arena(self._h, nbytes), "nrsc5hip_sis_debug_arena")
-
-    def stage(self, targets, frames_per_stream, reset_at=None) -> list:
-        """nrsc5hip_stage_sis: frames_per_stream[i] ([nframes, 80] bits as handed to pids_frame_push; may be empty) go to consumer stream targets[i],
-        all in one call (one k_sis workgroup per stream); reset_at[i]: the frame in front of which the stream's state is reset (None / negative:
-        none; == nframes: behind the last).  -> the events of this call, all of targets[0] first"""
-        n = len(targets)
-        arrs = [np.ascontiguousarray(f, dtype=np.uint8).reshape(-1, 80) for f in frames_per_stream]
-        i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
-        tg, nf = i32(targets), i32([a.shape[0] for a in arrs])
-        rs = None if reset_at is None else i32([-1 if r is None else r for r in reset_at])
-        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-        first = len(self.events)
-        rc = self._result(self.lib.nrsc5hip_stage_sis(self._h, n, tg.ctypes.data, ptrs, nf.ctypes.data, None if rs is None else rs.ctypes.data, self._cb, None),
-                          "nrsc5hip_stage_sis")
-        out = self.events[first:]
-        assert rc == len(out)
-        return out
-
-    def close(self):
-        if self._h:
-            self.lib.nrsc5hip_sis_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def feed_sis_batch(sis: SisConsumer, targets, fresh) -> list:
-    """nrsc5hip_sis_feed: the records of many streams (fresh[i]: the RECORD_DTYPE array for consumer stream targets[i], FM or AM; may be empty or None)
-    in one native call -- one upload of 16 bytes per record, one k_sis launch, one copy of the events.  -> [(stream, frame, kind, fields)] of this
-    call, all of targets[0] first (they are appended to sis.events as well)."""
-    tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
-    n = int(tg.size)
-    if len(fresh) != n:
-        raise ValueError("targets and fresh must have one entry per stream")
-    arrs = [None if r is None else np.ascontiguousarray(r, dtype=RECORD_DTYPE) for r in fresh]       # kept alive over the call
-    ptrs = (ctypes.c_void_p * max(n, 1))(*[None if a is None or a.size == 0 else a.ctypes.data for a in arrs])
-    counts = np.array([0 if a is None else a.size for a in arrs], dtype=np.int32)
-    first = len(sis.events)
-    rc = sis._result(sis.lib.nrsc5hip_sis_feed(sis._h, n, tg.ctypes.data, ptrs, counts.ctypes.data, sis._cb, None), "nrsc5hip_sis_feed")
-    out = sis.events[first:]
-    assert rc == len(out)
-    return out
 
 
 def l2_jobs_from_records(stream: int, recs: np.ndarray, mode: int = 0):
