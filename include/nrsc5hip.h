@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 14   /* 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 15   /* 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -542,6 +542,101 @@ int nrsc5hip_stage_sis(nrsc5hip_sis *s, int nstreams, const int *targets, const 
 /* TEST HOOK, not for callers (tests/sis_checks.py provokes NRSC5HIP_EOVERFLOW with it): the event arena of the following calls holds at most
  * `bytes` (0: sized from the host-known bounds again) */
 int nrsc5hip_sis_debug_arena(nrsc5hip_sis *s, long long bytes);
+
+/* ---- Data services: the Station Information Guide and LOT files -- album art, station logos (device side: csrc/k_aas.hip) ------
+ * The AAS packets the PSD transport reassembles go, in the reference, to output_aas_push (output.c:874-896).  This consumer is chained
+ * behind the PSD consumer: k_aas reads the packet arena k_psd leaves in device memory, and only events are copied to the host.  Per
+ * consumer stream it keeps, in device memory, the SIG table (16 services x 8 components and the service names, 5.8 KB), lot_lru_counter
+ * and `lot_files` file slots (a descriptor of 336 bytes and 65 536 data bytes each).
+ * Routing (output.c:874-896): port 0x5100 / 0x5201..0x5207 -> a PSD event: the packet untouched (program, port, seq, data), for the ID3
+ * parser; port 0x20 -> SIG; ports 0x0401..0x50FF -> process_port; any other port is counted ([7]).
+ * SIG (parse_sig, output.c:512-625): processed while services[0] is empty, i.e. once per stream unless it yields no service.  Element
+ * 0x4x opens a service (audio iff the byte is 0x40; number: 16 bits; 3 bytes skipped; a number already in the table clears and reuses that
+ * slot, output.c:540-546; a 17th service ends the parse, :549-553).  Element 0x6x: a length byte l, then the value; 0x69 the name, l - 2
+ * bytes from p + 1 (:571-574); 0x67 a data component (id, port, service_data_type, type, mime at p + 8; :575-594); 0x66 an audio component
+ * (id, port, type, mime at p + 7; :595-613); an id already in the service overwrites its slot, a 9th component ends the parse
+ * (find_component, :493-510); a 0x6x in front of any service ends the parse (:566-570); p += l - 1 (:614).  Any other byte ends the parse
+ * (:617-619).  The SIG event is emitted at the end of the parse in every case (:623-624).
+ *   Deviations, each counted: every read is checked against the packet, and an element whose bytes (service number; length byte; name with
+ *   l < 2 or running past the packet; the 12 / 11 bytes of a component) do not lie inside it ends the parse ([4]); so does l == 0 ([5]).  The
+ *   reference reads past the packet, or walks backwards.  A SIG that yields no service emits an event with an empty table ([6]); the
+ *   reference hands out an uninitialised pointer.  A name of length 0 is reported as no name (the reference reports an empty string).
+ * process_port (output.c:684-872): a packet in front of the SIG is dropped ([8], :688-692); the port is looked up as the first data
+ * component with that port, in service order (find_port, :627-647); not found: counted ([9]).  Type 0: a STREAM event, type 1: a PACKET
+ * event (port, seq, mime, data; :703-714); type 3: LOT; any other type is counted ([12]).  HERE-image assembly (here_images.c) is not done:
+ * its stream packets are STREAM events like any other.
+ * LOT (output.c:715-866), in the reference's order: the packet is dropped ([14]) if len < 8 (:717), if hdrlen < 8 or hdrlen > len (:726), or
+ * if seq >= 256 (:735).  find_lot matches the lot among the component's live files (:649-659); otherwise find_free_lot takes the
+ * component's first free file or its least recently used of 12, the first of equals (:661-682).  The timestamp is taken from the counter
+ * before the header is looked at (:748), so a packet with 0 < hdrlen - 8 < 16 returns with the file allocated and stamped ([15], :754-758).
+ * Header: version, expiry (year - 1900, mon - 1, mday, hour, min from bytes 4..7, :764-768), size, mime; the name is the rest of the header,
+ * kept cut at its first NUL, and compared as "length sent != length kept, or the bytes differ" (strlen on the strndup copy, :779-780, 804).
+ * Changed metadata resets the file: its timestamp becomes the counter's current value and new_data is set ([17], :788-795).  LOT_HEADER is
+ * emitted iff the header set new_data (:817-822).  A new fragment with len > 256 leaves the packet without a store or an event ([20],
+ * :831-835); otherwise len bytes are stored at seq * 256, the remaining 256 - len zeroed, and len added to bytes_so_far (:830-838).  A
+ * LOT_FRAGMENT event follows for new and duplicate fragments alike (:840).  The completeness test runs iff new_data && size, over
+ * fragments 0 .. ceil(size / 256) - 1 (:843-854); the LOT event carries lot, size, mime, name, expiry and the first `size` bytes.
+ *   Deviations: size > 65 536 can never complete ([22]; the reference runs past its fragment array).  LOT_FRAGMENT events never carry the
+ *   fragment's bytes, and are written only with NRSC5HIP_AAS_FRAGMENTS; [18] and [19] count them in either case.  A component never
+ *   holds more than 12 live files, as in the reference ([23] counts its evictions); the slots behind them are a pool of `lot_files` per stream,
+ *   and when all are in use and a file is needed the stream's least recently stamped file is evicted (the lowest slot of equals) and [24] counts
+ *   it -- this can only happen when more files are live than the pool has slots, and never silently.
+ * Events, in the arena and through the callback: kind, port, seq, v[8], data --
+ *   PSD           port, seq, v[0] program; data: what follows port and seq
+ *   SIG           v[0] services; data, per service: type (1 data, 2 audio), number (16 bits, little endian), name length, the name (raw
+ *                 ISO-8859-1: the reference converts it to UTF-8), component count; per component: type (1 data, 2 audio), id, port (16 bits),
+ *                 service_data_type (16 bits), type, mime (32 bits) -- 11 bytes; an audio component has service_data_type 0
+ *   LOT_HEADER    port, v[0] lot, v[1] size, v[2] mime, v[3..7] tm_year, tm_mon, tm_mday, tm_hour, tm_min; data: the name
+ *   LOT_FRAGMENT  port, seq, v[0] lot, v[1] repeat, v[2] is_duplicate, v[3] size, v[4] bytes_so_far; no data
+ *   LOT           as LOT_HEADER, seq = the length of the name; data: the first `size` bytes of the file, then the name
+ *   STREAM / PACKET   port, seq, v[0] mime, v[1] service, v[2] component (indices into the table); data
+ * An event takes 48 bytes and its data, padded to 4, in the arena. */
+enum { NRSC5HIP_AAS_PSD = 1, NRSC5HIP_AAS_SIG, NRSC5HIP_AAS_LOT_HEADER, NRSC5HIP_AAS_LOT_FRAGMENT, NRSC5HIP_AAS_LOT, NRSC5HIP_AAS_STREAM, NRSC5HIP_AAS_PACKET };
+#define NRSC5HIP_AAS_FRAGMENTS 1       /* flags of nrsc5hip_aas_create: write LOT_FRAGMENT events */
+#define NRSC5HIP_AAS_NSTATS 27
+#define NRSC5HIP_AAS_SIG_MAX 5632      /* bytes a SIG table can take in the layout above: 16 x (5 + 253 + 8 x 11) */
+typedef struct nrsc5hip_aas nrsc5hip_aas;
+typedef void (*nrsc5hip_aas_event_cb)(void *opaque, int stream, int kind, unsigned port, unsigned seq, const int32_t v[8], const uint8_t *data, unsigned len);
+/* nstreams consumer streams on the engine's device, lot_files (1..64) file slots each; destroy the consumer before its engine */
+int nrsc5hip_aas_create(nrsc5hip_engine *e, int nstreams, int lot_files, int flags, nrsc5hip_aas **out);
+void nrsc5hip_aas_destroy(nrsc5hip_aas *a);
+int nrsc5hip_aas_reset(nrsc5hip_aas *a, int stream);                  /* aas_reset, output.c:182-202: table and files gone, the counter 1 */
+/* nrsc5hip_psd_feed with the data services chained behind it: the same records, lists, targets and rejections (a target must lie inside
+ * both consumers), the fixed-data cut on the host as there, and `psd` advances exactly as nrsc5hip_psd_feed would advance it -- but its
+ * packet arena is not copied back: ONE k_aas launch (a wave64 workgroup per listed stream) runs over it, and the header and the used part
+ * of the event arena come back.  Events are delivered through cb (may be NULL: count only) inside the call, all of stream_ids[0] first,
+ * each stream's in packet order and those of one packet in the reference's callback order: LOT_HEADER, LOT_FRAGMENT, LOT.  Returns the
+ * number of events or a negative error.  A NRSC5HIP_REC_TO_FINE record resets HDLC state only: the data-service state survives a resync,
+ * as output_t does in the reference.
+ * Device -> host per call: what nrsc5hip_psd_feed moves without its arena (4 bytes per frame; fixed-data frames as there), 16 bytes of
+ * arena header, and per event 48 bytes + its data padded to 4.  The bytes of a LOT fragment cross only inside a complete file.
+ * The event arena is sized from what the host knows: four times the packet arena (an event is at most four times its packet's record,
+ * whatever the packet turns into except a complete file or the SIG), and per listed stream 8 KB for the SIG and lot_files x (65 536 + 512)
+ * for complete files: every file slot may complete once per call.  NRSC5HIP_EOVERFLOW: the event arena, or the packet arena in front of
+ * it, was too small (never a silent drop); the states have advanced, the events of the call are lost. */
+int nrsc5hip_aas_feed(nrsc5hip_aas *a, nrsc5hip_psd *psd, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
+                      const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_aas_event_cb cb, void *opaque);
+/* Counters of one consumer stream since its creation: [0] packets, [1] PSD-port packets passed on, [2] SIG packets, [3] SIGs parsed,
+ * [4] parses ended by a truncated element, [5] by l == 0, [6] SIGs without a service, [7] unknown port range, [8] packets in front of the
+ * SIG, [9] port not in the table, [10] STREAM, [11] PACKET events, [12] unknown component type, [13] LOT packets, [14] dropped (len,
+ * hdrlen, seq), [15] header too short, [16] LOT_HEADER events, [17] files reset by changed metadata, [18] fragments (new and duplicate),
+ * [19] duplicates, [20] fragments over 256 bytes, [21] LOT events, [22] completeness tests of a size over 65 536, [23] evictions by the
+ * component's LRU, [24] by the pool, [25] events written; [26] bytes the feeds copied device -> host, total over the consumer (the PSD
+ * consumer in front counts its own). */
+int nrsc5hip_aas_stats(nrsc5hip_aas *a, int stream, long long stats[NRSC5HIP_AAS_NSTATS]);
+/* the stream's SIG table as a snapshot, in the layout of the SIG event's data (what that event held), for callers that joined late:
+ * out[NRSC5HIP_AAS_SIG_MAX], *len its bytes, *nservices 0 while no SIG has been seen */
+int nrsc5hip_aas_sig(nrsc5hip_aas *a, int stream, uint8_t *out, unsigned *len, int *nservices);
+/* stage hook, through the production kernel: AAS packets per consumer stream targets[i] (NULL: stream i) -- packets[i]: nbytes[i] bytes,
+ * packet after packet, each as four little-endian 16-bit words (port, seq, data length, program) and then its data -- uploaded as one
+ * PsdPacket arena, the streams interleaved packet by packet */
+int nrsc5hip_stage_aas(nrsc5hip_aas *a, int nstreams, const int *targets, const uint8_t *const *packets, const int *nbytes,
+                       nrsc5hip_aas_event_cb cb, void *opaque);
+/* stage hook of the chain, frames -> index -> k_psd -> k_aas: the arguments of nrsc5hip_stage_psd_streams */
+int nrsc5hip_stage_aas_frames(nrsc5hip_aas *a, nrsc5hip_psd *psd, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits,
+                              const int *nbits, const int *nframes, const int *lcs, const int *reset_at, nrsc5hip_aas_event_cb cb, void *opaque);
+/* TEST HOOK, not for callers: as nrsc5hip_sis_debug_arena, for the event arena */
+int nrsc5hip_aas_debug_arena(nrsc5hip_aas *a, long long bytes);
 
 /* ---- stage-level entry points (host buffers): parity tests of single kernels against the oracle ---- */
 int nrsc5hip_stage_halfband_fm_cu8(nrsc5hip_engine *e, const uint8_t *iq, uint32_t nbytes, int16_t *out /* [nbytes/4][2] */);

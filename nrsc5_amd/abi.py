@@ -110,6 +110,26 @@ SIS_STATS = (("frames", "crc_good", "sis", "llds") + tuple("id%d" % k for k in r
 SIS_EVENT_HEADER = 48                    # bytes of an event in the arena in front of its text (padded to 4); the arena header is 16
 
 
+AAS_EVENT_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_int32),
+                                ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)                               # nrsc5hip_aas_event_cb
+AAS_KINDS = (None, "psd", "sig", "lot_header", "lot_fragment", "lot", "stream", "packet")               # NRSC5HIP_AAS_*
+AAS_STATS = ("packets", "psd", "sig_packets", "sig_parsed", "sig_truncated", "sig_zero_length", "sig_empty", "unknown_port", "before_sig", "not_in_sig",
+             "stream", "packet", "unknown_type", "lot_packets", "lot_dropped", "lot_short_header", "lot_headers", "lot_resets", "lot_fragments",
+             "lot_duplicates", "lot_too_large", "lot_files", "lot_oversize", "lru_evictions", "pool_evictions", "events", "d2h_bytes")   # nrsc5hip_aas_stats
+AAS_FRAGMENTS = 1                        # NRSC5HIP_AAS_FRAGMENTS
+AAS_EVENT_HEADER = 48                    # bytes of an event in the arena in front of its data (padded to 4); the arena header is 16
+AAS_SIG_MAX = 5632                       # NRSC5HIP_AAS_SIG_MAX
+AAS_MAX_FILES = 64
+
+
+class AasEvent(ctypes.Structure):        # an event of k_aas as it lies in the arena
+    _fields_ = [("pos", ctypes.c_uint32), ("len", ctypes.c_uint32), ("kind", ctypes.c_uint16), ("port", ctypes.c_uint16), ("seq", ctypes.c_uint32),
+                ("v", ctypes.c_int32 * 8)]
+
+
+assert ctypes.sizeof(AasEvent) == AAS_EVENT_HEADER
+
+
 class SisInfo(ctypes.Structure):         # nrsc5hip_sis_info
     _fields_ = [("country_code", ctypes.c_char * 4), ("fcc_facility_id", ctypes.c_int32),
                 ("name_enc", ctypes.c_int32), ("name_len", ctypes.c_int32), ("name", ctypes.c_uint8 * 16),

@@ -1,11 +1,11 @@
-"""The consumers of an engine's block records (nrsc5hip_hdc_* / _psd_* / _sis_*): audio packets on the host, PSD packets and SIS events from their
-arenas on the device.  Every name here is reachable as nrsc5_amd.engine.<name> too."""
+"""The consumers of an engine's block records (nrsc5hip_hdc_* / _psd_* / _sis_* / _aas_*): audio packets on the host, PSD packets, SIS events and
+data-service events (SIG, LOT files) from their arenas on the device.  Every name here is reachable as nrsc5_amd.engine.<name> too."""
 from __future__ import annotations
 
 import ctypes
 import numpy as np
 
-from .abi import (AAS_CB, HDC_CB, L2_AM, L2_FM_P1, L2_FM_PX, MODE_FM, PSD_STATS, REC_PROCESSED, REC_TO_FINE, RECORD_DTYPE, SIS_CB, SIS_KINDS, SIS_STATS,
+from .abi import (AAS_CB, AAS_EVENT_CB, AAS_FRAGMENTS, AAS_KINDS, AAS_SIG_MAX, AAS_STATS, HDC_CB, L2_AM, L2_FM_P1, L2_FM_PX, MODE_FM, PSD_STATS, REC_PROCESSED, REC_TO_FINE, RECORD_DTYPE, SIS_CB, SIS_KINDS, SIS_STATS,
                   L2Frame, Nrsc5HipError, SisInfo)
 
 
@@ -333,3 +333,126 @@ def feed_sis_batch(sis: SisConsumer, targets, fresh) -> list:
         raise ValueError("targets and fresh must have one entry per stream")
     arrs, ptrs, counts = _record_args(fresh)
     return sis._appended(sis.events, "nrsc5hip_sis_feed", sis._h, int(tg.size), tg.ctypes.data, ptrs, counts.ctypes.data, sis._cb, None)
+
+
+def aas_sig_table(data: bytes) -> list:
+    """The flat SIG layout of include/nrsc5hip.h (the SIG event's data, nrsc5hip_aas_sig) as a list of services with their components, as the
+    reference's NRSC5_EVENT_SIG lists them; the name converted like the reference's (ISO-8859-1 -> UTF-8, cut at a NUL), None where none was sent"""
+    out, p = [], 0
+    while p < len(data):
+        kind, number, n = data[p], data[p + 1] | data[p + 2] << 8, data[p + 3]
+        name = sis_text(0, data[p + 4:p + 4 + n]) if n else None
+        p += 4 + n
+        comps = []
+        for _ in range(data[p]):
+            c = data[p + 1:p + 12]
+            comp = {"type": "audio" if c[0] == 2 else "data", "id": c[1], "port": c[2] | c[3] << 8}
+            if c[0] == 1:
+                comp["service_data_type"] = c[4] | c[5] << 8
+            comp["data_type"] = c[6]
+            comp["mime"] = int.from_bytes(c[7:11], "little")
+            comps.append(comp)
+            p += 11
+        p += 1
+        out.append({"type": "audio" if kind == 2 else "data", "number": number, "name": name, "components": comps})
+    return out
+
+
+def aas_event_fields(kind: str, port: int, seq: int, v, data: bytes):
+    """An event of k_aas as the fields the reference's callback reports (nrsc5.h: sig, lot, lot_fragment, stream, packet); "psd" is the packet for the
+    ID3 parser.  A sig event is the list of services; names of files as str (ISO-8859-1)"""
+    if kind == "psd":
+        return {"program": v[0], "port": port, "seq": seq, "data": data}
+    if kind == "sig":
+        return aas_sig_table(data)
+    if kind in ("lot_header", "lot"):
+        f = {"port": port, "lot": v[0], "size": v[1] & 0xffffffff, "mime": v[2] & 0xffffffff, "expiry": tuple(v[3:8])}
+        if kind == "lot":
+            size = len(data) - seq
+            f["name"], f["data"] = data[size:].decode("latin-1"), data[:size]
+        else:
+            f["name"] = data.decode("latin-1")
+        return f
+    if kind == "lot_fragment":
+        return {"port": port, "lot": v[0], "seq": seq, "repeat": v[1], "is_duplicate": v[2], "size": v[3], "bytes_so_far": v[4] & 0xffffffff}
+    if kind in ("stream", "packet"):
+        return {"port": port, "seq": seq, "mime": v[0] & 0xffffffff, "service": v[1], "component": v[2], "data": data}
+    raise ValueError(kind)
+
+
+def aas_packets(packets) -> np.ndarray:
+    """[(port, seq, data) or (port, seq, data, program)] as nrsc5hip_stage_aas takes a stream's packets"""
+    out = bytearray()
+    for pk in packets:
+        port, seq, data = pk[:3]
+        out += int(port).to_bytes(2, "little") + int(seq).to_bytes(2, "little") + len(data).to_bytes(2, "little") + (pk[3] if len(pk) > 3 else 0).to_bytes(2, "little")
+        out += bytes(data)
+    return np.frombuffer(bytes(out), dtype=np.uint8)
+
+
+class AasConsumer(_Consumer):
+    """Data services on the device (nrsc5hip_aas_*), chained behind a PsdConsumer: SIG, port routing and LOT reassembly over the packet arena in HBM;
+    only events reach the host.  They land in `events` as (stream, kind, fields) and, raw, in `raw` as (stream, kind, port, seq, v[8], data).
+    lot_files: file slots per stream (1..64); fragments: write LOT_FRAGMENT events (they never carry the fragment's bytes)."""
+    _destroy = "nrsc5hip_aas_destroy"
+
+    def __init__(self, engine, nstreams: int, lot_files: int = 16, fragments: bool = False):
+        self.lib, self._engine, self._h, self.nstreams, self.lot_files = engine.lib, engine, ctypes.c_void_p(), nstreams, lot_files
+        rc = self.lib.nrsc5hip_aas_create(engine._h, nstreams, lot_files, AAS_FRAGMENTS if fragments else 0, ctypes.byref(self._h))
+        if rc != 0:
+            raise Nrsc5HipError(f"nrsc5hip_aas_create failed ({rc}): {self.lib.nrsc5hip_last_error().decode()}")
+        self.events, self.raw = [], []
+        self._cb = AAS_EVENT_CB(self._on_event)
+
+    def _on_event(self, opaque, stream, kind, port, seq, v, data, n):
+        vals, body, name = [int(v[k]) for k in range(8)], bytes(ctypes.string_at(data, n)) if n else b"", AAS_KINDS[kind]
+        self.raw.append((int(stream), name, int(port), int(seq), vals, body))
+        self.events.append((int(stream), name, aas_event_fields(name, int(port), int(seq), vals, body)))
+
+    def reset(self, stream: int):
+        self._result(self.lib.nrsc5hip_aas_reset(self._h, stream), "nrsc5hip_aas_reset")
+
+    def stats(self, stream: int) -> dict:
+        return self._stats("nrsc5hip_aas_stats", AAS_STATS, stream)
+
+    def sig(self, stream: int) -> list:
+        """nrsc5hip_aas_sig: the stream's SIG table as the sig event held it ([] while no SIG has been seen)"""
+        out, n, ns = (ctypes.c_uint8 * AAS_SIG_MAX)(), ctypes.c_uint(), ctypes.c_int()
+        self._result(self.lib.nrsc5hip_aas_sig(self._h, stream, out, ctypes.byref(n), ctypes.byref(ns)), "nrsc5hip_aas_sig")
+        table = aas_sig_table(bytes(out[:n.value]))
+        assert len(table) == ns.value
+        return table
+
+    def debug_arena(self, nbytes: int):
+        self._result(self.lib.nrsc5hip_aas_debug_arena(self._h, nbytes), "nrsc5hip_aas_debug_arena")
+
+    def stage(self, targets, packets_per_stream) -> list:
+        """nrsc5hip_stage_aas: packets_per_stream[i] ([(port, seq, data[, program])], may be empty) go to consumer stream targets[i], all in one call
+        (one k_aas workgroup per stream).  -> the events of this call, all of targets[0] first"""
+        n = len(targets)
+        arrs = [aas_packets(p) for p in packets_per_stream]
+        tg, nb = np.ascontiguousarray(targets, dtype=np.int32), np.ascontiguousarray([a.size for a in arrs], dtype=np.int32)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        return self._appended(self.events, "nrsc5hip_stage_aas", self._h, n, tg.ctypes.data, ptrs, nb.ctypes.data, self._cb, None)
+
+    def stage_frames(self, psd: PsdConsumer, targets, frames_per_stream, lcs, reset_at=None) -> list:
+        """nrsc5hip_stage_aas_frames: PsdConsumer.stage_streams with k_aas chained behind k_psd.  -> the events of this call, all of targets[0] first"""
+        n = len(targets)
+        arrs = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_per_stream]
+        arrs = [a[None, :] if a.ndim == 1 else a for a in arrs]
+        i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32)
+        tg, nb, nf, lc = i32(targets), i32([a.shape[1] for a in arrs]), i32([a.shape[0] for a in arrs]), i32(lcs)
+        rs = None if reset_at is None else i32([-1 if r is None else r for r in reset_at])
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        return self._appended(self.events, "nrsc5hip_stage_aas_frames", self._h, psd._h, self._engine._h, n, tg.ctypes.data, ptrs, nb.ctypes.data,
+                              nf.ctypes.data, lc.ctypes.data, None if rs is None else rs.ctypes.data, self._cb, None)
+
+
+def feed_aas_batch(engine, aas: AasConsumer, psd: PsdConsumer, stream_ids, recs_per_stream, targets=None, mode: int = MODE_FM) -> list:
+    """nrsc5hip_aas_feed: feed_psd_batch with the data services chained behind it -- the PSD consumer advances as it would there, its packets stay in
+    device memory, one k_aas launch runs over them.  -> [(stream, kind, fields)] of this call, all of stream_ids[0] first (appended to aas.events as
+    well); kinds: "psd", "sig", "lot_header", "lot_fragment", "lot", "stream", "packet".  Call it while the ring slots the records name hold their frames."""
+    ids, tg = _ids_targets(stream_ids, targets, recs_per_stream)
+    arrs, ptrs, counts = _record_args(recs_per_stream)
+    return aas._appended(aas.events, "nrsc5hip_aas_feed", aas._h, psd._h, engine._h, int(ids.size), ids.ctypes.data, None if tg is None else tg.ctypes.data,
+                         ptrs, counts.ctypes.data, mode, aas._cb, None)

@@ -2,6 +2,7 @@
 // device buffers that free themselves, the target check, one plan / arena round and the stats read-back.
 #pragma once
 #include <string.h>
+#include <functional>
 #include <vector>
 #include "kernels.h"
 #include "host_util.h"
@@ -68,24 +69,32 @@ bool arena_walk(const uint8_t *got, size_t used, size_t ns, Valid valid, std::ve
     return true;
 }
 
-// One round on `st`: grows plan and arena (nothing has been touched when that fails), uploads the plan (streams, then job_bytes of jobs) in one copy, clears
-// the header, launch(ArenaDev), reads the header and then the used part, and hands every record to deliver(stream, rec, its bytes): all of the first listed
-// stream's records first -- the arena holds each stream's records in order, the streams interleaved.  what / kernel: for the texts.  -> records delivered, or < 0
-template <typename Rec, typename Launch, typename Valid, typename Deliver>
-int arena_round(ArenaHost &h, hipStream_t st, const char *what, const char *kernel, const std::vector<ArenaStream> &streams, const void *jobs, size_t job_bytes,
-                size_t arena_cap, Launch launch, Valid valid, Deliver deliver)
+// The first half of a round on `st`: grows plan and arena (nothing has been touched when that fails), uploads the plan (streams, then job_bytes of jobs) in
+// one copy, clears the header and runs launch(ArenaDev).  *out: the round's device pointers, for arena_collect or for a consumer chained behind it
+template <typename Launch>
+int arena_begin(ArenaHost &h, hipStream_t st, const std::vector<ArenaStream> &streams, const void *jobs, size_t job_bytes, size_t arena_cap, Launch launch, ArenaDev *out)
 {
     const size_t ns = streams.size(), plan_streams = ns * sizeof(ArenaStream), plan_bytes = plan_streams + job_bytes;
     int rc;
     if ((rc = h.plan.need(plan_bytes)) || (rc = h.arena.need(sizeof(ArenaHdr) + arena_cap))) return rc;
     std::vector<uint8_t> plan(plan_bytes);
     memcpy(plan.data(), streams.data(), plan_streams);
-    memcpy(plan.data() + plan_streams, jobs, job_bytes);
+    if (job_bytes) memcpy(plan.data() + plan_streams, jobs, job_bytes);
     HIPCHK(hipMemcpy(h.plan.p, plan.data(), plan_bytes, hipMemcpyHostToDevice));
     HIPCHK(st ? hipMemsetAsync(h.arena.p, 0, sizeof(ArenaHdr), st) : hipMemset(h.arena.p, 0, sizeof(ArenaHdr)));
     const ArenaDev d{(const ArenaStream *)h.plan.p, (const uint8_t *)h.plan.p + plan_streams, (ArenaHdr *)h.arena.p, (uint8_t *)h.arena.p + sizeof(ArenaHdr), (unsigned)arena_cap};
     launch(d);
     HIPCHK(hipGetLastError());
+    *out = d;
+    return 0;
+}
+
+// The second half: reads the header and then the used part, and hands every record to deliver(stream, rec, its bytes): all of the first listed stream's
+// records first -- the arena holds each stream's records in order, the streams interleaved.  what / kernel: for the texts.  -> records delivered, or < 0
+template <typename Rec, typename Valid, typename Deliver>
+int arena_collect(ArenaHost &h, hipStream_t st, const char *what, const char *kernel, const std::vector<ArenaStream> &streams, const ArenaDev &d, Valid valid, Deliver deliver)
+{
+    const size_t ns = streams.size(), arena_cap = d.cap;
     ArenaHdr hdr;
     if (st) {
         HIPCHK(hipMemcpyAsync(&hdr, h.arena.p, sizeof(hdr), hipMemcpyDeviceToHost, st));
@@ -111,4 +120,23 @@ int arena_round(ArenaHost &h, hipStream_t st, const char *what, const char *kern
     return delivered;
 }
 
+// One round: arena_begin, then arena_collect
+template <typename Rec, typename Launch, typename Valid, typename Deliver>
+int arena_round(ArenaHost &h, hipStream_t st, const char *what, const char *kernel, const std::vector<ArenaStream> &streams, const void *jobs, size_t job_bytes,
+                size_t arena_cap, Launch launch, Valid valid, Deliver deliver)
+{
+    ArenaDev d;
+    const int rc = arena_begin(h, st, streams, jobs, job_bytes, arena_cap, launch, &d);
+    return rc ? rc : arena_collect<Rec>(h, st, what, kernel, streams, d, valid, deliver);
+}
+
 }  // namespace nrsc5
+
+// What a consumer chained behind k_psd does with the round's packet arena, still in device memory (aas_consumer.hip): -> its result.  The PSD consumer's
+// own delivery does not happen then
+using PsdChain = std::function<int(const nrsc5::ArenaDev &packets, const std::vector<nrsc5::ArenaStream> &streams)>;
+// nrsc5hip_psd_feed / nrsc5hip_stage_psd_streams; chain == nullptr: exactly those
+int psd_feed_chain(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets, const nrsc5hip_record *const *records,
+                   const int *counts, int mode, nrsc5hip_aas_cb cb, void *opaque, const PsdChain *chain);
+int psd_stage_chain(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits, const int *nbits, const int *nframes,
+                    const int *lcs, const int *reset_at, nrsc5hip_aas_cb cb, void *opaque, const PsdChain *chain);

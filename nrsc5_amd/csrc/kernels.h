@@ -242,6 +242,68 @@ struct SisArgs {
 void sis_state_init(SisState &s);                                   // pids_init, pids.c:1052-1102 (host)
 void launch_sis(const SisArgs &a, int nstreams, hipStream_t st);
 
+// ---- data services (k_aas.hip): output_aas_push (output.c:493-896) over the packet arena k_psd leaves in device memory, one wave64 workgroup per stream ----
+constexpr int AAS_SERVICES = 16, AAS_COMPONENTS = 8;                // MAX_SIG_SERVICES, MAX_SIG_COMPONENTS (output.h:13-14)
+constexpr int AAS_LOT_PER_COMPONENT = 12;                           // MAX_LOT_FILES (output.h:15)
+constexpr int AAS_FRAGMENT = 256, AAS_FRAGMENTS = 256;              // LOT_FRAGMENT_SIZE, MAX_LOT_FRAGMENTS
+constexpr int AAS_FILE_BYTES = AAS_FRAGMENT * AAS_FRAGMENTS;        // 65 536
+constexpr int AAS_NAME_MAX = 231;                                   // hdrlen is a byte: 255 - 8 - 16
+constexpr int AAS_MAX_FILES = 64;                                   // file slots per stream at most: a lane each
+constexpr int AAS_STATS = 26;                                       // device counters per stream: nrsc5hip_aas_stats [0..25]
+enum { AAS_C_PACKETS = 0, AAS_C_PSD, AAS_C_SIG, AAS_C_SIG_PARSED, AAS_C_SIG_TRUNCATED, AAS_C_SIG_ZERO_LEN, AAS_C_SIG_EMPTY, AAS_C_UNKNOWN_PORT,
+       AAS_C_BEFORE_SIG, AAS_C_NOT_IN_SIG, AAS_C_STREAM, AAS_C_PACKET, AAS_C_UNKNOWN_TYPE, AAS_C_LOT_PACKETS, AAS_C_LOT_BAD, AAS_C_LOT_SHORT_HEADER,
+       AAS_C_LOT_HEADERS, AAS_C_LOT_RESETS, AAS_C_LOT_FRAGMENTS, AAS_C_LOT_DUPLICATES, AAS_C_LOT_TOO_LARGE, AAS_C_LOT_FILES, AAS_C_LOT_OVERSIZE,
+       AAS_C_LRU_EVICTIONS, AAS_C_POOL_EVICTIONS, AAS_C_EVENTS };
+enum { AAS_FLAG_FRAGMENTS = 1 };                                    // NRSC5HIP_AAS_FRAGMENTS
+// sig_component_t / sig_service_t (output.h:60-92) without the pointers and the files; type: SIG_COMPONENT_* / SIG_SERVICE_* (0 none, 1 data, 2 audio)
+struct AasComponent { uint8_t type, id, data_type, pad; uint16_t port, service_data_type; uint32_t mime; };
+struct AasService { uint8_t type, pad; uint16_t number; uint32_t name_len; uint8_t name[256]; AasComponent comp[AAS_COMPONENTS]; };
+struct AasStream { AasService services[AAS_SERVICES]; uint32_t lot_lru_counter, pad[3]; };
+// the table as the SIG event and nrsc5hip_aas_sig carry it (include/nrsc5hip.h has the layout); out == nullptr: count only.  -> bytes, *nservices
+__host__ __device__ inline unsigned aas_sig_flatten(const AasService *sv, uint8_t *out, unsigned *nservices)
+{
+    unsigned n = 0, ns = 0;
+    auto put = [&](unsigned b) { if (out) out[n] = (uint8_t)b; n++; };
+    for (; ns < (unsigned)AAS_SERVICES && sv[ns].type != 0; ns++) {                        // nrsc5_report_sig, nrsc5.c:880-934
+        const AasService &s = sv[ns];
+        put(s.type); put(s.number & 0xffu); put(s.number >> 8); put(s.name_len);
+        for (unsigned k = 0; k < s.name_len; k++) put(s.name[k]);
+        unsigned nc = 0;
+        for (int j = 0; j < AAS_COMPONENTS; j++) nc += s.comp[j].type != 0;
+        put(nc);
+        for (int j = 0; j < AAS_COMPONENTS; j++) {
+            const AasComponent &c = s.comp[j];
+            if (c.type == 0) continue;
+            put(c.type); put(c.id); put(c.port & 0xffu); put(c.port >> 8); put(c.service_data_type & 0xffu); put(c.service_data_type >> 8); put(c.data_type);
+            put(c.mime & 0xffu); put((c.mime >> 8) & 0xffu); put((c.mime >> 16) & 0xffu); put(c.mime >> 24);
+        }
+    }
+    *nservices = ns;
+    return n;
+}
+// aas_file_t (output.h:47-58): owner = service * 8 + component (-1: the slot is free), local = its index in the component's lot_files[12]
+struct AasFile {
+    int32_t owner, local; uint32_t lot, timestamp, size, mime; int32_t expiry[5];        // tm_year, tm_mon, tm_mday, tm_hour, tm_min
+    uint32_t has_name, name_len, bytes_so_far, pad[4];
+    uint32_t mask[AAS_FRAGMENTS / 32];
+    uint8_t name[AAS_NAME_MAX + 1];
+};
+static_assert(sizeof(AasComponent) == 12 && sizeof(AasStream) % 16 == 0 && sizeof(AasFile) % 16 == 0, "the states are cleared and moved as words");
+// an event in the arena: AasEvent, then `len` data bytes padded to a multiple of 4 (include/nrsc5hip.h says what each kind carries)
+struct AasEvent { uint32_t pos, len; uint16_t kind, port; uint32_t seq; int32_t v[8]; };
+static_assert(sizeof(AasEvent) == 48, "nrsc5hip.h and abi.py state the size");
+struct AasArgs {
+    const ArenaStream *streams;      // the listed streams: a workgroup takes the packets whose `pos` is its stream's
+    int nstreams, lot_files, flags;  // consumer streams (a target outside is not walked), file slots per stream, AAS_FLAG_*
+    const ArenaHdr *in_hdr; const uint8_t *in_arena; unsigned in_cap;     // the packet arena: PsdPacket records
+    AasStream *state;                // [consumer streams]
+    AasFile *files;                  // [consumer streams][lot_files]
+    uint8_t *data;                   // [consumer streams][lot_files][AAS_FILE_BYTES]
+    unsigned long long *stats;       // [consumer streams][AAS_STATS]
+    ArenaHdr *hdr; uint8_t *arena; unsigned arena_cap;
+};
+void launch_aas(const AasArgs &a, int nstreams, hipStream_t st);
+
 // ---- stage-level entry points (parity tests) ---------------------------------------------------
 // scratch of the stage-level K=7 decode (end lanes, chunk maps, packed soft words, segment metadata): owned by the engine that calls it
 struct VitScratch { int *endlane = nullptr; int cap = 0; uint8_t *gmap = nullptr; size_t gcap = 0; int *soft = nullptr; size_t scap = 0; int *meta = nullptr; int mcap = 0; };

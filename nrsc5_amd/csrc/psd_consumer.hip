@@ -66,7 +66,7 @@ extern "C" int nrsc5hip_psd_stats(nrsc5hip_psd *p, int stream, long long stats[1
 // The device work of one call and the delivery: dj[k] = frame k's words in device memory, lcs[k] its logical channel; streams / jobs: what k_psd walks
 // (PsdJob::keep is filled in here).  Nothing of the consumer's device state has been touched when this returns an error in front of the k_psd launch.
 static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job> &dj, const std::vector<int> &lcs, std::vector<ArenaStream> &streams,
-                   std::vector<PsdJob> &jobs, nrsc5hip_aas_cb cb, void *opaque)
+                   std::vector<PsdJob> &jobs, nrsc5hip_aas_cb cb, void *opaque, const PsdChain *chain)
 {
     const size_t n = dj.size(), ns = streams.size();
     if (ns == 0 || jobs.empty()) return 0;
@@ -121,6 +121,11 @@ static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job>
         a.hdr = d.hdr; a.arena = d.arena; a.arena_cap = d.cap;
         launch_psd(a, (int)ns, e->main);
     };
+    if (chain) {                                                // the packets stay where k_psd leaves them
+        ArenaDev d;
+        const int rc = arena_begin(p->ar, e->main, streams, jobs.data(), jobs.size() * sizeof(PsdJob), arena_cap, launch, &d);
+        return rc ? rc : (*chain)(d, streams);
+    }
     return arena_round<PsdPacket>(p->ar, e->main, "packet", "k_psd", streams, jobs.data(), jobs.size() * sizeof(PsdJob), arena_cap, launch,
                                   [](const PsdPacket &) { return true; }, [&](const ArenaStream &s, const PsdPacket &pk, const uint8_t *data) {
                                       if (cb) cb(opaque, s.target, pk.program, pk.port, pk.seq, data, pk.len);
@@ -128,8 +133,8 @@ static int psd_run(nrsc5hip_psd *p, nrsc5hip_engine *e, const std::vector<L2Job>
 }
 
 // A loss of sync changes nothing here either (see nrsc5hip_hdc_feed): psd_buf / psd_idx are cleared by frame_reset on the NEXT transition to fine sync.
-extern "C" int nrsc5hip_psd_feed(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
-                                 const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_aas_cb cb, void *opaque)
+int psd_feed_chain(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets, const nrsc5hip_record *const *records,
+                   const int *counts, int mode, nrsc5hip_aas_cb cb, void *opaque, const PsdChain *chain)
 {
     ON_ENGINE_DEVICE(e);
     if (!p || nstreams < 0 || (mode != NRSC5HIP_MODE_FM && mode != NRSC5HIP_MODE_AM)) FAIL(NRSC5HIP_EINVAL, "bad consumer / stream count / mode");
@@ -168,11 +173,17 @@ extern "C" int nrsc5hip_psd_feed(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstrea
         if ((rc = l2_resolve(e, (int)nframes, l2.data(), dj))) return rc;
         HIPCHK(hipDeviceSynchronize());                         // the frames may still be in flight on a decode stream
     }
-    return psd_run(p, e, dj, lcs, streams, jobs, cb, opaque);
+    return psd_run(p, e, dj, lcs, streams, jobs, cb, opaque, chain);
 }
 
-extern "C" int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits, const int *nbits,
-                                          const int *nframes, const int *lcs, const int *reset_at, nrsc5hip_aas_cb cb, void *opaque)
+extern "C" int nrsc5hip_psd_feed(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *stream_ids, const int *targets,
+                                 const nrsc5hip_record *const *records, const int *counts, int mode, nrsc5hip_aas_cb cb, void *opaque)
+{
+    return psd_feed_chain(p, e, nstreams, stream_ids, targets, records, counts, mode, cb, opaque, nullptr);
+}
+
+int psd_stage_chain(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits, const int *nbits, const int *nframes,
+                    const int *lcs, const int *reset_at, nrsc5hip_aas_cb cb, void *opaque, const PsdChain *chain)
 {
     ON_ENGINE_DEVICE(e);
     if (!p || nstreams < 1 || !targets || !bits || !nbits || !nframes || !lcs) FAIL(NRSC5HIP_EINVAL, "bad argument");
@@ -206,7 +217,13 @@ extern "C" int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, i
         streams.push_back(ArenaStream{targets[i], first, (int)jobs.size() - first, i});
     }
     HIPCHK(hipMemcpy(p->words.p, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return psd_run(p, e, dj, lc, streams, jobs, cb, opaque);
+    return psd_run(p, e, dj, lc, streams, jobs, cb, opaque, chain);
+}
+
+extern "C" int nrsc5hip_stage_psd_streams(nrsc5hip_psd *p, nrsc5hip_engine *e, int nstreams, const int *targets, const uint8_t *const *bits, const int *nbits,
+                                          const int *nframes, const int *lcs, const int *reset_at, nrsc5hip_aas_cb cb, void *opaque)
+{
+    return psd_stage_chain(p, e, nstreams, targets, bits, nbits, nframes, lcs, reset_at, cb, opaque, nullptr);
 }
 
 extern "C" int nrsc5hip_stage_psd(nrsc5hip_psd *p, nrsc5hip_engine *e, int stream, const uint8_t *bits, int nbits, int nframes, int lc,

@@ -20,7 +20,7 @@ if _AB_LIB:
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
 from .abi import _Config, _ChanConfig, _ScanConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
-                        sis_utf8, sis_text, _sis_device_info, sis_event_fields)
+                        sis_utf8, sis_text, _sis_device_info, sis_event_fields, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
 
 
 def l2_frame_to_dict(fr: L2Frame) -> dict:
@@ -147,6 +147,16 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_sis_stats.argtypes = [vp, ci, vp]
     lib.nrsc5hip_stage_sis.argtypes = [vp, ci, vp, vp, vp, vp, SIS_CB, vp]
     lib.nrsc5hip_sis_debug_arena.argtypes = [vp, ctypes.c_longlong]
+    lib.nrsc5hip_aas_create.argtypes = [vp, ci, ci, ci, ctypes.POINTER(vp)]
+    lib.nrsc5hip_aas_destroy.argtypes = [vp]
+    lib.nrsc5hip_aas_destroy.restype = None
+    lib.nrsc5hip_aas_reset.argtypes = [vp, ci]
+    lib.nrsc5hip_aas_feed.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, AAS_EVENT_CB, vp]
+    lib.nrsc5hip_aas_stats.argtypes = [vp, ci, vp]
+    lib.nrsc5hip_aas_sig.argtypes = [vp, ci, vp, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ci)]
+    lib.nrsc5hip_stage_aas.argtypes = [vp, ci, vp, vp, vp, AAS_EVENT_CB, vp]
+    lib.nrsc5hip_stage_aas_frames.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, AAS_EVENT_CB, vp]
+    lib.nrsc5hip_aas_debug_arena.argtypes = [vp, ctypes.c_longlong]
     ll = ctypes.c_longlong
     lib.nrsc5hip_chan_create.argtypes = [ctypes.POINTER(_ChanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_chan_destroy.argtypes = [vp]
@@ -187,6 +197,8 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_psd_create", "nrsc5hip_psd_destroy", "nrsc5hip_psd_reset", "nrsc5hip_psd_feed", "nrsc5hip_psd_stats", "nrsc5hip_stage_psd", "nrsc5hip_stage_psd_streams",
     "nrsc5hip_sis_create", "nrsc5hip_sis_destroy", "nrsc5hip_sis_reset", "nrsc5hip_sis_feed", "nrsc5hip_sis_get", "nrsc5hip_sis_stats", "nrsc5hip_stage_sis",
     "nrsc5hip_sis_debug_arena",
+    "nrsc5hip_aas_create", "nrsc5hip_aas_destroy", "nrsc5hip_aas_reset", "nrsc5hip_aas_feed", "nrsc5hip_aas_stats", "nrsc5hip_aas_sig", "nrsc5hip_stage_aas",
+    "nrsc5hip_stage_aas_frames", "nrsc5hip_aas_debug_arena",
     "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
     "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed",
     "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",

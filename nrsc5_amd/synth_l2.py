@@ -346,3 +346,55 @@ def fixed_data_session(seed: int = 0, nbits: int = 146176, n_frames: int = 7, su
         pos += width
         frames.append(frame_from_bytes(bytes(body), nbits, pci=PCI_FIXED if fi in fixed_only else PCI_AUDIO_FIXED if fi % 2 == 0 else PCI_AUDIO_FIXED_OPP))
     return frames
+
+
+# ---- data services: the Station Information Guide and LOT packets (the inverse of parse_sig / process_port, output.c:512-872) ----
+def sig_service(number: int, audio: bool = False, kind: int | None = None) -> bytes:
+    return bytes([kind if kind is not None else (0x40 if audio else 0x41)]) + number.to_bytes(2, "little") + bytes(1)
+
+
+def sig_name(name: bytes) -> bytes:
+    return bytes([0x69, len(name) + 2, 0]) + name
+
+
+def sig_data(cid: int, port: int, data_type: int, mime: int, sdt: int = 0x0104) -> bytes:
+    return bytes([0x67, 13, cid]) + port.to_bytes(2, "little") + sdt.to_bytes(2, "little") + bytes([data_type, 0, 0]) + mime.to_bytes(4, "little")
+
+
+def sig_audio(cid: int, port: int, ptype: int, mime: int = 0x4DC66C5A) -> bytes:
+    return bytes([0x66, 12, cid, port, ptype, 0, 0, 0, 0]) + mime.to_bytes(4, "little")
+
+
+def lot_expiry(e) -> bytes:
+    """(tm_year, tm_mon, tm_mday, tm_hour, tm_min) as bytes 4..7 of a LOT header"""
+    year, mon, mday, hour, minute = e
+    return (minute | hour << 6 | mday << 11 | (mon + 1) << 16 | (year + 1900) << 20).to_bytes(4, "little")
+
+
+def lot_header(size: int, mime: int, name: bytes, expiry=(131, 4, 17, 21, 59), version: int = 1) -> bytes:
+    return version.to_bytes(4, "little") + lot_expiry(expiry) + size.to_bytes(4, "little") + mime.to_bytes(4, "little") + name
+
+
+def lot_packet(lot: int, seq: int, data: bytes = b"", header: bytes = b"", repeat: int = 0, hdrlen: int | None = None) -> bytes:
+    """the data of a LOT packet; hdrlen: the byte to send instead of 8 + len(header)"""
+    return bytes([8 + len(header) if hdrlen is None else hdrlen, repeat]) + lot.to_bytes(2, "little") + seq.to_bytes(4, "little") + header + data
+
+
+def lot_file_packets(port: int, lot: int, body: bytes, name: bytes, mime: int, seq0: int = 0) -> list:
+    """[(port, seq, data)] of a whole file, the header on its first fragment"""
+    return [(port, (seq0 + k) & 0xffff, lot_packet(lot, k, body[256 * k:256 * k + 256], lot_header(len(body), mime, name) if k == 0 else b""))
+            for k in range((len(body) + 255) // 256)]
+
+
+def aas_frames(packets, per_frame: int = 10, span: int = 236, seed: int = 0) -> np.ndarray:
+    """[(port, seq, data)] as program 0's PSD byte stream in P1 frames: per_frame PDUs of `span` PSD bytes each -> [nframes, 146176] bits"""
+    rng = np.random.default_rng(seed)
+    stream = b"\x7e" + b"".join(hdlc(aas_payload(p[0], p[1], p[2])) for p in packets)
+    total = per_frame * span
+    stream += b"\x7e" * (-len(stream) % total)
+    frames = []
+    for fi in range(len(stream) // total):
+        body = b"".join(make_pdu(rng, 18000 // per_frame, nop=2, seq=(fi * per_frame + q) % 64, pdu_seq=fi % 8, psd=stream[fi * total + q * span:fi * total + (q + 1) * span], fill=False)
+                        for q in range(per_frame))
+        frames.append(frame_from_bytes(body, 146176))
+    return np.stack(frames)

@@ -10,7 +10,10 @@ prints one line per station event (SYNC with its frequency offset, MER, BER, LOS
 parameter as it arrives), decoded from the PIDS frames on the device (nrsc5hip_sis_feed); with a scan, every `found` line then carries the call sign.
 --dump-hdc DIR also records every station's
 audio programs (the reference's NRSC5_EVENT_HDC packets, as `nrsc5 --dump-hdc` frames them: ADTS) into
-DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.  FILE may be `-` (standard input, read in
+DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.
+--dump-aas-files DIR writes every station's complete LOT files (album art, station logos, text files) as `nrsc5 --dump-aas-files` names them,
+DIR/station<k>_<offset in Hz>_<lot>_<name>, and prints the reference's `SIG Service:` / `Audio component:` / `Data component:` / `LOT file:` lines; the
+Station Information Guide and the files are put together on the device (nrsc5hip_aas_feed), only complete files reach the host.  FILE may be `-` (standard input, read in
 --chunk pieces until it ends; --offsets is then required): the session may be of any length, the receiver gives FIFO space back as it
 goes (nrsc5hip_batch_trim).  Without --offsets the stations are found
 first (scan(): the band scan nrsc5hip_scan_* nominates centres from the capture's power spectrum, a short decode confirms them):
@@ -52,10 +55,18 @@ class WidebandReceiver:
     all stations' new records; 16 bytes per record go up, only events come back).  Every state change the reference reports becomes an event
     (eng.SIS_KINDS: "station_id", "station_name", "station_slogan", "station_message", "station_location", "audio_service", "data_service", "alert",
     "leap_second", "local_time", "exciter", "importer"; fields as eng.sis_event_fields) behind that station's record (and id3) events of the push, and
-    station_info[s] is the station's snapshot (SisConsumer.info: country, fcc, name, slogan, message, alert, location, services)."""
+    station_info[s] is the station's snapshot (SisConsumer.info: country, fcc, name, slogan, message, alert, location, services).
+    data_services=True: the receiver also follows every station's data services on the device (AasConsumer with lot_files file slots per station,
+    chained behind the PsdConsumer, which it implies: one eng.feed_aas_batch call per push in place of eng.feed_psd_batch).  The PSD-port packets go
+    down the same ID3 path as with metadata=True (id3 events, now_playing and on_aas are the same); the Station Information Guide becomes a
+    ("sig", services) event and services[s] keeps it; a LOT header becomes a ("lot_header", fields) event, a complete file a ("lot", fields) event
+    (eng.aas_event_fields: port, lot, size, mime, name, expiry, data), files[s][(port, lot)] keeps the last one and on_file(station, fields), if
+    given, sees each; stream and packet data become ("stream" / "packet", fields) events.  No other packet reaches the host: aas[s] stays empty and
+    on_aas sees the PSD-port packets only, so the host holds what the files take however long a carousel repeats."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
-                 programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False):
+                 programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
+                 lot_files: int = 16, on_file=None):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -80,7 +91,12 @@ class WidebandReceiver:
         self.hdc = eng.HdcConsumer(self.k, lib=self.engine.lib) if self.programs else None
         self.metadata = bool(metadata)
         self.on_aas = on_aas
-        self.psd = eng.PsdConsumer(self.engine, self.k) if self.metadata else None
+        self.data_services = bool(data_services)
+        self.on_file = on_file
+        self.psd = eng.PsdConsumer(self.engine, self.k) if self.metadata or self.data_services else None
+        self.data = eng.AasConsumer(self.engine, self.k, lot_files=lot_files) if self.data_services else None
+        self.services = [[] for _ in range(self.k)]
+        self.files = [{} for _ in range(self.k)]
         self.now_playing = [{} for _ in range(self.k)]
         self.aas = [[] for _ in range(self.k)]
         self.sis = eng.SisConsumer(self.engine, self.k) if sis else None
@@ -100,22 +116,46 @@ class WidebandReceiver:
         self.sis.events.clear()
         self.sis.raw.clear()
 
+    def _packet(self, s, program, port, seq, data, events, keep: bool):
+        """an AAS packet on the host: a tag of a PSD port becomes an id3 event; keep: anything else goes to aas[s]"""
+        if self.on_aas is not None:
+            self.on_aas(s, program, port, seq, data)
+        tag = parse_id3(data) if is_psd_port(port) else None
+        if tag is None:
+            if keep:
+                self.aas[s].append((program, port, seq, data))
+            return
+        v = {"program": port & 7, **tag}                            # output.c:881: the port names the program
+        self.now_playing[s][port & 7] = tag
+        self.logs[s].append(("id3", v))
+        events[s].append((s, "id3", v))
+
     def _feed_metadata(self, fresh, events):
         """fresh[s]: as for _feed_programs; events[s]: the station's events of this push, which the id3 events go behind"""
         if not any(len(r) for r in fresh):
             return
         for s, program, port, seq, data in eng.feed_psd_batch(self.engine, self.psd, self.ids, fresh):
-            if self.on_aas is not None:
-                self.on_aas(s, program, port, seq, data)
-            tag = parse_id3(data) if is_psd_port(port) else None
-            if tag is None:
-                self.aas[s].append((program, port, seq, data))
-                continue
-            v = {"program": port & 7, **tag}                        # output.c:881: the port names the program
-            self.now_playing[s][port & 7] = tag
-            self.logs[s].append(("id3", v))
-            events[s].append((s, "id3", v))
+            self._packet(s, program, port, seq, data, events, True)
         self.psd.packets.clear()
+
+    def _feed_data_services(self, fresh, events):
+        """as _feed_metadata, with the data services chained behind the PSD transport on the device"""
+        if not any(len(r) for r in fresh):
+            return
+        for s, kind, f in eng.feed_aas_batch(self.engine, self.data, self.psd, self.ids, fresh):
+            if kind == "psd":
+                self._packet(s, f["program"], f["port"], f["seq"], f["data"], events, False)
+                continue
+            if kind == "sig":
+                self.services[s] = f
+            elif kind == "lot":
+                self.files[s][(f["port"], f["lot"])] = f
+                if self.on_file is not None:
+                    self.on_file(s, f)
+            self.logs[s].append((kind, f))
+            events[s].append((s, kind, f))
+        self.data.events.clear()
+        self.data.raw.clear()
 
     def _feed_programs(self, fresh):
         """fresh[s]: the records station s delivered in this push; their frames are still in the rings (nothing was processed since)"""
@@ -159,7 +199,9 @@ class WidebandReceiver:
                 new[s] += [(s, kind, v) for kind, v in log]
         if self.programs:
             self._feed_programs(fresh)
-        if self.metadata:
+        if self.data_services:
+            self._feed_data_services(fresh, new)
+        elif self.metadata:
             self._feed_metadata(fresh, new)
         if self.sis is not None:
             self._feed_sis(fresh, new)
@@ -171,6 +213,8 @@ class WidebandReceiver:
     def close(self):
         if self.hdc is not None:
             self.hdc.close()
+        if self.data is not None:
+            self.data.close()
         if self.psd is not None:
             self.psd.close()
         if self.sis is not None:
@@ -361,6 +405,20 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} ID3 program {v['program']}" + "".join(f" {k}={v[k]!r}" for k in ("title", "artist", "album", "genre") if k in v)
     if kind in _SIS_LINES:
         return f"{head} " + _SIS_LINES[kind](v)
+    if kind == "sig":                                               # main.c:416-438
+        lines = []
+        for sv in v:
+            lines.append(f"{head} SIG Service: type={sv['type']} number={sv['number']} name={sv['name']}")
+            for c in sv["components"]:
+                if c["type"] == "audio":
+                    lines.append(f"{head}   Audio component: id={c['id']} port={c['port']:04X} type={c['data_type']} mime={c['mime']:08X}")
+                else:
+                    lines.append(f"{head}   Data component: id={c['id']} port={c['port']:04X} service_data_type={c['service_data_type']} type={c['data_type']} mime={c['mime']:08X}")
+        return "\n".join(lines) if lines else None
+    if kind == "lot":                                               # main.c:445-450
+        y, mo, d, h, mi = v["expiry"]
+        return (f"{head} LOT file: port={v['port']:04X} lot={v['lot']} name={v['name']} size={v['size']} mime={v['mime']:08X} "
+                f"expiry={y + 1900:04d}-{mo + 1:02d}-{d:02d}T{h:02d}:{mi:02d}:00Z")
     return None
 
 
@@ -424,6 +482,25 @@ class HdcDump:
         return lines
 
 
+class AasDump:
+    """--dump-aas-files: every complete LOT file as the reference names it, <lot>_<name> (main.c:253), prefixed like --dump-hdc; path separators in the
+    name are replaced"""
+
+    def __init__(self, directory: str, offsets_hz):
+        import os
+        os.makedirs(directory, exist_ok=True)
+        self.dir, self.offsets = directory, [float(f) for f in offsets_hz]
+
+    def path(self, station: int, lot: int, name: str) -> str:
+        import os
+        safe = name.replace("/", "_").replace("\\", "_").replace("\0", "_")
+        return os.path.join(self.dir, f"station{station}_{int(round(self.offsets[station])):+d}_{lot}_{safe}")
+
+    def write(self, station: int, f: dict):
+        with open(self.path(station, f["lot"], f["name"]), "wb") as out:
+            out.write(f["data"])
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nrsc5_amd.wideband", description=__doc__.splitlines()[0])
     ap.add_argument("file", help="capture file, or - for standard input (needs --offsets)")
@@ -441,6 +518,8 @@ def main(argv=None) -> int:
                     help="decimated samples of FIFO per station: at least %d + the outputs of one push, whatever the length of the session" % eng.TRIM_RETAIN_MAX)
     ap.add_argument("--dump-hdc", metavar="DIR", default=None,
                     help="write every station's audio programs as ADTS: DIR/station<k>_<offset in Hz>_p<program>.aac")
+    ap.add_argument("--dump-aas-files", metavar="DIR", default=None,
+                    help="write every station's complete LOT files (album art, logos): DIR/station<k>_<offset in Hz>_<lot>_<name>; prints the SIG and a line per file")
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
     ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -475,7 +554,10 @@ def main(argv=None) -> int:
                     print("no station found", file=sys.stderr)
                     return 1
         del head
-    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis)
+    rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
+                          data_services=a.dump_aas_files is not None)
+    if a.dump_aas_files is not None:
+        rx.on_file = AasDump(a.dump_aas_files, offsets).write
     dump = None
     if a.dump_hdc is not None:
         dump = HdcDump(a.dump_hdc, offsets, rx.hdc.adts)
