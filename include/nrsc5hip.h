@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 15   /* 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 16   /* 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -945,6 +945,61 @@ int  nrsc5hip_scan_detect_psd(const double *psd, int nfft /* a power of two >= 1
                               nrsc5hip_scan_station *stations_out, int max, int *n);
 /* nrsc5hip_scan_spectrum followed by nrsc5hip_scan_detect_psd */
 int  nrsc5hip_scan_detect(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_station *stations_out, int max, int *n);
+
+/* ---- analog FM audio (ABI 16): the analog programme of every station's 744 187.5 S/s cs16 stream as 44.1 kS/s stereo PCM -----------
+ * Input: per channel (1 <= nchan <= 512) the cs16 stream the channelizer makes, x[n] (n counted from the last create / reset, x[n] = 0 for
+ * n < 0), Fs = 744 187.5 S/s.  Every quantity is a function of absolute sample indices; there is no recurrence and no loop filter, so any
+ * chunking of a session (down to 1 sample) gives identical bytes.  Fs1 = Fs / 2 = 372 093.75 S/s; audio rate = Fs1 * 16 / 135 = 44 100 S/s.
+ *   channel filter  z[m] = sum_i hA[i] x[2 m - i], i < 112: Kaiser lowpass (double on the host, stored float32, DC gain 1), +-0.1 dB to
+ *                   95 kHz, >= 70 dB from 129 361 Hz (the first primary-main carrier).  In MP2 / MP3 / MP11 the extended carriers from
+ *                   101.7 kHz lie inside the passband: inherent, the analog programme and they share those frequencies
+ *   discriminator   d[m] = atan2(Im w, Re w) * Fs1 / (2 pi 75 000), w = z[m] conj z[m - 1]; d[0] = 0, and d[m] = 0 where w = 0 (silence in,
+ *                   silence out); +-75 kHz -> +-1
+ *   pilot           phi19(m) = 2 pi ((608 m) mod 11907) / 11907 (19 kHz exactly, 64-bit integers); block sums p[j] = sum over m in
+ *                   [540 j, 540 j + 540) of d[m] exp(-j phi19(m)); smoothed p^[j] = sum over |w| <= 16 of win[w] p[j + w], win[w] =
+ *                   0.5 (1 + cos(pi w / 17)), blocks in front of the stream zero; level a = 2 |p^| / 540 / sum(win); block j is stereo
+ *                   when a >= pilot_min; subcarrier of block j: sub[m] = sin(2 phi19(m) + 2 theta_j), exp(j 2 theta_j) = -(p^ / |p^|)^2
+ *   paths           sum S[m] = d[m]; difference D_j[m] = 2 (aq d[m - 1] + bq d[m] + aq d[m + 1]) sub[m] (0 in a mono block); (aq, bq, aq)
+ *                   undoes the discriminator's droop sinc(f / Fs1) around the subcarrier: exact at 28 and 48 kHz
+ *   resampler       audio output k of block j = k / 64 sits at t_k = 135 k / 16 Fs1 samples, i = floor(t_k), phase (135 k) mod 16 exactly:
+ *                   y[k] = sum_j' tab[phase][j'] src[i - j'], j' < taps_audio, for src = S and src = D_j; the prototype (at 16 Fs1, DC gain
+ *                   16) is a Kaiser lowpass (flat to 15 kHz, >= 60 dB from 19 kHz) convolved with the de-emphasis exp(-t / tau) sampled
+ *                   at 16 Fs1 (its first sample halved) and cut below 2^-30; tau = 75 us, 50 us or 0 (none)
+ *   output          L = S + D, R = S - D; int16 = round to nearest of (float32)(32767 gain) v, clamped (clamps counted per channel and
+ *                   side), interleaved L, R
+ * Audio block j (64 outputs) exists once input sample 1080 (j + 17) - 2 has arrived (nrsc5hip_fm_info: latency_in = 18 359 samples in front
+ * of the first block): the smoothing window looks 16 blocks ahead.  There is no flush: the tail of a session stays undelivered.
+ * The object runs on its own HIP stream on cfg.device; it is not re-entrant. */
+typedef struct nrsc5hip_fm_config {
+    int device, nchan;
+    double deemphasis_us;                /* 75, 50 or 0 */
+    double pilot_min;                    /* 0: the default, 0.03 (the nominal injection is 0.08 .. 0.10) */
+    const float *gain;                   /* [nchan] or NULL (1) */
+} nrsc5hip_fm_config;
+typedef struct nrsc5hip_fm nrsc5hip_fm;
+int  nrsc5hip_fm_create(const nrsc5hip_fm_config *cfg, nrsc5hip_fm **out);
+void nrsc5hip_fm_destroy(nrsc5hip_fm *fm);
+int  nrsc5hip_fm_reset(nrsc5hip_fm *fm);                                       /* == a freshly created object */
+int  nrsc5hip_fm_info(nrsc5hip_fm *fm, int *taps_channel, int *taps_audio, int *phases, long long *latency_in);   /* any pointer may be NULL */
+int  nrsc5hip_fm_taps(nrsc5hip_fm *fm, float *channel /* [taps_channel] or NULL */, float *audio /* [phases][taps_audio] or NULL */);
+/* stereo frames per channel the next push of n_in samples yields (negative: error) */
+long long nrsc5hip_fm_outputs_for(nrsc5hip_fm *fm, long long n_in);
+/* channel k's n_in new cs16 samples at dev_in + k * in_stride_elems (device memory, 4-byte aligned, in_stride_elems even and >= 2 * n_in when
+ * nchan > 1); its new frames (L, R) go to dev_out + k * out_stride_elems (>= 2 * out_capacity when nchan > 1).  NRSC5HIP_EOVERFLOW when
+ * they exceed out_capacity (frames per channel): the object is then untouched.  Returns when the outputs are complete. */
+int  nrsc5hip_fm_process(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, int16_t *dev_out,
+                         long long out_stride_elems, long long out_capacity, long long *n_out);
+int  nrsc5hip_fm_clip_counts(nrsc5hip_fm *fm, long long *counts /* [nchan][2]: L, R, since create / reset */);
+/* level a and stereo flag of the last audio block delivered (0 before the first); either pointer may be NULL */
+int  nrsc5hip_fm_pilot(nrsc5hip_fm *fm, float *level /* [nchan] */, int *stereo /* [nchan] */);
+/* stage hook: d (host, [nchan][(n_in + 1) / 2]) and the block sums (host, [nchan][((n_in + 1) / 2) / 540][2], may be NULL) of n_in samples
+ * taken as a whole session from n = 0; the object's own session is not touched */
+int  nrsc5hip_stage_fm_mpx(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *d_out, float *psum_out);
+/* nrsc5hip_chan_feed, and the demodulator over the same staged outputs before the staging buffer is written again: the channelized
+ * samples never visit the host.  fm has the channelizer's nchan and device; channel k's new frames go to dev_audio + k * audio_stride_elems.
+ * NRSC5HIP_EOVERFLOW (audio_capacity) and an append the engine refuses leave both objects as before the call. */
+int  nrsc5hip_chan_feed_fm(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, nrsc5hip_fm *fm, const void *dev_in, long long n_in,
+                           int16_t *dev_audio, long long audio_stride_elems, long long audio_capacity, long long *n_audio);
 
 #ifdef __cplusplus
 }

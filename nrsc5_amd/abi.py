@@ -61,6 +61,12 @@ class _ChanConfig(ctypes.Structure):
                 ("rate_den", ctypes.c_longlong), ("offset_hz", ctypes.c_void_p), ("gain", ctypes.c_void_p)]
 
 
+class _FmConfig(ctypes.Structure):
+    """nrsc5hip_fm_config"""
+    _fields_ = [("device", ctypes.c_int), ("nchan", ctypes.c_int), ("deemphasis_us", ctypes.c_double), ("pilot_min", ctypes.c_double),
+                ("gain", ctypes.c_void_p)]
+
+
 class _ScanConfig(ctypes.Structure):
     """nrsc5hip_scan_config"""
     _fields_ = [("device", ctypes.c_int), ("format", ctypes.c_int), ("rate_num", ctypes.c_longlong), ("rate_den", ctypes.c_longlong),
@@ -85,6 +91,7 @@ EINVAL, ENOMEM, EHIP, EOVERFLOW = -1, -2, -3, -4
 TRIM_RETAIN_MAX = (8 * 16 + 1) * 71280      # NRSC5HIP_TRIM_RETAIN_MAX: what Engine.batch_trim can retain per FM stream (pipeline depth, include/nrsc5hip.h)
 TRIM_RETAIN_MAX_AM = (8 * 8 + 1) * 8910     # NRSC5HIP_TRIM_RETAIN_MAX_AM: ... per AM stream
 
+FM_AUDIO_RATE = 44100                       # what nrsc5hip_fm_* delivers: stereo int16 frames per second
 L2_FM_P1, L2_FM_PX, L2_AM = 0, 1, 2
 TUNE_DECODE_STREAMS, TUNE_AM_DECODE_STREAMS, TUNE_VERDICT_LAG, TUNE_SYNC_PHASES, TUNE_FWD_SEGMENTS, TUNE_FWD_WARM, TUNE_AM_SEGMENTS, TUNE_DECODE_CUS, TUNE_DECODE_PRIORITY, TUNE_AM_WARM, TUNE_MIXFFT_SYMS, TUNE_DEFER_WAIT, TUNE_TRACEBACK_WALK, TUNE_SYNC_LANES, TUNE_DIRECT_DECIMATE, TUNE_EARLY_FLUSH_KB, TUNE_SEAM_PREPARE, TUNE_NCO_EXACT, TUNE_FLOW_MIN, TUNE_LOOP_EXACT, TUNE_HOST_CAPTURE, TUNE_FOLD_REPORT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21
 MATH_REF_SINCOSF, MATH_REF_ATAN2F, MATH_FAST_SINCOS, MATH_FAST_SINCOS_REDUCED, MATH_FAST_ATAN2, MATH_SMALL_COS_SIN, MATH_SMALL_ATAN = range(7)   # NRSC5HIP_MATH_*

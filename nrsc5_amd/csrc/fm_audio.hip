@@ -1,0 +1,398 @@
+// Analog FM audio, host side (include/nrsc5hip.h, "analog FM audio"): the filter design in double, the object's buffers and the C ABI.
+// The kernels are in k_fm_audio.hip; the definition is DESIGN.md (o).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+#include <new>
+#include <vector>
+#include "nrsc5hip.h"
+#include "host_util.h"
+#include "fm_audio.h"
+
+using namespace nrsc5::fm;
+
+namespace {
+
+constexpr double FS = 744187.5, FS1 = FS / 2;
+constexpr double PASS_A = 95e3, STOP_A = 129361.0, ATT_A = 80.0;     // channel filter: passband edge, first primary-main carrier, design target
+constexpr double PASS_B = 15e3, STOP_B = 19e3, ATT_B = 66.0;          // audio prototype at 16 Fs1
+constexpr double EQ_F0 = 28000.0, EQ_F1 = 48000.0;                    // the droop equaliser is exact at these two frequencies
+constexpr int MAX_CHANNELS = 512;
+constexpr long long KEEP_MAX_BLOCKS = 2 * W + 3;
+
+double bessel_i0(double x)
+{
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < 500; k++) {
+        t *= (x / (2.0 * k)) * (x / (2.0 * k));
+        s += t;
+        if (t < 1e-18 * s) break;
+    }
+    return s;
+}
+
+double sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
+
+// Kaiser-windowed sinc, fc in cycles per sample, symmetric about (taps - 1) / 2
+std::vector<double> kaiser_lowpass(int taps, double fc, double att_db)
+{
+    const double beta = 0.1102 * (att_db - 8.7), i0b = bessel_i0(beta);
+    std::vector<double> h(taps);
+    for (int i = 0; i < taps; i++) {
+        const double tau = i - 0.5 * (taps - 1), u = 2.0 * tau / (taps - 1);
+        const double w = fabs(u) < 1.0 ? bessel_i0(beta * sqrt(1.0 - u * u)) / i0b : (fabs(u) == 1.0 ? 1.0 / i0b : 0.0);
+        h[i] = 2.0 * fc * sinc(2.0 * fc * tau) * w;
+    }
+    return h;
+}
+
+}  // namespace
+
+struct nrsc5hip_fm {
+    int device = 0, nchan = 0, tb = 0;
+    double deemphasis_us = 75.0;
+    float pilot_min = 0.03f, aq = 0, bq = 0, wsum = 0;
+    std::vector<float> ha, tab, scale;                       // tab: host copy [PHASES][tb]
+    hipStream_t stream = nullptr;
+    float *d_ha = nullptr, *d_tab = nullptr, *d_win = nullptr, *d_scale = nullptr, *d_pilot = nullptr;
+    float2 *d_cs = nullptr;
+    int *d_hist[2] = {nullptr, nullptr};
+    float *d_d[2] = {nullptr, nullptr}; long long d_cap = 0, d_base = 0;     // d[m], m in [d_base, m_total), of channel c at d_d[cur][c * d_cap + m - d_base]
+    float2 *d_p[2] = {nullptr, nullptr}; long long p_cap = 0, p_base = 0;    // block sums [p_base, blocks)
+    int cur = 0;
+    unsigned long long *d_clips = nullptr;
+    long long n_total = 0, m_total = 0, blocks = 0, audio_blocks = 0;        // input samples, d samples, complete pilot blocks, audio blocks delivered
+};
+
+namespace {
+
+void free_fm(nrsc5hip_fm *f)
+{
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    (void)hipFree(f->d_ha); (void)hipFree(f->d_tab); (void)hipFree(f->d_win); (void)hipFree(f->d_scale); (void)hipFree(f->d_pilot); (void)hipFree(f->d_cs);
+    for (int i = 0; i < 2; i++) { (void)hipFree(f->d_hist[i]); (void)hipFree(f->d_d[i]); (void)hipFree(f->d_p[i]); }
+    (void)hipFree(f->d_clips);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
+}
+
+int fm_zero_state(nrsc5hip_fm *f)
+{
+    HIPCHK(hipMemsetAsync(f->d_hist[0], 0, sizeof(int) * HIST * f->nchan, f->stream));
+    HIPCHK(hipMemsetAsync(f->d_hist[1], 0, sizeof(int) * HIST * f->nchan, f->stream));
+    HIPCHK(hipMemsetAsync(f->d_clips, 0, sizeof(unsigned long long) * 2 * f->nchan, f->stream));
+    HIPCHK(hipMemsetAsync(f->d_pilot, 0, sizeof(float) * 2 * f->nchan, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0;
+    return 0;
+}
+
+struct Counts { long long n1, m1, b1, a1; };
+Counts counts_after(const nrsc5hip_fm *f, long long n_in)
+{
+    Counts c;
+    c.n1 = f->n_total + n_in; c.m1 = (c.n1 + 1) >> 1; c.b1 = c.m1 / BLOCK; c.a1 = c.b1 > W ? c.b1 - W : 0;
+    return c;
+}
+
+// room for d[d_base, m1) and p[p_base, b1): grown once the work queued on `s` has finished; what is kept moves over
+int fm_reserve(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1)
+{
+    const long long need_d = m1 - f->d_base, need_p = b1 - f->p_base;
+    if (need_d > f->d_cap) {
+        HIPCHK(hipStreamSynchronize(s));
+        const long long cap = need_d + need_d / 4 + 4096;
+        float *nd[2] = {nullptr, nullptr};
+        HIPCHK(hipMalloc(&nd[0], sizeof(float) * (size_t)cap * f->nchan));
+        if (hipMalloc(&nd[1], sizeof(float) * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(nd[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (d, %lld per channel)", cap); }
+        const long long have = f->m_total - f->d_base;
+        if (have > 0)
+            HIPCHK(hipMemcpy2DAsync(nd[f->cur], sizeof(float) * cap, f->d_d[f->cur], sizeof(float) * f->d_cap, sizeof(float) * have, f->nchan, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        (void)hipFree(f->d_d[0]); (void)hipFree(f->d_d[1]);
+        f->d_d[0] = nd[0]; f->d_d[1] = nd[1]; f->d_cap = cap;
+    }
+    if (need_p > f->p_cap) {
+        HIPCHK(hipStreamSynchronize(s));
+        const long long cap = need_p + need_p / 4 + 64;
+        float2 *np[2] = {nullptr, nullptr};
+        HIPCHK(hipMalloc(&np[0], sizeof(float2) * (size_t)cap * f->nchan));
+        if (hipMalloc(&np[1], sizeof(float2) * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(np[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (pilot sums)"); }
+        const long long have = f->blocks - f->p_base;
+        if (have > 0)
+            HIPCHK(hipMemcpy2DAsync(np[f->cur], sizeof(float2) * cap, f->d_p[f->cur], sizeof(float2) * f->p_cap, sizeof(float2) * have, f->nchan, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        (void)hipFree(f->d_p[0]); (void)hipFree(f->d_p[1]);
+        f->d_p[0] = np[0]; f->d_p[1] = np[1]; f->p_cap = cap;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int nrsc5::fm_nchan(const nrsc5hip_fm *f) { return f->nchan; }
+int nrsc5::fm_device(const nrsc5hip_fm *f) { return f->device; }
+
+namespace {
+int fm_check_input(const nrsc5hip_fm *f, const void *dev_in, long long in_stride_elems, long long n_in)
+{
+    if (n_in < 0 || (n_in > 0 && !dev_in)) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
+    if (((uintptr_t)dev_in & 3) || (in_stride_elems & 1)) FAIL(NRSC5HIP_EINVAL, "input not aligned to 4 bytes (in_stride_elems %lld)", in_stride_elems);
+    if (f->nchan > 1 && in_stride_elems < 2 * n_in) FAIL(NRSC5HIP_EINVAL, "in_stride_elems %lld < 2 * n_in %lld", in_stride_elems, n_in);
+    return 0;
+}
+}  // namespace
+
+int nrsc5::fm_check(nrsc5hip_fm *f, long long n_in, const int16_t *dev_out, long long out_stride_elems, long long out_capacity, long long *n_out)
+{
+    const Counts c = counts_after(f, n_in);
+    const long long nout = BLOCK_OUT * (c.a1 - f->audio_blocks);
+    if (nout > 0 && !dev_out) FAIL(NRSC5HIP_EINVAL, "null output");
+    if (out_capacity < 0 || (f->nchan > 1 && out_stride_elems < 2 * out_capacity))
+        FAIL(NRSC5HIP_EINVAL, "out_stride_elems %lld < 2 * out_capacity %lld", out_stride_elems, out_capacity);
+    if (nout > out_capacity) FAIL(NRSC5HIP_EOVERFLOW, "push of %lld samples yields %lld audio frames per channel > out_capacity %lld", n_in, nout, out_capacity);
+    if ((c.m1 - f->m_total + FT - 1) / FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "push too large (%lld samples)", n_in);
+    if (n_out) *n_out = nout;
+    return 0;
+}
+
+// front, pilot sums, audio and the kept tails on `stream`; no host wait (but for a buffer that has to grow)
+int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long long in_stride, long long n_in, int16_t *out, long long out_stride)
+{
+    if (n_in <= 0) return 0;
+    const Counts c = counts_after(f, n_in);
+    int rc = fm_reserve(f, s, c.m1, c.b1);
+    if (rc) return rc;
+    float *d = f->d_d[f->cur]; float2 *p = f->d_p[f->cur];
+    if (c.m1 > f->m_total) {
+        FrontArgs a;
+        a.in = dev_in; a.in_stride = in_stride; a.n0 = f->n_total; a.n_in = n_in; a.hist = f->d_hist[f->cur]; a.ha = f->d_ha;
+        a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.m0 = f->m_total; a.m_count = c.m1 - f->m_total;
+        launch_front(s, (int)((a.m_count + FT - 1) / FT), f->nchan, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (c.b1 > f->blocks) {
+        PilotArgs a;
+        a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.cs = f->d_cs; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.j0 = f->blocks;
+        launch_pilot(s, (int)(c.b1 - f->blocks), f->nchan, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (c.a1 > f->audio_blocks) {
+        AudioArgs a;
+        a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.cs = f->d_cs;
+        a.tab = f->d_tab; a.tb = f->tb; a.win = f->d_win; a.wsum = f->wsum; a.aq = f->aq; a.bq = f->bq; a.pilot_min = f->pilot_min; a.scale = f->d_scale;
+        a.j0 = f->audio_blocks; a.k0 = BLOCK_OUT * f->audio_blocks; a.out = out; a.out_stride = out_stride; a.clips = f->d_clips; a.pilot = f->d_pilot;
+        launch_audio(s, (int)(c.a1 - f->audio_blocks), f->nchan, a);
+        HIPCHK(hipGetLastError());
+    }
+    // what the next call needs: d from the first tap of audio block a1, the block sums from a1 - W, the last HIST input samples
+    long long d_base = (long long)BLOCK * c.a1 - f->tb - 1, p_base = c.a1 - W;
+    if (d_base < 0) d_base = 0;
+    if (p_base < 0) p_base = 0;
+    KeepArgs k;
+    k.d_old = d; k.d_new = f->d_d[f->cur ^ 1]; k.d_stride = f->d_cap; k.d_shift = d_base - f->d_base; k.d_count = c.m1 - d_base;
+    k.p_old = p; k.p_new = f->d_p[f->cur ^ 1]; k.p_stride = f->p_cap; k.p_shift = p_base - f->p_base; k.p_count = c.b1 - p_base;
+    k.in = dev_in; k.in_stride = in_stride; k.n0 = f->n_total; k.n_in = n_in; k.hist_old = f->d_hist[f->cur]; k.hist_new = f->d_hist[f->cur ^ 1];
+    launch_keep(s, f->nchan, k);
+    HIPCHK(hipGetLastError());
+    f->cur ^= 1; f->d_base = d_base; f->p_base = p_base;
+    f->n_total = c.n1; f->m_total = c.m1; f->blocks = c.b1; f->audio_blocks = c.a1;
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_create(const nrsc5hip_fm_config *cfg, nrsc5hip_fm **out)
+{
+    if (!cfg || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    *out = nullptr;
+    if (cfg->nchan < 1 || cfg->nchan > MAX_CHANNELS) FAIL(NRSC5HIP_EINVAL, "nchan %d out of range 1..%d", cfg->nchan, MAX_CHANNELS);
+    if (cfg->deemphasis_us != 75.0 && cfg->deemphasis_us != 50.0 && cfg->deemphasis_us != 0.0)
+        FAIL(NRSC5HIP_EINVAL, "deemphasis_us %g: 75, 50 or 0", cfg->deemphasis_us);
+    if (!(cfg->pilot_min >= 0.0) || !(cfg->pilot_min <= 1.0)) FAIL(NRSC5HIP_EINVAL, "pilot_min %g outside 0..1", cfg->pilot_min);
+    for (int k = 0; k < cfg->nchan; k++)
+        if (cfg->gain && !std::isfinite(cfg->gain[k])) FAIL(NRSC5HIP_EINVAL, "channel %d: gain not finite", k);
+
+    nrsc5hip_fm *f = new (std::nothrow) nrsc5hip_fm;
+    if (!f) FAIL(NRSC5HIP_ENOMEM, "out of host memory");
+    f->device = cfg->device; f->nchan = cfg->nchan; f->deemphasis_us = cfg->deemphasis_us;
+    f->pilot_min = cfg->pilot_min == 0.0 ? 0.03f : (float)cfg->pilot_min;
+    for (int k = 0; k < cfg->nchan; k++) f->scale.push_back((float)(32767.0 * (cfg->gain ? cfg->gain[k] : 1.0f)));
+    {   // channel filter, DC gain 1
+        std::vector<double> h = kaiser_lowpass(TA, 0.5 * (PASS_A + STOP_A) / FS, ATT_A);
+        double sum = 0;
+        for (double v : h) sum += v;
+        for (double v : h) f->ha.push_back((float)(v / sum));
+    }
+    {   // droop equaliser (a, b, a): b + 2 a cos(w) = 1 / sinc(f / Fs1) at EQ_F0 and EQ_F1
+        const double r0 = 1.0 / sinc(EQ_F0 / FS1), r1 = 1.0 / sinc(EQ_F1 / FS1), c0 = cos(2 * M_PI * EQ_F0 / FS1), c1 = cos(2 * M_PI * EQ_F1 / FS1);
+        const double a = (r0 - r1) / (2 * (c0 - c1));
+        f->aq = (float)a; f->bq = (float)(r0 - 2 * a * c0);
+    }
+    {   // audio prototype at 16 Fs1: Kaiser lowpass convolved with the sampled one-pole, DC gain 16
+        const double fv = PHASES * FS1, dw = 2 * M_PI * (STOP_B - PASS_B) / fv;
+        const int nk = (int)ceil((ATT_B - 7.95) / (2.285 * dw)) + 1;
+        std::vector<double> g = kaiser_lowpass(nk, 0.5 * (PASS_B + STOP_B) / fv, ATT_B);
+        if (cfg->deemphasis_us > 0) {
+            const double tf = cfg->deemphasis_us * 1e-6 * fv;
+            const int ne = (int)ceil(30.0 * log(2.0) * tf);                 // exp(-v / tf) < 2^-30 from here on
+            std::vector<double> e(ne), y(nk + ne - 1, 0.0);
+            for (int v = 0; v < ne; v++) e[v] = exp(-v / tf);
+            e[0] = 0.5;                                                     // the step at t = 0 sampled at its mid value
+            for (int i = 0; i < nk; i++)
+                for (int v = 0; v < ne; v++) y[i + v] += g[i] * e[v];
+            g.swap(y);
+        }
+        double sum = 0;
+        for (double v : g) sum += v;
+        f->tb = ((int)g.size() + PHASES - 1) / PHASES;
+        f->tab.assign((size_t)PHASES * f->tb, 0.0f);
+        for (size_t v = 0; v < g.size(); v++) f->tab[(v % PHASES) * f->tb + v / PHASES] = (float)(g[v] * PHASES / sum);
+    }
+    std::vector<float> dev_tab((size_t)PHASES * f->tb), win(2 * W + 1);
+    for (int p = 0; p < PHASES; p++)
+        for (int j = 0; j < f->tb; j++) dev_tab[(size_t)j * PHASES + p] = f->tab[(size_t)p * f->tb + j];
+    double wsum = 0;
+    for (int w = -W; w <= W; w++) { const double v = 0.5 * (1 + cos(M_PI * w / (W + 1))); win[w + W] = (float)v; wsum += v; }
+    f->wsum = (float)wsum;
+    std::vector<float2> cs(PILOT_DEN);
+    for (int k = 0; k < PILOT_DEN; k++) { const double t = 2 * M_PI * k / PILOT_DEN; cs[k] = make_float2((float)cos(t), (float)sin(t)); }
+
+    nrsc5::DeviceGuard guard(f->device);
+#define CREATE_CHK(expr) HIPCHK_OR(expr, free_fm(f))
+    CREATE_CHK(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    CREATE_CHK(hipMalloc(&f->d_ha, sizeof(float) * TA));
+    CREATE_CHK(hipMalloc(&f->d_tab, sizeof(float) * dev_tab.size()));
+    CREATE_CHK(hipMalloc(&f->d_win, sizeof(float) * win.size()));
+    CREATE_CHK(hipMalloc(&f->d_scale, sizeof(float) * f->nchan));
+    CREATE_CHK(hipMalloc(&f->d_pilot, sizeof(float) * 2 * f->nchan));
+    CREATE_CHK(hipMalloc(&f->d_cs, sizeof(float2) * PILOT_DEN));
+    CREATE_CHK(hipMalloc(&f->d_hist[0], sizeof(int) * HIST * f->nchan));
+    CREATE_CHK(hipMalloc(&f->d_hist[1], sizeof(int) * HIST * f->nchan));
+    CREATE_CHK(hipMalloc(&f->d_clips, sizeof(unsigned long long) * 2 * f->nchan));
+    f->d_cap = KEEP_MAX_BLOCKS * BLOCK + f->tb + 65536;
+    f->p_cap = KEEP_MAX_BLOCKS + 256;
+    for (int i = 0; i < 2; i++) {
+        CREATE_CHK(hipMalloc(&f->d_d[i], sizeof(float) * (size_t)f->d_cap * f->nchan));
+        CREATE_CHK(hipMalloc(&f->d_p[i], sizeof(float2) * (size_t)f->p_cap * f->nchan));
+    }
+    CREATE_CHK(hipMemcpy(f->d_ha, f->ha.data(), sizeof(float) * TA, hipMemcpyHostToDevice));
+    CREATE_CHK(hipMemcpy(f->d_tab, dev_tab.data(), sizeof(float) * dev_tab.size(), hipMemcpyHostToDevice));
+    CREATE_CHK(hipMemcpy(f->d_win, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice));
+    CREATE_CHK(hipMemcpy(f->d_scale, f->scale.data(), sizeof(float) * f->nchan, hipMemcpyHostToDevice));
+    CREATE_CHK(hipMemcpy(f->d_cs, cs.data(), sizeof(float2) * PILOT_DEN, hipMemcpyHostToDevice));
+#undef CREATE_CHK
+    int rc = fm_zero_state(f);
+    if (rc) { free_fm(f); return rc; }
+    *out = f;
+    return 0;
+}
+
+extern "C" void nrsc5hip_fm_destroy(nrsc5hip_fm *f)
+{
+    if (!f) return;
+    nrsc5::DeviceGuard guard(f->device);
+    free_fm(f);
+}
+
+extern "C" int nrsc5hip_fm_reset(nrsc5hip_fm *f)
+{
+    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
+    nrsc5::DeviceGuard guard(f->device);
+    HIPCHK(hipStreamSynchronize(f->stream));
+    return fm_zero_state(f);
+}
+
+extern "C" int nrsc5hip_fm_info(nrsc5hip_fm *f, int *taps_channel, int *taps_audio, int *phases, long long *latency_in)
+{
+    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
+    if (taps_channel) *taps_channel = TA;
+    if (taps_audio) *taps_audio = f->tb;
+    if (phases) *phases = PHASES;
+    if (latency_in) *latency_in = 2LL * BLOCK * (W + 1) - 1;
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_taps(nrsc5hip_fm *f, float *channel, float *audio)
+{
+    if (!f || (!channel && !audio)) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (channel) memcpy(channel, f->ha.data(), sizeof(float) * TA);
+    if (audio) memcpy(audio, f->tab.data(), sizeof(float) * f->tab.size());
+    return 0;
+}
+
+extern "C" long long nrsc5hip_fm_outputs_for(nrsc5hip_fm *f, long long n_in)
+{
+    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
+    if (n_in < 0) FAIL(NRSC5HIP_EINVAL, "n_in %lld negative", n_in);
+    return BLOCK_OUT * (counts_after(f, n_in).a1 - f->audio_blocks);
+}
+
+extern "C" int nrsc5hip_fm_process(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, int16_t *dev_out,
+                                   long long out_stride_elems, long long out_capacity, long long *n_out)
+{
+    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
+    long long nout = 0;
+    int rc = fm_check_input(f, dev_in, in_stride_elems, n_in);
+    if (rc) return rc;
+    rc = nrsc5::fm_check(f, n_in, dev_out, out_stride_elems, out_capacity, &nout);
+    if (rc) return rc;
+    nrsc5::DeviceGuard guard(f->device);
+    rc = nrsc5::fm_launch(f, f->stream, dev_in, in_stride_elems, n_in, dev_out, out_stride_elems);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(f->stream));               // outputs complete, dev_in no longer read
+    if (n_out) *n_out = nout;
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_clip_counts(nrsc5hip_fm *f, long long *counts)
+{
+    if (!f || !counts) FAIL(NRSC5HIP_EINVAL, "null argument");
+    nrsc5::DeviceGuard guard(f->device);
+    HIPCHK(hipStreamSynchronize(f->stream));
+    HIPCHK(hipMemcpy(counts, f->d_clips, sizeof(long long) * 2 * f->nchan, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_pilot(nrsc5hip_fm *f, float *level, int *stereo)
+{
+    if (!f || (!level && !stereo)) FAIL(NRSC5HIP_EINVAL, "null argument");
+    nrsc5::DeviceGuard guard(f->device);
+    HIPCHK(hipStreamSynchronize(f->stream));
+    std::vector<float> v(2 * (size_t)f->nchan);
+    HIPCHK(hipMemcpy(v.data(), f->d_pilot, sizeof(float) * v.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < f->nchan; k++) {
+        if (level) level[k] = v[2 * k];
+        if (stereo) stereo[k] = v[2 * k + 1] != 0.0f;
+    }
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_fm_mpx(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *d_out, float *psum_out)
+{
+    if (!f || !d_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (n_in <= 0) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
+    int rc = fm_check_input(f, dev_in, in_stride_elems, n_in);
+    if (rc) return rc;
+    const long long m1 = (n_in + 1) >> 1, b1 = m1 / BLOCK;
+    if ((m1 + FT - 1) / FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
+    nrsc5::DeviceGuard guard(f->device);
+    nrsc5::DevTmp d, p, hist;
+    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * f->nchan));
+    HIPCHK(hipMalloc(&p.p, sizeof(float2) * (size_t)(b1 + 1) * f->nchan));
+    HIPCHK(hipMalloc(&hist.p, sizeof(int) * HIST * f->nchan));
+    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * HIST * f->nchan, f->stream));
+    FrontArgs a;
+    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
+    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
+    launch_front(f->stream, (int)((m1 + FT - 1) / FT), f->nchan, a);
+    HIPCHK(hipGetLastError());
+    if (b1 > 0) {
+        PilotArgs q;
+        q.d = (const float *)d.p; q.d_stride = m1; q.d_base = 0; q.cs = f->d_cs; q.p = (float2 *)p.p; q.p_stride = b1; q.p_base = 0; q.j0 = 0;
+        launch_pilot(f->stream, (int)b1, f->nchan, q);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(f->stream));
+    HIPCHK(hipMemcpy(d_out, d.p, sizeof(float) * (size_t)m1 * f->nchan, hipMemcpyDeviceToHost));
+    if (psum_out && b1 > 0) HIPCHK(hipMemcpy(psum_out, p.p, sizeof(float2) * (size_t)b1 * f->nchan, hipMemcpyDeviceToHost));
+    return 0;
+}

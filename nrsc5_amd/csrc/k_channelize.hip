@@ -20,6 +20,7 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "host_util.h"
+#include "fm_audio.h"
 
 namespace {
 
@@ -411,12 +412,21 @@ extern "C" int nrsc5hip_chan_clip_counts(nrsc5hip_chan *c, long long *counts)
     return 0;
 }
 
-extern "C" int nrsc5hip_chan_feed(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, const void *dev_in, long long n_in)
+namespace {
+// nrsc5hip_chan_feed; with fm, the demodulator then reads the staged outputs on the channelizer's stream, in front of the next push's write
+int chan_feed_impl(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, const void *dev_in, long long n_in, nrsc5hip_fm *fm,
+                   int16_t *dev_audio, long long audio_stride, long long audio_capacity, long long *n_audio)
 {
     if (!c || !e || !stream_ids) FAIL(NRSC5HIP_EINVAL, "null argument");
     if (n_in < 0 || (n_in > 0 && !dev_in)) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
     const long long nout = outputs_total(c, c->n_total + n_in) - c->m_total;
     if (2 * nout > 0xffffffffLL) FAIL(NRSC5HIP_EINVAL, "push too large for one append (%lld outputs)", nout);
+    if (fm) {
+        if (nrsc5::fm_nchan(fm) != c->nchan || nrsc5::fm_device(fm) != c->device)
+            FAIL(NRSC5HIP_EINVAL, "demodulator has %d channels on device %d, the channelizer %d on device %d", nrsc5::fm_nchan(fm), nrsc5::fm_device(fm), c->nchan, c->device);
+        int rc = nrsc5::fm_check(fm, nout, dev_audio, audio_stride, audio_capacity, n_audio);   // (the staging buffer: 4-byte aligned, even stride)
+        if (rc) return rc;
+    }
     nrsc5::DeviceGuard guard(c->device);
     if (nout > c->feed_cap) {                               // grow the staging buffer once the engine has read the old one
         if (c->eng_pending) { HIPCHK(hipEventSynchronize(c->ev_eng)); c->eng_pending = false; }
@@ -448,7 +458,24 @@ extern "C" int nrsc5hip_chan_feed(nrsc5hip_chan *c, nrsc5hip_engine *e, const in
         }
         HIPCHK(hipEventRecord(c->ev_eng, es));
         c->eng_pending = true;
+        if (fm) {
+            rc = nrsc5::fm_launch(fm, c->stream, c->d_feed, 2 * c->feed_cap, nout, dev_audio, audio_stride);
+            if (rc) return rc;
+        }
     }
     HIPCHK(hipStreamSynchronize(c->stream));               // dev_in no longer read when the call returns
     return 0;
+}
+}  // namespace
+
+extern "C" int nrsc5hip_chan_feed(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, const void *dev_in, long long n_in)
+{
+    return chan_feed_impl(c, e, stream_ids, dev_in, n_in, nullptr, nullptr, 0, 0, nullptr);
+}
+
+extern "C" int nrsc5hip_chan_feed_fm(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, nrsc5hip_fm *fm, const void *dev_in, long long n_in,
+                                     int16_t *dev_audio, long long audio_stride_elems, long long audio_capacity, long long *n_audio)
+{
+    if (!fm) FAIL(NRSC5HIP_EINVAL, "null demodulator");
+    return chan_feed_impl(c, e, stream_ids, dev_in, n_in, fm, dev_audio, audio_stride_elems, audio_capacity, n_audio);
 }

@@ -1,0 +1,223 @@
+// Analog FM audio of a station's 744 187.5 S/s cs16 stream (include/nrsc5hip.h, "analog FM audio"; the definition: DESIGN.md (o)).
+//
+// Every quantity is a function of absolute sample indices (x[n] = 0 for n < 0), no recurrence anywhere: any chunking gives the same bytes.
+//   k_fm_front  one workgroup = FT consecutive Fs1 outputs of one channel.  The cs16 span (new input and kept history) is staged in LDS as
+//               float2 from 4-byte loads, every work-item sums one z[m] = sum_i hA[i] x[2 m - i] (the tile one more than it emits), and the
+//               discriminator d[m] = atan2(z[m] conj z[m - 1]) goes to the channel's d buffer as float32.
+//   k_fm_pilot  one wave = one complete pilot block: p[j] = sum d[m] exp(-j phi19(m)) in a fixed order (9 terms per lane, then a butterfly),
+//               so the sum does not depend on which push completed the block.  No atomics.
+//   k_fm_audio  one workgroup = one pilot block = 64 audio outputs.  Every wave forms the smoothed pilot (33 block sums, a butterfly), the d span
+//               and the difference path 2 eq(d) sub go to LDS, and the block's 4 waves each sum a quarter of the taps of the 64 outputs for
+//               both paths from one table load; wave 0 adds the quarters in order, rounds, clamps and writes L, R.
+//   k_fm_keep   what the next call needs: the tail of d, of the block sums and of the input (as k_chan_history).
+// The pilot phase (608 m mod 11907) indexes a table of 11907 (cos, sin) pairs computed in double on the host: exact to float32 rounding,
+// the same bits on the device and in the CPU twin.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "fm_audio.h"
+#include "fastmath.h"
+
+namespace nrsc5 {
+namespace fm {
+namespace {
+
+__device__ __forceinline__ float2 unpack_cs16(int v) { return make_float2((float)(short)(v & 0xffff), (float)(short)(v >> 16)); }
+
+// sample at absolute index n of channel ch, n < n0 + n_in
+__device__ __forceinline__ int load_x(const FrontArgs &a, const int *in32, const int *hist, long long n)
+{
+    if (n >= a.n0) return n < a.n0 + a.n_in ? in32[n - a.n0] : 0;
+    const long long h = n - (a.n0 - HIST);
+    return h >= 0 ? hist[h] : 0;                              // (n >= 0 never reaches back further; n < 0 reads the zeros the history starts with)
+}
+
+__global__ __launch_bounds__(256) void k_fm_front(FrontArgs a)
+{
+    HIP_DYNAMIC_SHARED(float2, sm);
+    float2 *xs = sm, *zs = sm + (2 * FT + TA);
+    const int ch = blockIdx.y;
+    const long long mt0 = a.m0 + (long long)blockIdx.x * FT;
+    const long long left = a.m0 + a.m_count - mt0;
+    const int cnt = left < FT ? (int)left : FT;
+    if (cnt <= 0) return;
+    const long long n_lo = 2 * (mt0 - 1) - (TA - 1);          // x index of xs[0]; xs[2 q + TA - 1 - i] = x[2 (mt0 - 1 + q) - i]
+    const int span = 2 * cnt + TA;
+    const int *in32 = (const int *)(a.in + (long long)ch * a.in_stride);
+    const int *hist = a.hist + (long long)ch * HIST;
+    for (int k = threadIdx.x; k < span; k += blockDim.x) {
+        const long long n = n_lo + k;
+        xs[k] = n < 0 ? make_float2(0.0f, 0.0f) : unpack_cs16(load_x(a, in32, hist, n));
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q <= cnt; q += blockDim.x) {    // z[mt0 - 1 + q]
+        const float2 *v = xs + 2 * q + TA - 1;
+        float re = 0.0f, im = 0.0f;
+#pragma unroll 16                                            // 16 taps per scalar load; unrolled whole, the 112 taps spill out of the SGPRs
+        for (int i = 0; i < TA; i++) {
+            const float t = a.ha[i];
+            const float2 x = v[-i];
+            re = fmaf(x.x, t, re); im = fmaf(x.y, t, im);
+        }
+        zs[q] = make_float2(re, im);
+    }
+    __syncthreads();
+    const int q = threadIdx.x + 1;
+    if (q <= cnt) {
+        const long long m = mt0 - 1 + q;
+        const float2 z = zs[q], zp = zs[q - 1];
+        const float re = fmaf(z.x, zp.x, z.y * zp.y), im = fmaf(z.y, zp.x, -(z.x * zp.y));      // z conj(zp)
+        float d = 0.0f;
+        if (m > 0 && !(re == 0.0f && im == 0.0f)) d = ref_atan2f(im, re) * DEV_SCALE;
+        a.d[(long long)ch * a.d_stride + (m - a.d_base)] = d;
+    }
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);  // a + b == b + a: every lane ends with the same bits
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_fm_pilot(PilotArgs a)
+{
+    const int ch = blockIdx.y;
+    const long long j = a.j0 + blockIdx.x;
+    const float *d = a.d + (long long)ch * a.d_stride + ((long long)BLOCK * j - a.d_base);
+    float re = 0.0f, im = 0.0f;
+    for (int mi = threadIdx.x; mi < BLOCK; mi += 64) {
+        const long long m = (long long)BLOCK * j + mi;
+        const float2 t = a.cs[(int)((PILOT_NUM * m) % PILOT_DEN)];
+        const float v = d[mi];
+        re = fmaf(v, t.x, re); im = fmaf(-v, t.y, im);       // d exp(-j phi)
+    }
+    re = wave_sum(re); im = wave_sum(im);
+    if (threadIdx.x == 0) a.p[(long long)ch * a.p_stride + (j - a.p_base)] = make_float2(re, im);
+}
+
+__global__ __launch_bounds__(256) void k_fm_audio(AudioArgs a)
+{
+    HIP_DYNAMIC_SHARED(float, lds);
+    const int tb = a.tb, ch = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    float *ds = lds;                                         // [tb + 542]: d[mlo ..], mlo = 540 j - tb - 1
+    float *dd = lds + (tb + 542);                            // [tb + 540]: the difference path at m = mlo + 1 ..
+    float *part = dd + (tb + 540);                           // [4][64][2]
+    const long long j = a.j0 + blockIdx.x;
+    const long long mlo = (long long)BLOCK * j - tb - 1;
+
+    // the smoothed pilot: the same loads, the same order in every wave
+    float pr = 0.0f, pi = 0.0f;
+    if (lane <= 2 * W) {
+        const long long jb = j + lane - W;
+        if (jb >= 0) {
+            const float2 v = a.p[(long long)ch * a.p_stride + (jb - a.p_base)];
+            const float w = a.win[lane];
+            pr = v.x * w; pi = v.y * w;
+        }
+    }
+    pr = wave_sum(pr); pi = wave_sum(pi);
+    const float mag = sqrtf(pr * pr + pi * pi);
+    const float level = 2.0f * mag / (float)BLOCK / a.wsum;
+    const bool stereo = level >= a.pilot_min;
+
+    const float *d = a.d + (long long)ch * a.d_stride;
+    for (int i = tid; i < tb + 542; i += 256) {
+        const long long m = mlo + i;
+        ds[i] = m >= 0 ? d[m - a.d_base] : 0.0f;
+    }
+    __syncthreads();
+    if (stereo) {
+        const float ur = pr / mag, ui = pi / mag;            // exp(j 2 theta) = -(p / |p|)^2: the pilot is a sine
+        const float c2 = -(ur * ur - ui * ui), s2 = -(2.0f * ur * ui);
+        for (int i = tid; i < tb + 540; i += 256) {
+            const long long m = mlo + 1 + i;
+            float v = 0.0f;
+            if (m >= 0) {
+                const float2 t = a.cs[(int)((2 * PILOT_NUM * m) % PILOT_DEN)];
+                const float sub = t.y * c2 + t.x * s2;       // sin(2 phi19(m) + 2 theta)
+                v = 2.0f * (a.aq * ds[i] + a.bq * ds[i + 1] + a.aq * ds[i + 2]) * sub;
+            }
+            dd[i] = v;
+        }
+    }
+    __syncthreads();
+
+    const int qtr = tid >> 6;
+    const long long k = (long long)BLOCK_OUT * j + lane;
+    const long long t16 = (long long)T_NUM * k;
+    const int base = (int)((t16 >> 4) - mlo), ph = (int)(t16 & 15);
+    const int tq = (tb + 3) / 4, j0 = qtr * tq, j1 = min(tb, j0 + tq);
+    const float *tab = a.tab + ph;
+    float s = 0.0f, dl = 0.0f;
+    if (stereo) {
+        for (int jj = j0; jj < j1; jj++) {
+            const float t = tab[jj * PHASES];
+            s = fmaf(t, ds[base - jj], s);
+            dl = fmaf(t, dd[base - 1 - jj], dl);
+        }
+    } else {
+        for (int jj = j0; jj < j1; jj++) s = fmaf(tab[jj * PHASES], ds[base - jj], s);
+    }
+    part[(qtr * 64 + lane) * 2] = s; part[(qtr * 64 + lane) * 2 + 1] = dl;
+    __syncthreads();
+    if (tid < 64) {
+        float S = part[lane * 2], D = part[lane * 2 + 1];
+        for (int q = 1; q < 4; q++) { S += part[(q * 64 + lane) * 2]; D += part[(q * 64 + lane) * 2 + 1]; }
+        const float g = a.scale[ch];
+        float yl = rintf((S + D) * g), yr = rintf((S - D) * g);
+        int cl = 0, cr = 0;
+        if (yl > 32767.0f) { yl = 32767.0f; cl = 1; } else if (yl < -32768.0f) { yl = -32768.0f; cl = 1; }
+        if (yr > 32767.0f) { yr = 32767.0f; cr = 1; } else if (yr < -32768.0f) { yr = -32768.0f; cr = 1; }
+        const unsigned long long bl = __ballot(cl), br = __ballot(cr);
+        int16_t *o = a.out + (long long)ch * a.out_stride + 2 * (k - a.k0);
+        o[0] = (int16_t)(int)yl; o[1] = (int16_t)(int)yr;
+        if (tid == 0) {
+            if (bl) atomicAdd(a.clips + 2 * ch, (unsigned long long)__popcll(bl));
+            if (br) atomicAdd(a.clips + 2 * ch + 1, (unsigned long long)__popcll(br));
+            if (blockIdx.x == gridDim.x - 1) { a.pilot[2 * ch] = level; a.pilot[2 * ch + 1] = stereo ? 1.0f : 0.0f; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fm_keep(KeepArgs a)
+{
+    const int ch = blockIdx.y;
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    for (long long i = i0; i < a.d_count; i += step) a.d_new[ch * a.d_stride + i] = a.d_old[ch * a.d_stride + i + a.d_shift];
+    for (long long i = i0; i < a.p_count; i += step) a.p_new[ch * a.p_stride + i] = a.p_old[ch * a.p_stride + i + a.p_shift];
+    if (i0 < HIST) {                                         // absolute samples [n1 - HIST, n1), n1 = n0 + n_in
+        const long long n = a.n0 + a.n_in - HIST + i0;
+        int v;
+        if (n >= a.n0) v = ((const int *)(a.in + (long long)ch * a.in_stride))[n - a.n0];
+        else v = a.hist_old[ch * HIST + (n - (a.n0 - HIST))];
+        a.hist_new[ch * HIST + i0] = v;
+    }
+}
+
+}  // namespace
+
+void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a)
+{
+    hipLaunchKernelGGL(k_fm_front, dim3(tiles, nchan), dim3(256), sizeof(float2) * (2 * FT + TA + FT + 1), s, a);
+}
+
+void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a)
+{
+    hipLaunchKernelGGL(k_fm_pilot, dim3(blocks, nchan), dim3(64), 0, s, a);
+}
+
+void launch_audio(hipStream_t s, int blocks, int nchan, const AudioArgs &a)
+{
+    hipLaunchKernelGGL(k_fm_audio, dim3(blocks, nchan), dim3(256), sizeof(float) * (2 * a.tb + 542 + 540 + 512), s, a);
+}
+
+void launch_keep(hipStream_t s, int nchan, const KeepArgs &a)
+{
+    long long n = a.d_count > a.p_count ? a.d_count : a.p_count;
+    if (n < HIST) n = HIST;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(k_fm_keep, dim3((unsigned)blocks, nchan), dim3(256), 0, s, a);
+}
+
+}  // namespace fm
+}  // namespace nrsc5

@@ -18,7 +18,7 @@ if _AB_LIB:
     DEFAULT_LIB = _AB_LIB
 
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
-from .abi import _Config, _ChanConfig, _ScanConfig
+from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
                         sis_utf8, sis_text, _sis_device_info, sis_event_fields, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
 
@@ -169,6 +169,19 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_chan_process.argtypes = [vp, vp, ll, vp, ll, ll, ctypes.POINTER(ll)]
     lib.nrsc5hip_chan_clip_counts.argtypes = [vp, vp]
     lib.nrsc5hip_chan_feed.argtypes = [vp, vp, vp, vp, ll]
+    lib.nrsc5hip_chan_feed_fm.argtypes = [vp, vp, vp, vp, vp, ll, vp, ll, ll, ctypes.POINTER(ll)]
+    lib.nrsc5hip_fm_create.argtypes = [ctypes.POINTER(_FmConfig), ctypes.POINTER(vp)]
+    lib.nrsc5hip_fm_destroy.argtypes = [vp]
+    lib.nrsc5hip_fm_destroy.restype = None
+    lib.nrsc5hip_fm_reset.argtypes = [vp]
+    lib.nrsc5hip_fm_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ll)]
+    lib.nrsc5hip_fm_taps.argtypes = [vp, vp, vp]
+    lib.nrsc5hip_fm_outputs_for.argtypes = [vp, ll]
+    lib.nrsc5hip_fm_outputs_for.restype = ll
+    lib.nrsc5hip_fm_process.argtypes = [vp, vp, ll, ll, vp, ll, ll, ctypes.POINTER(ll)]
+    lib.nrsc5hip_fm_clip_counts.argtypes = [vp, vp]
+    lib.nrsc5hip_fm_pilot.argtypes = [vp, vp, vp]
+    lib.nrsc5hip_stage_fm_mpx.argtypes = [vp, vp, ll, ll, vp, vp]
     lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_scan_destroy.argtypes = [vp]
     lib.nrsc5hip_scan_destroy.restype = None
@@ -202,7 +215,9 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_chan_create", "nrsc5hip_chan_destroy", "nrsc5hip_chan_reset", "nrsc5hip_chan_info", "nrsc5hip_chan_taps",
     "nrsc5hip_chan_outputs_for", "nrsc5hip_chan_process", "nrsc5hip_chan_clip_counts", "nrsc5hip_chan_feed",
     "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",
-    "nrsc5hip_scan_spectrum", "nrsc5hip_scan_detect", "nrsc5hip_scan_detect_psd"]
+    "nrsc5hip_scan_spectrum", "nrsc5hip_scan_detect", "nrsc5hip_scan_detect_psd",
+    "nrsc5hip_fm_create", "nrsc5hip_fm_destroy", "nrsc5hip_fm_reset", "nrsc5hip_fm_info", "nrsc5hip_fm_taps", "nrsc5hip_fm_outputs_for",
+    "nrsc5hip_fm_process", "nrsc5hip_fm_clip_counts", "nrsc5hip_fm_pilot", "nrsc5hip_stage_fm_mpx", "nrsc5hip_chan_feed_fm"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -829,6 +844,102 @@ class Channelizer:
         ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
         assert ids.size == self.nchan
         self._check(self.lib.nrsc5hip_chan_feed(self._h, engine._h, ids.ctypes.data, dev_in, n_in))
+
+    def feed_fm(self, engine: "Engine", stream_ids, fm: "FmDemod", dev_in: int, n_in: int, dev_audio: int, audio_stride_elems: int, audio_capacity: int) -> int:
+        """feed(), and `fm` demodulates the same staged outputs on the device (nrsc5hip_chan_feed_fm); -> audio frames per channel"""
+        ids = np.ascontiguousarray(stream_ids, dtype=np.int32)
+        assert ids.size == self.nchan
+        n = ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_chan_feed_fm(self._h, engine._h, ids.ctypes.data, fm._h, dev_in, n_in, dev_audio, audio_stride_elems,
+                                                   audio_capacity, ctypes.byref(n)))
+        return n.value
+
+
+class FmDemod:
+    """Analog FM audio (nrsc5hip_fm_*): nchan cs16 streams at 744 187.5 S/s -> 44.1 kS/s stereo int16 frames (L, R) per channel.
+    deemphasis_us: 75, 50 or 0; pilot_min: least pilot level of a stereo block (0: the default, 0.03).  Buffers are device pointers
+    (ints) or torch tensors on the demodulator's device."""
+
+    AUDIO_RATE = FM_AUDIO_RATE
+
+    def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None):
+        self.lib = load_library(lib_path)
+        self.nchan, self.device, self.deemphasis_us = int(nchan), device, float(deemphasis_us)
+        self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), (self.nchan,)))
+        self.cfg = _FmConfig(device, self.nchan, self.deemphasis_us, float(pilot_min), None if self.gains is None else self.gains.ctypes.data)
+        self._h = ctypes.c_void_p()
+        self._check(self.lib.nrsc5hip_fm_create(ctypes.byref(self.cfg), ctypes.byref(self._h)))
+        ta, tb, ph, lat = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_fm_info(self._h, ctypes.byref(ta), ctypes.byref(tb), ctypes.byref(ph), ctypes.byref(lat)))
+        self.taps_channel, self.taps_audio, self.phases, self.latency_in = ta.value, tb.value, ph.value, lat.value
+
+    _check = Channelizer._check
+
+    def close(self):
+        if self._h:
+            self.lib.nrsc5hip_fm_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._check(self.lib.nrsc5hip_fm_reset(self._h))
+
+    def tables(self):
+        """-> (channel filter float32 [taps_channel], audio prototype float32 [phases][taps_audio]) as stored"""
+        ha = np.zeros(self.taps_channel, dtype=np.float32)
+        tab = np.zeros((self.phases, self.taps_audio), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_fm_taps(self._h, ha.ctypes.data, tab.ctypes.data))
+        return ha, tab
+
+    def outputs_for(self, n_in: int) -> int:
+        n = int(self.lib.nrsc5hip_fm_outputs_for(self._h, n_in))
+        if n < 0:
+            self._check(n)
+        return n
+
+    def clip_counts(self) -> np.ndarray:
+        """int64 [nchan][2]: clamped L and R samples since create / reset"""
+        out = np.zeros((self.nchan, 2), dtype=np.int64)
+        self._check(self.lib.nrsc5hip_fm_clip_counts(self._h, out.ctypes.data))
+        return out
+
+    def pilot(self):
+        """-> (level float32 [nchan], stereo bool [nchan]) of the last audio block delivered"""
+        level, flag = np.zeros(self.nchan, dtype=np.float32), np.zeros(self.nchan, dtype=np.int32)
+        self._check(self.lib.nrsc5hip_fm_pilot(self._h, level.ctypes.data, flag.ctypes.data))
+        return level, flag.astype(bool)
+
+    def process(self, dev_in: int, in_stride_elems: int, n_in: int, dev_out: int, out_stride_elems: int, capacity: int) -> int:
+        """raw form: channel k's n_in samples at dev_in + k * in_stride_elems, its frames to dev_out + k * out_stride_elems (int16
+        elements); -> frames per channel"""
+        n = ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_fm_process(self._h, dev_in, in_stride_elems, n_in, dev_out, out_stride_elems, capacity, ctypes.byref(n)))
+        return n.value
+
+    def process_tensor(self, x):
+        """torch int16 device tensor [nchan, n, 2] -> int16 tensor [nchan, frames, 2]"""
+        import torch
+        x = x.contiguous()
+        n_in = x.shape[1]
+        n_out = self.outputs_for(n_in)
+        out = torch.empty((self.nchan, max(n_out, 1), 2), dtype=torch.int16, device=x.device)
+        torch.cuda.current_stream(x.device).synchronize()          # the demodulator runs on its own stream
+        got = self.process(x.data_ptr(), 2 * n_in, n_in, out.data_ptr(), 2 * out.shape[1], out.shape[1])
+        assert got == n_out
+        return out[:, :n_out]
+
+    def stage_mpx(self, dev_in: int, in_stride_elems: int, n_in: int):
+        """nrsc5hip_stage_fm_mpx -> (d float32 [nchan][(n_in + 1) // 2], block sums complex64 [nchan][blocks])"""
+        m1 = (n_in + 1) // 2
+        d = np.zeros((self.nchan, m1), dtype=np.float32)
+        p = np.zeros((self.nchan, m1 // 540), dtype=np.complex64)
+        self._check(self.lib.nrsc5hip_stage_fm_mpx(self._h, dev_in, in_stride_elems, n_in, d.ctypes.data, p.ctypes.data))
+        return d, p
 
 
 def _stations(out, n: int) -> list:

@@ -2,7 +2,7 @@
 
 K hybrid-FM MP1 stations, each: clean baseband from synth_torch.modulate at 1 488 375 S/s with its own payload seed, an optional
 channel (channel.Impairments, e.g. an analog host), a carrier offset, a timing offset, the receiver-side conjugation synth / synth_torch
-apply, an FFT (zero-padding) resampler to Fs_in, a shift to +f_k and a level; the stations are summed, white noise is added and the
+apply, an optional analog FM stereo host (synth_fm), an FFT (zero-padding) resampler to Fs_in, a shift to +f_k and a level; the stations are summed, white noise is added and the
 result is quantised to cu8, cs16 or cf32.  float64 (complex128) throughout, fixed seeds."""
 from __future__ import annotations
 
@@ -27,6 +27,8 @@ class Station:
     chan: object = None                  # channel.Impairments or None
     psd: bytes | None = None             # program 0's PSD byte stream (synth_torch.payload_stream), None: flag bytes only
     pids: object = None                  # the PIDS frames to transmit, cycled ([n, 80] bits, synth.sis_frame), None: reserved-id frames only
+    host: dict | None = None             # analog FM host in the middle of the station: synth_fm.fm_carrier's programme (left, right, pilot, preemph_us, ...)
+    host_db: float = 20.0                # ... its carrier power over the total digital power, dB
 
 
 @dataclass
@@ -91,7 +93,13 @@ def capture(stations, rate, fmt: str = "cs16", n_frames: int = 3, noise_rms: flo
         n0 = sig.shape[0]
         t = torch.arange(n0, device=dev, dtype=torch.float64)
         sig = sig * torch.exp(1j * (2 * np.pi * st.cfo_hz / synth.FS_CU8) * t)
-        sig = torch.cat([torch.zeros(st.timing, dtype=torch.complex128, device=dev), sig.conj(),
+        sig = sig.conj()
+        if st.host is not None:                              # as transmitted (the conjugation above is the digital receiver's), with the station's carrier offset
+            from . import synth_fm
+            amp = float(torch.sqrt(torch.mean(torch.abs(sig) ** 2))) * 10 ** (st.host_db / 20)
+            car = synth_fm.fm_carrier(n0, fs=synth.FS_CU8, **st.host) * np.exp(-2j * np.pi * st.cfo_hz / synth.FS_CU8 * np.arange(n0))
+            sig = sig + amp * torch.from_numpy(car).to(dev)
+        sig = torch.cat([torch.zeros(st.timing, dtype=torch.complex128, device=dev), sig,
                          torch.zeros(8640, dtype=torch.complex128, device=dev)])
         y = fft_resample(sig, ratio)
         y = y[:int(sig.shape[0] * ratio)]

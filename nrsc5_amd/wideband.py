@@ -11,6 +11,8 @@ parameter as it arrives), decoded from the PIDS frames on the device (nrsc5hip_s
 --dump-hdc DIR also records every station's
 audio programs (the reference's NRSC5_EVENT_HDC packets, as `nrsc5 --dump-hdc` frames them: ADTS) into
 DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.
+--dump-analog DIR writes every station's analog FM programme, demodulated on the device (nrsc5hip_fm_*), as DIR/station<k>_<offset in Hz>_analog.wav
+(44.1 kHz, 16 bit, stereo; --deemphasis 75, 50 or 0 us) and prints one `analog frames N` line per file at the end.
 --dump-aas-files DIR writes every station's complete LOT files (album art, station logos, text files) as `nrsc5 --dump-aas-files` names them,
 DIR/station<k>_<offset in Hz>_<lot>_<name>, and prints the reference's `SIG Service:` / `Audio component:` / `Data component:` / `LOT file:` lines; the
 Station Information Guide and the files are put together on the device (nrsc5hip_aas_feed), only complete files reach the host.  FILE may be `-` (standard input, read in
@@ -62,11 +64,16 @@ class WidebandReceiver:
     ("sig", services) event and services[s] keeps it; a LOT header becomes a ("lot_header", fields) event, a complete file a ("lot", fields) event
     (eng.aas_event_fields: port, lot, size, mime, name, expiry, data), files[s][(port, lot)] keeps the last one and on_file(station, fields), if
     given, sees each; stream and packet data become ("stream" / "packet", fields) events.  No other packet reaches the host: aas[s] stays empty and
-    on_aas sees the PSD-port packets only, so the host holds what the files take however long a carousel repeats."""
+    on_aas sees the PSD-port packets only, so the host holds what the files take however long a carousel repeats.
+    analog=True: the receiver also demodulates every station's analog FM programme on the device (eng.FmDemod behind the channelizer's staged
+    outputs, nrsc5hip_chan_feed_fm: the channelized samples never visit the host; deemphasis_us 75, 50 or 0).  audio[s] collects int16 arrays
+    of shape (n, 2) -- 44.1 kS/s stereo frames L, R -- and on_audio(station, pcm), if given, sees each push's new block; stereo[s] and pilot[s]
+    hold the flag and the pilot level of the last block, and an ("analog", {"stereo", "pilot"}) event behind that station's other events of the
+    push says when the flag changes.  The demodulator looks 18 359 input samples ahead and has no flush: the last 25 ms of a session stay undelivered."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
                  programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
-                 lot_files: int = 16, on_file=None):
+                 lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -100,6 +107,12 @@ class WidebandReceiver:
         self.now_playing = [{} for _ in range(self.k)]
         self.aas = [[] for _ in range(self.k)]
         self.sis = eng.SisConsumer(self.engine, self.k) if sis else None
+        self.analog = bool(analog)
+        self.on_audio = on_audio
+        self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path) if self.analog else None
+        self.audio = [[] for _ in range(self.k)]
+        self.stereo = [False] * self.k
+        self.pilot = [0.0] * self.k
 
     @property
     def station_info(self) -> list:
@@ -183,7 +196,14 @@ class WidebandReceiver:
             self.held = int(kept.max())
             self.max_retained = max(self.max_retained, self.held)
             self.trims += 1
-        self.chan.feed(self.engine, self.ids, chunk.data_ptr(), n)     # (still too large: EOVERFLOW from the append, nothing was touched)
+        pcm = None
+        if self.analog:
+            cap = max(self.fm.outputs_for(m), 1)
+            pcm = torch.empty((self.k, cap, 2), dtype=torch.int16, device=chunk.device)
+            got = self.chan.feed_fm(self.engine, self.ids, self.fm, chunk.data_ptr(), n, pcm.data_ptr(), 2 * cap, cap)
+            pcm = pcm[:, :got].cpu().numpy()
+        else:
+            self.chan.feed(self.engine, self.ids, chunk.data_ptr(), n)     # (still too large: EOVERFLOW from the append, nothing was touched)
         self.held += m
         self.pushes += 1
         self.engine.batch_process(self.k, stream_ids=self.ids)
@@ -205,7 +225,26 @@ class WidebandReceiver:
             self._feed_metadata(fresh, new)
         if self.sis is not None:
             self._feed_sis(fresh, new)
+        if self.analog:
+            self._deliver_audio(pcm, new)
         return [ev for per in new for ev in per]
+
+    def _deliver_audio(self, pcm, events):
+        """pcm: int16 [k, frames, 2], this push's new frames; events[s]: as for _feed_metadata"""
+        if pcm.shape[1] == 0:
+            return
+        level, flag = self.fm.pilot()
+        for s in range(self.k):
+            block = np.ascontiguousarray(pcm[s])
+            self.audio[s].append(block)
+            if self.on_audio is not None:
+                self.on_audio(s, block)
+            self.pilot[s] = float(level[s])
+            if bool(flag[s]) != self.stereo[s]:
+                self.stereo[s] = bool(flag[s])
+                v = {"stereo": self.stereo[s], "pilot": self.pilot[s]}
+                self.logs[s].append(("analog", v))
+                events[s].append((s, "analog", v))
 
     def station_records(self, s: int) -> np.ndarray:
         return np.concatenate(self.records[s]) if self.records[s] else np.zeros(0, dtype=eng.RECORD_DTYPE)
@@ -219,6 +258,8 @@ class WidebandReceiver:
             self.psd.close()
         if self.sis is not None:
             self.sis.close()
+        if self.fm is not None:
+            self.fm.close()
         self.engine.close()
         self.chan.close()
 
@@ -501,6 +542,44 @@ class AasDump:
             out.write(f["data"])
 
 
+class AnalogDump:
+    """--dump-analog: one WAV file per station (44.1 kHz, 16 bit, stereo), opened on the station's first audio.  Every write leaves a
+    complete file behind it -- the header is brought up to date and the file flushed -- so a live pipe does not hold its audio."""
+
+    def __init__(self, directory: str, offsets_hz):
+        import os
+        os.makedirs(directory, exist_ok=True)
+        self.dir, self.offsets = directory, [float(f) for f in offsets_hz]
+        self.files = {}                  # station -> [file, wave writer, frames]
+
+    def path(self, station: int) -> str:
+        import os
+        return os.path.join(self.dir, f"station{station}_{int(round(self.offsets[station])):+d}_analog.wav")
+
+    def write(self, station: int, pcm):
+        import wave
+        if not len(pcm):
+            return
+        ent = self.files.get(station)
+        if ent is None:
+            f = open(self.path(station), "wb")
+            w = wave.open(f, "wb")
+            w.setnchannels(2); w.setsampwidth(2); w.setframerate(eng.FM_AUDIO_RATE)
+            ent = self.files[station] = [f, w, 0]
+        ent[1].writeframes(np.ascontiguousarray(pcm, dtype="<i2").tobytes())      # (writeframes patches the header's lengths)
+        ent[0].flush()
+        ent[2] += len(pcm)
+
+    def close(self) -> list:
+        """-> the summary lines, by station"""
+        lines = []
+        for s, (f, w, frames) in sorted(self.files.items()):
+            w.close()
+            f.close()
+            lines.append(f"station {s} ({self.offsets[s] / 1e3:+.1f} kHz): analog frames {frames} seconds {frames / eng.FM_AUDIO_RATE:.3f}")
+        return lines
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m nrsc5_amd.wideband", description=__doc__.splitlines()[0])
     ap.add_argument("file", help="capture file, or - for standard input (needs --offsets)")
@@ -520,6 +599,9 @@ def main(argv=None) -> int:
                     help="write every station's audio programs as ADTS: DIR/station<k>_<offset in Hz>_p<program>.aac")
     ap.add_argument("--dump-aas-files", metavar="DIR", default=None,
                     help="write every station's complete LOT files (album art, logos): DIR/station<k>_<offset in Hz>_<lot>_<name>; prints the SIG and a line per file")
+    ap.add_argument("--dump-analog", metavar="DIR", default=None,
+                    help="write every station's analog FM programme as WAV (44.1 kHz, 16 bit, stereo): DIR/station<k>_<offset in Hz>_analog.wav")
+    ap.add_argument("--deemphasis", type=float, default=75.0, choices=[75.0, 50.0, 0.0], help="de-emphasis of the analog audio in us (0: none)")
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
     ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -555,7 +637,11 @@ def main(argv=None) -> int:
                     return 1
         del head
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
-                          data_services=a.dump_aas_files is not None)
+                          data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis)
+    wav = None
+    if a.dump_analog is not None:
+        wav = AnalogDump(a.dump_analog, offsets)
+        rx.on_audio = wav.write
     if a.dump_aas_files is not None:
         rx.on_file = AasDump(a.dump_aas_files, offsets).write
     dump = None
@@ -573,12 +659,18 @@ def main(argv=None) -> int:
                 line = format_event(rx, s, kind, v)
                 if line:
                     print(line, flush=True)
+            if wav is not None:
+                for kept in rx.audio:                          # written and flushed by on_audio
+                    kept.clear()
             if dump is not None:
                 dump.flush()
                 for kept in rx.packets:                        # written: a session of any length must not keep its audio in memory
                     kept.clear()
     if dump is not None:
         for line in dump.close():
+            print(line, flush=True)
+    if wav is not None:
+        for line in wav.close():
             print(line, flush=True)
     rx.close()
     return 0
