@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 16   /* 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 17   /* 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -735,6 +735,14 @@ int nrsc5hip_stage_acquire_raw(nrsc5hip_engine *e, int n, const uint8_t *iq, lon
  *   LDS and stay unobserved; nothing behind the acquisition section writes coarse_samperr / coarse_re / coarse_im / fir_hist, so they are read from the
  *   stream state after the step: -> *samperr, peak [2], hist_out [31][2]. */
 int nrsc5hip_stage_am_acquire(nrsc5hip_engine *e, const int16_t *win, const int16_t *hist, int state, int fill, int *samperr, float *peak, int16_t *hist_out);
+/* ---- the exact oscillator on caller data (ABI 17; tests/nco_checks.py) ---------------------------------------------------------------------
+ * Runs the PRODUCTION launch (launch_nco_exact: k_nco_exact) once on streams 0 .. n-1 of the engine, freshly reset, into whose state it wrote what the block's
+ * bookkeeping leaves for the kernel: start [n][2] = the oscillator in front of the block (acquire_t.phase after the block-start rotation), inc [n][2] = phase_increment,
+ * active [n], nco_mode [n] (the block runs on the table: 1).  -> tab float [n][32 * 2160][2]: the streams' table rows, filled with 0xA5 bytes before the launch -- a
+ * stream that is not active or not in exact mode still shows the fill -- and end [n][2]: the stream's oscillator state afterwards (for such a stream: start).  All
+ * arrays are HOST arrays.  The streams are left freshly reset.  NRSC5HIP_EINVAL with nothing launched: a null pointer; n < 1 or n > max_streams; a stream in AM mode;
+ * an engine without the table. */
+int nrsc5hip_stage_nco_exact(nrsc5hip_engine *e, int n, const float *start, const float *inc, const int *active, const int *nco_mode, float *tab, float *end);
 /* one frame, also returning the len+64 survivor-decision words of the forward pass */
 int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out);
 /* micro-benchmark of the Viterbi kernel on random frames: phases bit0 = forward, bit1 = traceback */

@@ -567,6 +567,40 @@ extern "C" int nrsc5hip_stage_am_acquire(nrsc5hip_engine *e, const int16_t *win,
     return nrsc5hip_stream_fresh(e, 0);
 }
 
+// ---- the exact oscillator on caller data (include/nrsc5hip.h; tests/nco_checks.py) --------------------------------------------------------------
+// launch_nco_exact unchanged on streams 0 .. n-1, freshly reset, into whose state the hook wrote what prepare_block leaves for the kernel; the streams' table rows are
+// filled with ACQ_FILL bytes first.  Nothing of the arithmetic lives here.
+extern "C" int nrsc5hip_stage_nco_exact(nrsc5hip_engine *e, int n, const float *start, const float *inc, const int *active, const int *nco_mode, float *tab, float *end)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!start || !inc || !active || !nco_mode || !tab || !end) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (n < 1 || n > e->cfg.max_streams) FAIL(NRSC5HIP_EINVAL, "%d streams: 1 .. max_streams (%d)", n, e->cfg.max_streams);
+    if (!e->db.nco_tab) FAIL(NRSC5HIP_EINVAL, "the engine has no oscillator table");
+    int rc;
+    for (int s = 0; s < n; s++) {
+        if (e->mode_host[s] != MODE_FM) FAIL(NRSC5HIP_EINVAL, "stream %d must be in FM mode", s);
+        if ((rc = nrsc5hip_stream_fresh(e, s))) return rc;
+    }
+    const size_t row = (size_t)NSYM * SYM_N;
+    HIPCHK(hipMemset(e->db.nco_tab, ACQ_FILL, (size_t)n * row * sizeof(float2)));
+    for (int s = 0; s < n; s++) {
+        POKE(e->db.state + s, StreamState, active, active[s] ? 1 : 0);
+        POKE(e->db.state + s, StreamState, nco_mode, nco_mode[s] ? 1 : 0);
+        POKE(e->db.state + s, StreamState, nco_re, start[2 * s]);
+        POKE(e->db.state + s, StreamState, nco_im, start[2 * s + 1]);
+        POKE(e->db.state + s, StreamState, inc_re, inc[2 * s]);
+        POKE(e->db.state + s, StreamState, inc_im, inc[2 * s + 1]);
+    }
+    launch_nco_exact(e->db, n, nullptr, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(tab, e->db.nco_tab, (size_t)n * row * sizeof(float2), hipMemcpyDeviceToHost));
+    static_assert(offsetof(StreamState, nco_im) - offsetof(StreamState, nco_re) == 4, "nco_re, nco_im are adjacent words");
+    for (int s = 0; s < n; s++) HIPCHK(hipMemcpy(end + 2 * s, (const char *)(e->db.state + s) + offsetof(StreamState, nco_re), 2 * sizeof(float), hipMemcpyDeviceToHost));
+    for (int s = 0; s < n; s++) if ((rc = nrsc5hip_stream_fresh(e, s))) return rc;
+    return 0;
+}
+
 extern "C" int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out)
 {
     ON_ENGINE_DEVICE(e);

@@ -307,20 +307,52 @@ __global__ __launch_bounds__(256) MIXFFT8_OCCUPANCY void k_mixfft8(DevTables tb,
 
 // The reference's oscillator for one block, sample by sample (acquire.c:237-252): phase *= phase_increment 2160 times per symbol as the float
 // complex product it is (four products, two sums, each rounded), phase /= cabsf(phase) at the symbol's end -- 69 120 DEPENDENT steps, so one
-// lane per stream walks them (three packed instructions a step: ~0.5 ms, whatever the number of streams) and leaves every sample's phasor in db.nco_tab for
+// wave per stream walks them (three packed instructions a step, whatever the number of streams) and leaves every sample's phasor in db.nco_tab for
 // the symbol kernel.  Launched only on steps that run the acquisition kernels, and it leaves at once for a stream whose block runs on the closed-form
-// phasor -- under NCO_EXACT_UNTIL_FINE that is every block after a stream's first lock; the batch default is NCO_CLOSED_FORM (no exact block at all), the drop-in's NCO_EXACT_FIRST_BLOCK.
+// phasor -- under the default policy, NCO_EXACT_FIRST_BLOCK, that is every block but the first after a stream's reset (NCO_EXACT_UNTIL_FINE: every block after its first
+// lock; NCO_CLOSED_FORM: every block).
 // cabsf: glibc's hypotf computes sqrt((double)x * x + (double)y * y) and rounds once to float (verified equal on 5e7 random pairs); the
 // divisions are IEEE float divisions (hipcc's default).
-// One WAVE per stream with one lane at work: as lane = stream the 64 lanes of a wave stored to 64 different cache lines per instruction and the
-// vector memory unit, one line per cycle, became the bound (measured: 1.8 ms for 256 streams instead of the chain's ~0.5 ms).
+// One WAVE per stream: as lane = stream the 64 lanes of a wave stored to 64 different cache lines per instruction and the vector memory unit, one
+// line per cycle, became the bound (measured: 1.8 ms for 256 streams).  Up to round 6 one lane of that wave worked and stored its 8 bytes after
+// every step -- 69 120 partial-line stores per stream, each an instruction between two links of the chain (1.23 ms per launch, 43 cycles a step).
+// Now (round 7) the whole wave runs the recurrence from the same start values -- the same operations, so the same bits, and the SIMD executes all lanes
+// anyway -- and the phasors leave the registers a ROW of 64 steps at a time, as one coalesced 512-byte store: nco_row below says how lane l comes to
+// hold the phasor of the row's step l.  A symbol is 33 rows and a tail of 48 steps.  Measured, 256 streams: 0.52 ms per launch, 18 cycles a step (the forms
+// that were tried and their times: tools/probe/nco_probe.hip, profiles/r07_front_of_pass.txt).
+#ifndef HIPEMU
+#define NCO_STEP "v_pk_mul_f32 %[t1], %[p], %[k] op_sel_hi:[0,1]\n\tv_pk_mul_f32 %[t2], %[p], %[k] op_sel:[1,1] op_sel_hi:[1,0]\n\t"
+#define NCO_ADD "v_pk_add_f32 %[p], %[t1], %[t2] neg_lo:[0,1]"
+// R steps (R <= 64) from the phasor P all lanes hold: -> the phasor in front of step l in lane l (l < R); P: the phasor behind the row, in all lanes.
+// THREE packed instructions per step -- (ac, ad), (bd, bc), then (ac - bd, ad + bc) with the sign of the low half in neg_lo -- the same six IEEE
+// operations, each rounded once (the compiler's own vectorisation of the scalar form spends four: it forms the sum AND the difference of both
+// halves); plain VALU dependencies are interlocked in hardware.
+template <int R> __device__ __forceinline__ cf nco_row(cf &P, const cf K)
+{
+    cf t1, t2;
+    // EXEC loses one lane per step (s_lshl_b64 exec, exec, 1, on the scalar ALU, off the chain), so lane l takes part in the first l steps and stops on the phasor in
+    // front of step l: no instruction beside the chain's three touches the vector ALU.  The whole row is ONE statement: between two statements the compiler may place
+    // instructions of its own, which must not run under a partial EXEC.  Needs what the launch guarantees: 64 work-items, all of them here (EXEC = -1 on entry).
+    asm volatile(".rept %c[n]\n\ts_lshl_b64 exec, exec, 1\n\t" NCO_STEP NCO_ADD "\n\t.endr\n\ts_mov_b64 exec, -1"
+                 : [p] "+v"(P), [t1] "=&v"(t1), [t2] "=&v"(t2) : [k] "v"(K), [n] "n"(R - 1) : "scc");
+    const cf mine = P;
+    // the last lane's phasor back to every lane (through two scalar registers), then the row's last step by all of them
+    const float lx = mine.x, ly = mine.y;                      // (element by element through plain floats: a bit cast applied to P.y directly read P.x)
+    P = cf_make(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(lx), R - 1)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ly), R - 1)));
+    asm(NCO_STEP NCO_ADD : [p] "+v"(P), [t1] "=&v"(t1), [t2] "=&v"(t2) : [k] "v"(K));
+    return mine;
+}
+#endif
 __global__ __launch_bounds__(64) void k_nco_exact(DevBuffers db, const int *ids, int nstreams)
 {
     const int idx = blockIdx.x;
-    if (idx >= nstreams || threadIdx.x != 0) return;
+    if (idx >= nstreams) return;
+#ifdef HIPEMU
+    if (threadIdx.x != 0) return;                              // the CPU twin: one work-item on the plain scalar form
+#endif
     const int s = stream_of(ids, idx);
     StreamState &st = db.state[s];
-    if (!st.active || !st.nco_mode) return;
+    if (!st.active || !st.nco_mode) return;                    // (uniform: the whole wave leaves)
     float pr = st.nco_re, pi = st.nco_im;
     const float c = st.inc_re, d = st.inc_im;
     float2 *tab = db.nco_tab + (size_t)s * NSYM * SYM_N;
@@ -332,27 +364,21 @@ __global__ __launch_bounds__(64) void k_nco_exact(DevBuffers db, const int *ids,
             pr = ac - bd; pi = ad + bc;
         }
 #else
-        // THREE packed instructions per step -- (ac, ad), (bd, bc), then (ac - bd, ad + bc) with the sign of the low half in neg_lo -- the same
-        // six IEEE operations, each rounded once (the compiler's own vectorisation of the scalar form spends four: it forms the sum AND the
-        // difference of both halves); the chain is latency-bound at two dependent instructions per step
+        constexpr int ROWS = SYM_N / 64, TAIL = SYM_N % 64;
+        static_assert(ROWS * 64 + TAIL == SYM_N && TAIL > 0, "a symbol is whole rows of 64 steps and a shorter tail");
+        const int lane = threadIdx.x;
         cf P = cf_make(pr, pi);
         const cf K = cf_make(c, d);
         cf *out = (cf *)(tab + sym * SYM_N);
-#pragma unroll 8
-        for (int j = 0; j < SYM_N; j++) {
-            out[j] = P;
-            cf t1, t2;                                             // (one statement: plain VALU dependencies are interlocked in hardware, and between separate
-                                                                   //  statements the compiler pads with s_nop it cannot know to be unnecessary)
-            asm("v_pk_mul_f32 %1, %0, %3 op_sel_hi:[0,1]\n\t"
-                "v_pk_mul_f32 %2, %0, %3 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-                "v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "+v"(P), "=&v"(t1), "=&v"(t2) : "v"(K));
-        }
+        for (int row = 0; row < ROWS; row++) { const cf mine = nco_row<64>(P, K); out[row * 64 + lane] = mine; }
+        const cf mine = nco_row<TAIL>(P, K);
+        if (lane < TAIL) out[ROWS * 64 + lane] = mine;         // entries 2112 .. 2159; the lanes beyond hold nothing of this symbol
         pr = P.x; pi = P.y;
 #endif
         const float m = (float)sqrt((double)pr * (double)pr + (double)pi * (double)pi);
         pr = pr / m; pi = pi / m;
     }
-    st.nco_re = pr; st.nco_im = pi;                            // acquire_t.phase after the block
+    if (threadIdx.x == 0) { st.nco_re = pr; st.nco_im = pi; }  // acquire_t.phase after the block
 }
 
 void launch_nco_exact(const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st)

@@ -97,6 +97,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_stage_acquire.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nrsc5hip_stage_acquire_raw.argtypes = [vp, ci, vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nrsc5hip_stage_am_acquire.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
+    lib.nrsc5hip_stage_nco_exact.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     lib.nrsc5hip_debug_poison_results.argtypes = [vp]
     lib.nrsc5hip_debug_seam_totals.argtypes = [vp, ci]
     lib.nrsc5hip_debug_seam_totals.restype = None
@@ -200,7 +201,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
-    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
+    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_stage_nco_exact", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
     "nrsc5hip_stream_set_mode", "nrsc5hip_am_frame_bits", "nrsc5hip_stage_viterbi_k9", "nrsc5hip_px_frame_bits",
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
@@ -735,6 +736,17 @@ class Engine:
         se, peak, hist_out = ctypes.c_int(0), np.zeros(2, dtype=np.float32), np.zeros((31, 2), dtype=np.int16)
         self._check(self.lib.nrsc5hip_stage_am_acquire(self._h, _ptr(win), _ptr(hist), state, fill, ctypes.byref(se), peak.ctypes.data, hist_out.ctypes.data))
         return dict(samperr=np.array([se.value], dtype=np.int32), peak=peak[None], hist_out=hist_out[None])
+
+    def stage_nco_exact(self, start, inc, active, nco_mode, n: int | None = None):
+        """nrsc5hip_stage_nco_exact: launch_nco_exact on streams 0 .. n-1.  start / inc float32 [n, 2], active / nco_mode int [n] ->
+        (tab float32 [n, 32 * 2160, 2], rows the kernel left alone still filled with 0xA5 bytes; end float32 [n, 2])"""
+        n = len(active) if n is None else n
+        m = max(n, 0)
+        start, inc = _exact(start, np.float32, 2 * m), _exact(inc, np.float32, 2 * m)
+        active, nco_mode = _exact(active, np.int32, m), _exact(nco_mode, np.int32, m)
+        tab, end = np.zeros((m, 32 * 2160, 2), dtype=np.float32), np.zeros((m, 2), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_stage_nco_exact(self._h, n, _ptr(start), _ptr(inc), _ptr(active), _ptr(nco_mode), tab.ctypes.data, end.ctypes.data))
+        return tab, end
 
     def stage_selftest(self) -> int:
         n = ctypes.c_int(-1)
