@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 17   /* 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 18   /* 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -735,6 +735,33 @@ int nrsc5hip_stage_acquire_raw(nrsc5hip_engine *e, int n, const uint8_t *iq, lon
  *   LDS and stay unobserved; nothing behind the acquisition section writes coarse_samperr / coarse_re / coarse_im / fir_hist, so they are read from the
  *   stream state after the step: -> *samperr, peak [2], hist_out [31][2]. */
 int nrsc5hip_stage_am_acquire(nrsc5hip_engine *e, const int16_t *win, const int16_t *hist, int state, int fill, int *samperr, float *peak, int16_t *hist_out);
+/* ---- the AM block step on caller data (ABI 18; tests/am_checks.py) ----------------------------------------------------------------------------
+ * Runs k_am_block ALONE -- the first launch of launch_am_step, without the decode and interleave launches behind it -- once on stream 0 of an am_enable
+ * engine in AM mode, freshly reset, into whose state the hook wrote the caller's window (win [8910][2], fill <= 8910 = the FIFO's write position), the
+ * acquisition filter's history (hist [31][2]) and the state words of *in.  The launch shape follows the engine as in nrsc5hip_stage_am_acquire:
+ * k_am_block<256> with pipeline = 0 on an engine without p1_async, k_am_block<512> with pipeline = 1 (window parity 0, slot 0) on one with it.  dump != 0
+ * selects the instantiation that also copies the tile out: spectra float [32][256][2] = the 32 symbol spectra behind the sideband combine (FFT order: bin k of
+ * the carrier at index k & 255), mult float [4][25][2] = the equaliser taps (pl, pu, s, t; written only by a block that is FINE at its end).  Everything the
+ * kernel may write is filled with 0xA5 bytes first: the record, am_sym, the staged PIDS bytes, spectra and mult.  ->  *rec: the block's record (record slot
+ * 0); *out: the same state words after the launch, with the read-only ones; am_sym uint8 [4][6400]: the stream's whole hard-symbol matrices; pids_stage
+ * int8 [240]: the pipeline form's staged trellis input (in order: still the fill; rec->pids and NRSC5HIP_REC_PIDS_CRC hold the decode).  The stream is left
+ * freshly reset.  No arithmetic lives in the hook.  NRSC5HIP_EINVAL with nothing launched: a null pointer (spectra / mult may be null when dump == 0); an
+ * engine without am_enable; a stream in FM mode; in->sync_state outside 0 .. 2; in->bc outside 0 .. 7; in->samperr outside -135 .. 135 or in->coarse_samperr
+ * outside 0 .. 269 (the window would be read out of range); fill outside 0 .. 8910. */
+typedef struct nrsc5hip_am_block_state {
+    int32_t sync_state, samperr, cfo, psmi, bc, cfo_wait;      /* StreamState */
+    float prev_angle, angle;
+    double theta;
+    int32_t coarse_samperr; float coarse_re, coarse_im;         /* (overwritten by the acquisition section while not FINE) */
+    int32_t keep_extra;
+    uint32_t offset_history;                                    /* AmStream */
+    int32_t rdbi, pli, hppi, aabi, am_diversity_wait;
+    uint32_t am_errors;
+    int32_t fine_epoch, active, nblocks;                        /* read back only: ignored in *in */
+    long long rd;
+} nrsc5hip_am_block_state;
+int nrsc5hip_stage_am_block(nrsc5hip_engine *e, const int16_t *win, const int16_t *hist, const nrsc5hip_am_block_state *in, int fill, int dump,
+                            nrsc5hip_record *rec, nrsc5hip_am_block_state *out, uint8_t *am_sym, int8_t *pids_stage, float *spectra, float *mult);
 /* ---- the exact oscillator on caller data (ABI 17; tests/nco_checks.py) ---------------------------------------------------------------------
  * Runs the PRODUCTION launch (launch_nco_exact: k_nco_exact) once on streams 0 .. n-1 of the engine, freshly reset, into whose state it wrote what the block's
  * bookkeeping leaves for the kernel: start [n][2] = the oscillator in front of the block (acquire_t.phase after the block-start rotation), inc [n][2] = phase_increment,
@@ -836,6 +863,9 @@ int nrsc5hip_debug_fetch_costas(nrsc5hip_engine *e, int stream, float *freq /* [
 
 /* debugging aid: PX1 / PX2 soft bits of the stream's current block pair, [2 channels][2 blocks][4608] int8 */
 int nrsc5hip_debug_fetch_px(nrsc5hip_engine *e, int stream, int8_t *pair /* [18432] */);
+
+/* debugging aid: an AM stream's hard-symbol matrices (pl, pu, s, t: 4 x 6400 bytes; block bc of the L1 frame being received at bc * 800) */
+int nrsc5hip_debug_fetch_am_sym(nrsc5hip_engine *e, int stream, uint8_t *sym /* [4][6400] */);
 
 /* fresh-session state for every stream (input_reset on all of them) */
 int nrsc5hip_reset_all(nrsc5hip_engine *e);

@@ -147,5 +147,27 @@ class SisInfo(ctypes.Structure):         # nrsc5hip_sis_info
                 ("n_audio", ctypes.c_int32), ("audio", (ctypes.c_int32 * 4) * 8), ("n_data", ctypes.c_int32), ("data", (ctypes.c_int32 * 3) * 16)]
 
 
+class AmBlockState(ctypes.Structure):
+    """nrsc5hip_am_block_state: the words of StreamState / AmStream that k_am_block reads (nrsc5hip_stage_am_block); the last four are read back only"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("sync_state", "samperr", "cfo", "psmi", "bc", "cfo_wait")] + \
+               [("prev_angle", ctypes.c_float), ("angle", ctypes.c_float), ("theta", ctypes.c_double),
+                ("coarse_samperr", ctypes.c_int32), ("coarse_re", ctypes.c_float), ("coarse_im", ctypes.c_float), ("keep_extra", ctypes.c_int32),
+                ("offset_history", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("rdbi", "pli", "hppi", "aabi", "am_diversity_wait")] + [("am_errors", ctypes.c_uint32)] + \
+               [(n, ctypes.c_int32) for n in ("fine_epoch", "active", "nblocks")] + [("rd", ctypes.c_longlong)]
+
+
+assert ctypes.sizeof(AmBlockState) == 104
+AM_BLOCK_STATE_IN = tuple(n for n, _ in AmBlockState._fields_[:21])       # what the hook writes into the stream before the launch
+AM_SYMS, AM_FFT, AM_NSYM, AM_PW = 6400, 256, 32, 25                          # hard symbols per partition and L1 frame; FFT size; symbols per block; carriers per partition
+
+
+def bind_am_block(lib) -> None:
+    """argument types of the AM block-step stage hook and of the symbol fetch (include/nrsc5hip.h, ABI 18)"""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.nrsc5hip_stage_am_block.argtypes = [vp, vp, vp, ctypes.POINTER(AmBlockState), ci, ci, vp, ctypes.POINTER(AmBlockState), vp, vp, vp, vp]
+    lib.nrsc5hip_debug_fetch_am_sym.argtypes = [vp, ci, vp]
+
+
 class Nrsc5HipError(RuntimeError):
     pass

@@ -567,6 +567,91 @@ extern "C" int nrsc5hip_stage_am_acquire(nrsc5hip_engine *e, const int16_t *win,
     return nrsc5hip_stream_fresh(e, 0);
 }
 
+// ---- the AM block step on caller data (include/nrsc5hip.h; tests/am_checks.py) ----------------------------------------------------------------------
+// k_am_block alone (launch_stage_am_block: the launch shapes of launch_am_step) on stream 0, freshly reset, whose window, history and state words the hook wrote;
+// the record, the symbol matrices, the staged PIDS bytes and the dump buffers are filled with ACQ_FILL bytes first.  Nothing of the arithmetic lives here.
+static void am_block_state_out(const StreamState &st, const AmStream &am, nrsc5hip_am_block_state *o)
+{
+    o->sync_state = st.sync_state; o->samperr = st.samperr; o->cfo = st.cfo; o->psmi = st.psmi; o->bc = st.bc; o->cfo_wait = st.cfo_wait;
+    o->prev_angle = st.prev_angle; o->angle = st.angle; o->theta = st.theta;
+    o->coarse_samperr = st.coarse_samperr; o->coarse_re = st.coarse_re; o->coarse_im = st.coarse_im; o->keep_extra = st.keep_extra;
+    o->offset_history = am.offset_history; o->rdbi = am.rdbi; o->pli = am.pli; o->hppi = am.hppi; o->aabi = am.aabi;
+    o->am_diversity_wait = am.am_diversity_wait; o->am_errors = am.am_errors;
+    o->fine_epoch = st.fine_epoch; o->active = st.active; o->nblocks = st.nblocks; o->rd = st.rd;
+}
+
+extern "C" int nrsc5hip_stage_am_block(nrsc5hip_engine *e, const int16_t *win, const int16_t *hist, const nrsc5hip_am_block_state *in, int fill, int dump,
+                                       nrsc5hip_record *rec, nrsc5hip_am_block_state *out, uint8_t *am_sym, int8_t *pids_stage, float *spectra, float *mult)
+{
+    ON_ENGINE_DEVICE(e);
+    static_assert(sizeof(nrsc5hip_record) == sizeof(BlockRecord), "the public record mirrors BlockRecord");
+    if (!win || !hist || !in || !rec || !out || !am_sym || !pids_stage || (dump && (!spectra || !mult))) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!e->db.am) FAIL(NRSC5HIP_EINVAL, "engine was created without am_enable");
+    int rc = acq_check_common(e, 1, &in->sync_state, MODE_AM, AM_WIN); if (rc) return rc;
+    if (fill < 0 || fill > AM_WIN) FAIL(NRSC5HIP_EINVAL, "fill %d: 0 .. %d samples", fill, AM_WIN);
+    if (in->bc < 0 || in->bc > 7) FAIL(NRSC5HIP_EINVAL, "block count %d: 0 .. 7", in->bc);
+    // the fold reads win[31 * AM_SYM + AM_SYM - 1 + samperr] at most: samperr = AM_SYM / 2 + st.samperr (FINE) or coarse_samperr must stay in 0 .. AM_SYM
+    if (in->samperr < -AM_SYM / 2 || in->samperr > AM_SYM / 2) FAIL(NRSC5HIP_EINVAL, "samperr %d: %d .. %d", in->samperr, -AM_SYM / 2, AM_SYM / 2);
+    if (in->coarse_samperr < 0 || in->coarse_samperr >= AM_SYM) FAIL(NRSC5HIP_EINVAL, "coarse_samperr %d: 0 .. %d", in->coarse_samperr, AM_SYM - 1);
+    if ((rc = nrsc5hip_stream_fresh(e, 0))) return rc;
+    DevBuffers db = e->db;                                                     // without the consumers a stage run must not feed (stage_stream0), and without the replay
+    db.l2_ring = nullptr; db.l2_px_ring = nullptr; db.l2_am_ring = nullptr; db.p1_mirror = nullptr; db.am_ckpt = nullptr;
+    const int pipeline = e->cfg.p1_async ? 1 : 0;
+    StreamState st; AmStream am;
+    HIPCHK(hipMemcpy(&st, db.state, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&am, db.am, sizeof(am), hipMemcpyDeviceToHost));
+    st.wr = fill;
+    memcpy(st.fir_hist, hist, sizeof(st.fir_hist));
+    st.sync_state = in->sync_state; st.samperr = in->samperr; st.cfo = in->cfo; st.psmi = in->psmi; st.bc = in->bc; st.cfo_wait = in->cfo_wait;
+    st.prev_angle = in->prev_angle; st.angle = in->angle; st.theta = in->theta;
+    st.coarse_samperr = in->coarse_samperr; st.coarse_re = in->coarse_re; st.coarse_im = in->coarse_im; st.keep_extra = in->keep_extra;
+    am.offset_history = in->offset_history; am.rdbi = in->rdbi; am.pli = in->pli; am.hppi = in->hppi; am.aabi = in->aabi;
+    am.am_diversity_wait = in->am_diversity_wait; am.am_errors = in->am_errors;
+    HIPCHK(hipMemcpy(db.state, &st, sizeof(st), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db.am, &am, sizeof(am), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db.q15, win, (size_t)AM_WIN * sizeof(c16), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(db.records, ACQ_FILL, sizeof(BlockRecord)));
+    HIPCHK(hipMemset(db.am_sym, ACQ_FILL, (size_t)4 * AM_SYMS));
+    HIPCHK(hipMemset(db.am_pids_stage, ACQ_FILL, (size_t)3 * PIDS_LEN));           // window parity 0, slot 0 of stream 0
+    DevTmp dx, dm;
+    if (dump) {
+        HIPCHK(hipMalloc(&dx.p, (size_t)NSYM * AM_FFT * sizeof(float2)));
+        HIPCHK(hipMalloc(&dm.p, (size_t)4 * AM_PW * sizeof(float2)));
+        HIPCHK(hipMemset(dx.p, ACQ_FILL, (size_t)NSYM * AM_FFT * sizeof(float2)));
+        HIPCHK(hipMemset(dm.p, ACQ_FILL, (size_t)4 * AM_PW * sizeof(float2)));
+    }
+    HIPCHK(hipMemsetAsync(db.counters, 0, 4 * sizeof(int), e->main));
+    launch_stage_am_block(e->tb, db, pipeline, (float2 *)dx.p, (float2 *)dm.p, e->main);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(&st, db.state, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&am, db.am, sizeof(am), hipMemcpyDeviceToHost));
+    am_block_state_out(st, am, out);
+    HIPCHK(hipMemcpy(rec, db.records, sizeof(BlockRecord), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(am_sym, db.am_sym, (size_t)4 * AM_SYMS, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pids_stage, db.am_pids_stage, (size_t)3 * PIDS_LEN, hipMemcpyDeviceToHost));
+    if (dump) {
+        HIPCHK(hipMemcpy(spectra, dx.p, (size_t)NSYM * AM_FFT * sizeof(float2), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mult, dm.p, (size_t)4 * AM_PW * sizeof(float2), hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemset(db.am_sym, 0, (size_t)4 * AM_SYMS));                       // as the engine's creation leaves them
+    HIPCHK(hipMemset(db.am_pids_stage, 0, (size_t)3 * PIDS_LEN));
+    HIPCHK(hipMemset(db.records, 0, sizeof(BlockRecord)));
+    return nrsc5hip_stream_fresh(e, 0);
+}
+
+extern "C" int nrsc5hip_debug_fetch_am_sym(nrsc5hip_engine *e, int stream, uint8_t *sym)
+{
+    ON_ENGINE_DEVICE(e);
+    int rc = check_stream(e, stream); if (rc) return rc;
+    if (!sym) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!e->db.am_sym) FAIL(NRSC5HIP_EINVAL, "engine was created without am_enable");
+    if (e->staged_stream >= 0 && (rc = flush_staged(e))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(sym, e->db.am_sym + (size_t)stream * 4 * AM_SYMS, (size_t)4 * AM_SYMS, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- the exact oscillator on caller data (include/nrsc5hip.h; tests/nco_checks.py) --------------------------------------------------------------
 // launch_nco_exact unchanged on streams 0 .. n-1, freshly reset, into whose state the hook wrote what prepare_block leaves for the kernel; the streams' table rows are
 // filled with ACQ_FILL bytes first.  Nothing of the arithmetic lives here.

@@ -211,8 +211,10 @@ __device__ __forceinline__ void am_nco_steps(AmBlockSmem &sm)
 // 64 KB of LDS waits for a whole CU's worth of slots while the decode streams keep the chip full of long one-wave trellis passes.
 // (NT, the block size, is a template constant: read as blockDim.x it is two dependent global loads -- implicit-argument pointer, dispatch packet -- in
 // front of the first loop that strides by it; profiles/r04_mixfft_phases.txt)
-template <int NT>
-__global__ __launch_bounds__(NT) void k_am_block(DevTables tb, DevBuffers db, const int *ids, int pipeline, int parity, int slot)
+// DUMP (nrsc5hip_stage_am_block, tests/am_checks.py): the stage hook's instantiations take two more arguments, float2 *x [NSYM * AM_FFT] and float2 *mult [4 * AM_PW], and
+// copy the tile behind the sideband combine and the equaliser taps out to them.  The production instantiations (DUMP = false, an empty pack) are the code they were.
+template <int NT, bool DUMP = false, typename... Dump>
+__global__ __launch_bounds__(NT) void k_am_block(DevTables tb, DevBuffers db, const int *ids, int pipeline, int parity, int slot, Dump... dump)
 {
     wave_set_priority_high();                                  // block-step chain = critical path; the decode waves run at priority 0
     const int s = stream_of(ids, blockIdx.x);
@@ -449,6 +451,10 @@ __global__ __launch_bounds__(NT) void k_am_block(DevTables tb, DevBuffers db, co
         if (!sm.ma3 && i <= 53) { float2 &up = am_bin(sm, i, n); up = make_float2(up.x + lo.x, up.y + lo.y); }
     }
     __syncthreads();
+    if constexpr (DUMP) {
+        float2 *out = [](float2 *x, float2 *) { return x; }(dump...);
+        for (int k = tid; k < NSYM * AM_FFT; k += NT) out[k] = sm.X[k];
+    }
     if (tid < 64) {
         const unsigned long long m = __ballot(tid < NSYM && am_bin(sm, 1, tid & 31).y > 0);
         if (tid == 0) sm.refmask = (int)(uint32_t)m;           // bit n = reference-carrier BPSK bit of symbol n
@@ -533,6 +539,10 @@ __global__ __launch_bounds__(NT) void k_am_block(DevTables tb, DevBuffers db, co
             if (part < 2) sm.marg[part][col] = ref_atan2f(m.y, m.x);
         }
         __syncthreads();
+        if constexpr (DUMP) {
+            float2 *out = [](float2 *, float2 *m) { return m; }(dump...);
+            for (int k = tid; k < 4 * AM_PW; k += NT) out[k] = sm.mult[k / AM_PW][k % AM_PW];
+        }
         AM_MARK(7);                                            // PIDS carriers + equaliser taps
         if (tid == 0) {
             float se = 0;
@@ -766,16 +776,38 @@ __global__ __launch_bounds__(AM_IL_THREADS) void k_am_interleave(DevTables tb, D
     }
 }
 
-void launch_am_step(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st, int l2_feedback, int pipeline_parity, int slot, int window)
+// (per device: the attribute belongs to the function as loaded on the current device -- one process may drive several, include/nrsc5hip.h)
+static void am_block_attributes()
 {
-    // (per device: the attribute belongs to the function as loaded on the current device -- one process may drive several, include/nrsc5hip.h)
     static std::atomic<bool> attr_set[64];
     int dev = 0; (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {      // (a device index beyond the table: set it on every launch rather than never)
         (void)hipFuncSetAttribute((const void *)k_am_block<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(AmBlockSmem));
         (void)hipFuncSetAttribute((const void *)k_am_block<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(AmBlockSmem));
+        (void)hipFuncSetAttribute((const void *)k_am_block<512, true, float2 *, float2 *>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(AmBlockSmem));
+        (void)hipFuncSetAttribute((const void *)k_am_block<256, true, float2 *, float2 *>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(AmBlockSmem));
         if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
     }
+}
+
+// k_am_block alone, for the stage hook (nrsc5hip_stage_am_block): the launch shapes of launch_am_step, without the decode and interleave launches behind them.
+// dump_x / dump_mult non-null: the dumping instantiation
+void launch_stage_am_block(const DevTables &tb, const DevBuffers &db, int pipeline, float2 *dump_x, float2 *dump_mult, hipStream_t st)
+{
+    am_block_attributes();
+    const int *ids = nullptr;
+    if (dump_x && dump_mult) {
+        if (pipeline) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_am_block<512, true, float2 *, float2 *>), dim3(1), dim3(512), sizeof(AmBlockSmem), st, tb, db, ids, 1, 0, 0, dump_x, dump_mult);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_am_block<256, true, float2 *, float2 *>), dim3(1), dim3(256), sizeof(AmBlockSmem), st, tb, db, ids, 0, -1, 0, dump_x, dump_mult);
+    } else {
+        if (pipeline) hipLaunchKernelGGL(k_am_block<512>, dim3(1), dim3(512), sizeof(AmBlockSmem), st, tb, db, ids, 1, 0, 0);
+        else hipLaunchKernelGGL(k_am_block<256>, dim3(1), dim3(256), sizeof(AmBlockSmem), st, tb, db, ids, 0, -1, 0);
+    }
+}
+
+void launch_am_step(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, hipStream_t st, int l2_feedback, int pipeline_parity, int slot, int window)
+{
+    am_block_attributes();
     if (pipeline_parity >= 0) hipLaunchKernelGGL(k_am_block<512>, dim3(nstreams), dim3(512), sizeof(AmBlockSmem), st, tb, db, stream_ids, 1, pipeline_parity, slot);
     else hipLaunchKernelGGL(k_am_block<256>, dim3(nstreams), dim3(256), sizeof(AmBlockSmem), st, tb, db, stream_ids, 0, pipeline_parity, slot);
     if (pipeline_parity < 0) launch_am_decode_in_order(tb, db, nstreams, stream_ids, l2_feedback, st);

@@ -322,6 +322,9 @@ void launch_stage_halfband_acq(const DevTables &tb, const uint8_t *raw, long lon
 // the FEC stage hooks (nrsc5hip_stage_pids / _am_deinterleave / _am_epilogue; the others need the production launchers above only).
 // PIDS gather + depuncture of block bc of the soft-bit matrices pm through tb.pids_gather into stage[240] (k_pids_px.hip: sync_body.h's two lines restated)
 void launch_stage_pids_gather(const DevTables &tb, const int8_t *pm, int bc, int8_t *stage, hipStream_t st);
+// k_am_block alone on stream 0 (k_am.hip; launch_am_step's first launch): <256> in order (pipeline 0), <512> as the window pipeline launches it (pipeline 1: window parity 0,
+// slot 0); dump_x [NSYM * AM_FFT] / dump_mult [4 * AM_PW] non-null: the instantiation that copies the tile behind the sideband combine and the equaliser taps out
+void launch_stage_am_block(const DevTables &tb, const DevBuffers &db, int pipeline, float2 *dump_x, float2 *dump_mult, hipStream_t st);
 // k_am_interleave alone (k_am.hip; launch_am_step's last launch)
 void launch_am_interleave(const DevTables &tb, const DevBuffers &db, int nstreams, const int *stream_ids, int parity, int window, hipStream_t st);
 // am_p3_epilogue (k_am_decode.hip) on the frame am_decode_frame(vit, slot, ., role, psmi) describes, one workgroup of `threads`: vit [2][AM_VIT]

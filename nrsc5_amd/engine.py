@@ -17,6 +17,7 @@ if _AB_LIB:
     print(f"nrsc5_amd.engine: NRSC5HIP_AB_LIB={_AB_LIB}: running a library that is NOT built from this tree (A/B measurement)", file=_sys.stderr)
     DEFAULT_LIB = _AB_LIB
 
+from . import abi
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
 from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
@@ -98,6 +99,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_stage_acquire_raw.argtypes = [vp, ci, vp, ctypes.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nrsc5hip_stage_am_acquire.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
     lib.nrsc5hip_stage_nco_exact.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    abi.bind_am_block(lib)
     lib.nrsc5hip_debug_poison_results.argtypes = [vp]
     lib.nrsc5hip_debug_seam_totals.argtypes = [vp, ci]
     lib.nrsc5hip_debug_seam_totals.restype = None
@@ -201,7 +203,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
-    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_stage_nco_exact", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
+    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_stage_am_block", "nrsc5hip_debug_fetch_am_sym", "nrsc5hip_stage_nco_exact", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
     "nrsc5hip_stream_set_mode", "nrsc5hip_am_frame_bits", "nrsc5hip_stage_viterbi_k9", "nrsc5hip_px_frame_bits",
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
@@ -736,6 +738,35 @@ class Engine:
         se, peak, hist_out = ctypes.c_int(0), np.zeros(2, dtype=np.float32), np.zeros((31, 2), dtype=np.int16)
         self._check(self.lib.nrsc5hip_stage_am_acquire(self._h, _ptr(win), _ptr(hist), state, fill, ctypes.byref(se), peak.ctypes.data, hist_out.ctypes.data))
         return dict(samperr=np.array([se.value], dtype=np.int32), peak=peak[None], hist_out=hist_out[None])
+
+    def stage_am_block(self, win, hist, state: dict, fill: int = ACQ_WIN_AM, dump: bool = False) -> dict:
+        """nrsc5hip_stage_am_block: k_am_block alone on stream 0 (AM mode), <256> in order or <512> on a p1_async engine.  win int16 [8910, 2], hist int16 [31, 2],
+        state: the words of abi.AM_BLOCK_STATE_IN (missing ones: as a fresh session has them -- psmi 1, the system bits -1, am_diversity_wait 4, the rest 0) ->
+        dict(rec: one RECORD_DTYPE record, state: dict of every word of abi.AmBlockState afterwards, am_sym uint8 [4, 6400], pids_stage int8 [240]; with dump:
+        spectra complex64 [32, 256], mult complex64 [4, 25]); whatever the kernel left alone still holds 0xA5 bytes"""
+        win, hist = _exact(win, np.int16, ACQ_WIN_AM * 2), _exact(hist, np.int16, 62)
+        words = dict(psmi=1, pli=-1, hppi=-1, aabi=-1, rdbi=-1, am_diversity_wait=4)
+        words.update(state)
+        unknown = set(words) - set(abi.AM_BLOCK_STATE_IN)
+        if unknown:
+            raise ValueError("not a state word of the AM block step: %s" % sorted(unknown))
+        sin, sout = abi.AmBlockState(**words), abi.AmBlockState()
+        rec = np.zeros(1, dtype=RECORD_DTYPE)
+        am_sym, stage = np.zeros((4, abi.AM_SYMS), dtype=np.uint8), np.zeros(240, dtype=np.int8)
+        spectra = np.zeros((abi.AM_NSYM, abi.AM_FFT), dtype=np.complex64) if dump else None
+        mult = np.zeros((4, abi.AM_PW), dtype=np.complex64) if dump else None
+        self._check(self.lib.nrsc5hip_stage_am_block(self._h, _ptr(win), _ptr(hist), ctypes.byref(sin), fill, 1 if dump else 0, rec.ctypes.data, ctypes.byref(sout),
+                                                     am_sym.ctypes.data, stage.ctypes.data, _ptr(spectra), _ptr(mult)))
+        out = dict(rec=rec[0], state={n: getattr(sout, n) for n, _ in abi.AmBlockState._fields_}, am_sym=am_sym, pids_stage=stage)
+        if dump:
+            out.update(spectra=spectra, mult=mult)
+        return out
+
+    def debug_fetch_am_sym(self, stream: int) -> np.ndarray:
+        """the stream's hard-symbol matrices [4 (pl, pu, s, t), 6400]: block bc of the L1 frame being received at bc * 800"""
+        out = np.zeros((4, abi.AM_SYMS), dtype=np.uint8)
+        self._check(self.lib.nrsc5hip_debug_fetch_am_sym(self._h, stream, out.ctypes.data))
+        return out
 
     def stage_nco_exact(self, start, inc, active, nco_mode, n: int | None = None):
         """nrsc5hip_stage_nco_exact: launch_nco_exact on streams 0 .. n-1.  start / inc float32 [n, 2], active / nco_mode int [n] ->

@@ -508,9 +508,22 @@ def run_am_capture(lib, cap, chunk=32768):
     return E, recs, eng.am_records_to_log(E, 0, recs)
 
 
-def am_symbol_agreement(E, ol):
-    """Hard symbols are diagnostic (a cell on a decision boundary may flip with a 1-ulp libm difference)."""
-    return None
+def am_symbol_agreement(E, ol, stream=0):
+    """The share of hard symbols in which the stream's symbol matrices (nrsc5hip_debug_fetch_am_sym, after the capture) differ from the oracle's `amsym` records:
+    for every block count the matrices hold the block the receiver last filed under it -- the last, partly filled L1 frame and behind it what is left of the frame
+    before -- and so does the last `amsym` record of that bc.  -> (share, cells compared), or (None, 0) for a log without such records.  A cell that sits on a slicer
+    boundary may flip with the last ulp of a float, so the share is bounded, not zero (check_am_oracle_end_to_end); every cell AWAY from a boundary is compared exactly, block
+    by block against the float64 model, in tests/am_checks.py."""
+    last = {}
+    for k, v in ol:
+        if k == "amsym":
+            last[v["bc"]] = v
+    if not last:
+        return None, 0
+    sym = E.debug_fetch_am_sym(stream).reshape(4, 8, 800)
+    differ = sum(int((sym[p, bc] != v[key]).sum()) for bc, v in last.items() for p, key in enumerate(("pl", "pu", "s", "t")))
+    cells = 4 * 800 * len(last)
+    return differ / cells, cells
 
 
 def check_am_oracle_end_to_end(lib, oracle, kw, chunk=32768, max_sym_diff=0.002):
@@ -521,6 +534,10 @@ def check_am_oracle_end_to_end(lib, oracle, kw, chunk=32768, max_sym_diff=0.002)
     E, recs, log = run_am_capture(lib, cap, chunk=chunk)
     diffs = common.compare_logs(common.strip_states(ol), common.strip_states(log))
     assert not diffs, diffs[:10]
+    share, cells = am_symbol_agreement(E, ol)
+    assert (share is None) == (not any(k == "sync" for k, _ in ol)), "hard symbols are filed from the block that locks on"
+    print("hard symbols: %s of %d cells differ from the oracle's" % (share, cells))       # (None: the capture is too short to lock -- nothing was sliced)
+    assert share is None or share <= max_sym_diff, "%.5f of the %d hard symbols of the last blocks differ from the oracle's (bound %.5f)" % (share, cells, max_sym_diff)
     E.close()
     return log
 
