@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 18   /* 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 19   /* 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -1028,6 +1028,10 @@ long long nrsc5hip_fm_outputs_for(nrsc5hip_fm *fm, long long n_in);
 int  nrsc5hip_fm_process(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, int16_t *dev_out,
                          long long out_stride_elems, long long out_capacity, long long *n_out);
 int  nrsc5hip_fm_clip_counts(nrsc5hip_fm *fm, long long *counts /* [nchan][2]: L, R, since create / reset */);
+/* test hook (ABI 19): kernel launches the pushes have issued since create / reset -- per push the front end (when a d sample is new), the pilot
+ * sums (a block complete), the audio (an audio block due) and the kept tails (always); with RDS also the matched filter (a grid point new) and,
+ * when a window was decided, decisions, groups and the kept y.  The stage hooks are not counted */
+int  nrsc5hip_fm_debug_launches(nrsc5hip_fm *fm, long long *count);
 /* level a and stereo flag of the last audio block delivered (0 before the first); either pointer may be NULL */
 int  nrsc5hip_fm_pilot(nrsc5hip_fm *fm, float *level /* [nchan] */, int *stereo /* [nchan] */);
 /* stage hook: d (host, [nchan][(n_in + 1) / 2]) and the block sums (host, [nchan][((n_in + 1) / 2) / 540][2], may be NULL) of n_in samples
@@ -1038,6 +1042,78 @@ int  nrsc5hip_stage_fm_mpx(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_
  * NRSC5HIP_EOVERFLOW (audio_capacity) and an append the engine refuses leave both objects as before the call. */
 int  nrsc5hip_chan_feed_fm(nrsc5hip_chan *c, nrsc5hip_engine *e, const int *stream_ids, nrsc5hip_fm *fm, const void *dev_in, long long n_in,
                            int16_t *dev_audio, long long audio_stride_elems, long long audio_capacity, long long *n_audio);
+
+/* ---- RDS / RBDS of the analog host (ABI 19): programme identification, station name, RadioText and clock from the 57 kHz subcarrier ----
+ * Opt-in per analog FM object (nrsc5hip_fm_rds_enable); it then runs inside every nrsc5hip_fm_process / nrsc5hip_chan_feed_fm on the same
+ * stream, from the discriminator output d[m] at Fs1 (the channel filter is flat to 95 kHz).  Every rate is exact on the Fs1 grid: 57 kHz is
+ * 1824 / 11907 cycles per sample, a bit is 11907 / 38 samples, so bit timing is a function of absolute sample indices (64-bit integers): no
+ * NCO, no loop filter, no recurrence in the signal path, and any chunking of a session gives identical bits, events and counters.
+ *   baseband        v[m] = d[m] exp(-j 2 pi ((1824 m) mod 11907) / 11907).  The pilot is not used: detection is differential, the carrier's
+ *                   phase drops out, and a station without a pilot decodes as well
+ *   matched filter  on a grid of 8 points per bit: point r at t_r = 11907 r / 304 samples, i = floor(t_r), phase (11907 r) mod 304 exactly;
+ *                   y[r] = sum_j tab[phase][j] v[i + j - 627], j < 1255 (every |m - t_r| <= 2 T, T the bit period; samples in front of the
+ *                   stream zero); tab = g(tau + T / 4) w(tau) at tau = j - 627 - phase / 304: g(t) = h(t) - h(t - T / 2), h(t) =
+ *                   sinc(4 t / T + 1/2) + sinc(4 t / T - 1/2) (the standard's cos(pi f T / 4) spectrum), w the Hann window over |tau| <= 2 T,
+ *                   zero beyond; double on the host, stored float32
+ *   timing          windows of 152 bits = 1216 grid points = 47 628 samples: E_w[s] = sum over the window's bits k of |y[8 k + s]|^2 (lane
+ *                   8 g + s sums k = g, g + 8, .. in order, then a butterfly over g), s_w = argmax, ties to the lowest s; sampling points
+ *                   8 k + s_w.  Seam to window w - 1: gap = 8 + s_w - s_{w-1}; gap < 4: the first point of w is dropped; gap > 12: one point
+ *                   is inserted 8 grid steps behind the last point of w - 1
+ *   decisions       data bit i = Re(y[r_i] conj y[r_{i-1}]) < 0 (differentially coherent detection of the differentially encoded stream);
+ *                   the first point of a session gives no bit.  A window is decided once every y it reads exists: window w after
+ *                   latency_in + 95 256 w input samples (nrsc5hip_fm_rds_info; latency_in = 96 431).  There is no flush
+ *   blocks          (26, 16) code, generator x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1, offset words A 0x0FC, B 0x198, C 0x168, C' 0x350,
+ *                   D 0x1B4: a word is valid with offset X when its remainder equals X.  Searching: every bit position is tested against
+ *                   all five; sync when three valid words follow each other 26 bits apart in the cyclic order A, B, C or C', D (nothing is
+ *                   corrected).  In sync: only the expected offset (C, then C' in the third place); a burst of at most correct_burst bits is
+ *                   corrected by syndrome; sync is lost after 16 invalid blocks with no block valid as received between them (a corrected block
+ *                   neither counts nor ends the run: behind a bit slip the shifted blocks have few syndromes, some of them correctable)
+ *   groups          four blocks from an A on, all valid, else the group is dropped and counted; blocks between the sync and the first A
+ *                   belong to no group
+ *   content         PI (block A, and block C of version-B groups); PTY, TP (every group); TA, MS, DI and the name (0A / 0B: reported when all
+ *                   four segments have arrived since the last reset or PI change and it differs from the last one reported); RadioText
+ *                   (2A: 16 x 4 bytes, 2B: 16 x 2; a change of the A/B flag or of the version clears the buffer; reported when segments
+ *                   0 .. L - 1 are present, L ending at the segment that holds 0x0D, else 16, and the text differs from the last one
+ *                   reported); clock (4A: MJD, hour, minute, signed offset in half hours; once per distinct value); every other group is
+ *                   counted by type and version.  A PI change forgets name and text.  Text is raw bytes. */
+typedef struct nrsc5hip_rds_config {
+    int raw_groups;                      /* also an NRSC5HIP_RDS_GROUP event per group */
+    int correct_burst;                   /* 0 .. 2 bits corrected per block while in sync */
+} nrsc5hip_rds_config;
+enum { NRSC5HIP_RDS_PI = 1, NRSC5HIP_RDS_PS = 2, NRSC5HIP_RDS_RT = 3, NRSC5HIP_RDS_CLOCK = 4, NRSC5HIP_RDS_GROUP = 5 };
+/* v: PI {pi}; PS {pi} + 8 bytes; RT {pi, A/B flag} + the text; CLOCK {mjd, hour, minute, offset}; GROUP {a, b, c, d}.  group: index of the
+ * group since the last reset (dropped ones counted); bit: index of the bit that completed it */
+typedef void (*nrsc5hip_rds_cb)(void *opaque, int channel, int kind, long long group, long long bit, const int32_t v[8], const uint8_t *data,
+                                unsigned len);
+typedef struct nrsc5hip_rds_info {
+    int32_t pi;                          /* -1: none yet */
+    int32_t pty, tp, ta, ms, di, synced;
+    int32_t ps_len; uint8_t ps[8];       /* the last name reported; ps_len -1: none */
+    int32_t rt_len, rt_ab; uint8_t rt[64];
+    int32_t have_clock, mjd, hour, minute, offset_half_hours;
+} nrsc5hip_rds_info;
+/* bits, blocks valid / corrected / invalid, groups, groups dropped, syncs gained / lost, seam drops / inserts, groups by type and version
+ * (0A, 0B, 1A, ..), events */
+#define NRSC5HIP_RDS_NSTATS 43
+/* cfg NULL: no raw groups, bursts of 2.  Only before the first nrsc5hip_fm_process / nrsc5hip_chan_feed_fm of the object; nrsc5hip_fm_reset
+ * resets the RDS state as well */
+int  nrsc5hip_fm_rds_enable(nrsc5hip_fm *fm, const nrsc5hip_rds_config *cfg);
+/* the events appended since the last read, channel by channel, each channel's in order; -> events delivered, or < 0 */
+int  nrsc5hip_fm_rds_read(nrsc5hip_fm *fm, nrsc5hip_rds_cb cb, void *opaque);
+int  nrsc5hip_fm_rds_get(nrsc5hip_fm *fm, int channel, nrsc5hip_rds_info *out);
+int  nrsc5hip_fm_rds_stats(nrsc5hip_fm *fm, int channel, long long stats[NRSC5HIP_RDS_NSTATS]);
+int  nrsc5hip_fm_rds_info(nrsc5hip_fm *fm, int *taps, int *phases, int *points_per_bit, int *window_bits, long long *latency_in);   /* any pointer may be NULL */
+int  nrsc5hip_fm_rds_taps(nrsc5hip_fm *fm, float *taps /* [phases][taps] */);
+/* stage hook: n_in samples taken as a whole session from n = 0 -> on the host y [nchan][points][2], the window energies [nchan][windows][8],
+ * s_w [nchan][windows], the decisions [nchan][windows][160] (one byte per bit) and their counts [nchan][windows], before any decoding; points =
+ * ((304 (m - 628) + 303) / 11907) + 1 for m = (n_in + 1) / 2 >= 628, windows = points / 1216.  Any pointer may be NULL.  The object's own
+ * session is not touched */
+int  nrsc5hip_stage_rds_mf(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *y_out, float *energy_out,
+                           int32_t *s_out, uint8_t *bits_out, int32_t *counts_out);
+/* stage hook: bits (host, one byte each) fed straight to the group decoder of the listed channels (channels NULL: 0 .. n - 1); reset_at[i]
+ * (or NULL): channel i's decoder is reset in front of that bit of the call (nbits[i]: behind the last; -1: never).  Events come with
+ * nrsc5hip_fm_rds_read */
+int  nrsc5hip_stage_rds_groups(nrsc5hip_fm *fm, int n, const int *channels, const uint8_t *const *bits, const int *nbits, const int *reset_at);
 
 #ifdef __cplusplus
 }

@@ -169,5 +169,40 @@ def bind_am_block(lib) -> None:
     lib.nrsc5hip_debug_fetch_am_sym.argtypes = [vp, ci, vp]
 
 
+class _RdsConfig(ctypes.Structure):
+    """nrsc5hip_rds_config"""
+    _fields_ = [("raw_groups", ctypes.c_int), ("correct_burst", ctypes.c_int)]
+
+
+class RdsInfo(ctypes.Structure):
+    """nrsc5hip_rds_info"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("pi", "pty", "tp", "ta", "ms", "di", "synced", "ps_len")] + [("ps", ctypes.c_uint8 * 8)] + \
+               [("rt_len", ctypes.c_int32), ("rt_ab", ctypes.c_int32), ("rt", ctypes.c_uint8 * 64)] + \
+               [(n, ctypes.c_int32) for n in ("have_clock", "mjd", "hour", "minute", "offset_half_hours")]
+
+
+RDS_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int32),
+                          ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)                                     # nrsc5hip_rds_cb
+RDS_KINDS = (None, "pi", "ps", "rt", "clock", "group")                                                  # NRSC5HIP_RDS_*
+RDS_STATS = (("bits", "blocks_valid", "blocks_corrected", "blocks_invalid", "groups", "groups_dropped", "syncs_gained", "syncs_lost", "seam_drops",
+              "seam_inserts") + tuple("g%d%s" % (t, v) for t in range(16) for v in "AB") + ("events",))      # nrsc5hip_fm_rds_stats
+assert len(RDS_STATS) == 43
+RDS_BITS_STRIDE = 160                    # bytes per window in what nrsc5hip_stage_rds_mf returns
+
+
+def bind_rds(lib) -> None:
+    """argument types of RDS on the analog FM object (include/nrsc5hip.h, ABI 19)"""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    lib.nrsc5hip_fm_debug_launches.argtypes = [vp, ctypes.POINTER(ll)]
+    lib.nrsc5hip_fm_rds_enable.argtypes = [vp, ctypes.POINTER(_RdsConfig)]
+    lib.nrsc5hip_fm_rds_read.argtypes = [vp, RDS_CB, vp]
+    lib.nrsc5hip_fm_rds_get.argtypes = [vp, ci, ctypes.POINTER(RdsInfo)]
+    lib.nrsc5hip_fm_rds_stats.argtypes = [vp, ci, vp]
+    lib.nrsc5hip_fm_rds_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ll)]
+    lib.nrsc5hip_fm_rds_taps.argtypes = [vp, vp]
+    lib.nrsc5hip_stage_rds_mf.argtypes = [vp, vp, ll, ll, vp, vp, vp, vp, vp]
+    lib.nrsc5hip_stage_rds_groups.argtypes = [vp, ci, vp, vp, vp, vp]
+
+
 class Nrsc5HipError(RuntimeError):
     pass

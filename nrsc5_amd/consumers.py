@@ -231,6 +231,40 @@ def sis_text(enc: int, data: bytes) -> str | None:
     return None if raw is None else raw.decode("utf-8", errors="replace")
 
 
+def rds_text(data: bytes) -> str:
+    """RDS name or RadioText for display: 0x20 .. 0x7E as ASCII, any other byte as U+FFFD; trailing spaces and the 0x0D that ends a text cut"""
+    data = bytes(data)
+    if b"\r" in data:
+        data = data[:data.index(b"\r")]
+    return "".join(chr(b) if 0x20 <= b <= 0x7E else "\ufffd" for b in data).rstrip(" ")
+
+
+def rds_callsign(pi: int) -> str | None:
+    """the RBDS rule: PI 0x1000 .. 0x54A7 is K + three letters in base 26, 0x54A8 .. 0x994F is W + three letters; anything else has no call sign"""
+    if 0x1000 <= pi <= 0x54A7:
+        first, n = "K", pi - 0x1000
+    elif 0x54A8 <= pi <= 0x994F:
+        first, n = "W", pi - 0x54A8
+    else:
+        return None
+    return first + "".join(chr(65 + n // k % 26) for k in (676, 26, 1))
+
+
+def rds_event_fields(kind: str, v, data: bytes) -> dict:
+    """An event of k_rds_groups as named fields; text decoded by rds_text, the raw bytes beside it"""
+    if kind == "pi":
+        return {"pi": v[0], "callsign": rds_callsign(v[0])}
+    if kind == "ps":
+        return {"pi": v[0], "ps": rds_text(data), "raw": bytes(data)}
+    if kind == "rt":
+        return {"pi": v[0], "ab": v[1], "text": rds_text(data), "raw": bytes(data)}
+    if kind == "clock":
+        return {"mjd": v[0], "hour": v[1], "minute": v[2], "offset_half_hours": v[3]}
+    if kind == "group":
+        return {"blocks": tuple(v[:4])}
+    raise ValueError(kind)
+
+
 def _sis_device_info(p) -> dict:
     """manufacturer id, versions and status of parameters 4..7 / 8..11 (pids.c:698-744)"""
     ver = lambda a, b: [(a >> 11) & 0x1f, (a >> 6) & 0x1f, (a >> 1) & 0x1f, b]

@@ -3,7 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "nrsc5hip.h"
+#include "rds.h"
 
 namespace nrsc5 {
 namespace fm {
@@ -54,13 +56,43 @@ struct KeepArgs {
     const int *hist_old; int *hist_new;
 };
 
+// Where the launch_* functions of k_fm_audio.hip and k_rds.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
+// for the length of a push (nrsc5hip_fm_debug_launches); nullptr anywhere else (the stage hooks are not counted)
+extern thread_local long long *launch_count;
+inline void count_launch() { if (launch_count) ++*launch_count; }
+struct CountLaunches {
+    explicit CountLaunches(long long *to) { launch_count = to; }
+    ~CountLaunches() { launch_count = nullptr; }
+};
+
 void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a);
 void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a);
 void launch_audio(hipStream_t s, int blocks, int nchan, const AudioArgs &a);
 void launch_keep(hipStream_t s, int nchan, const KeepArgs &a);
 
 }  // namespace fm
+}  // namespace nrsc5
 
+struct nrsc5hip_fm {
+    int device = 0, nchan = 0, tb = 0;
+    double deemphasis_us = 75.0;
+    float pilot_min = 0.03f, aq = 0, bq = 0, wsum = 0;
+    std::vector<float> ha, tab, scale;                       // tab: host copy [PHASES][tb]
+    hipStream_t stream = nullptr;
+    float *d_ha = nullptr, *d_tab = nullptr, *d_win = nullptr, *d_scale = nullptr, *d_pilot = nullptr;
+    float2 *d_cs = nullptr;
+    int *d_hist[2] = {nullptr, nullptr};
+    float *d_d[2] = {nullptr, nullptr}; long long d_cap = 0, d_base = 0;     // d[m], m in [d_base, m_total), of channel c at d_d[cur][c * d_cap + m - d_base]
+    float2 *d_p[2] = {nullptr, nullptr}; long long p_cap = 0, p_base = 0;    // block sums [p_base, blocks)
+    int cur = 0;
+    unsigned long long *d_clips = nullptr;
+    long long n_total = 0, m_total = 0, blocks = 0, audio_blocks = 0;        // input samples, d samples, complete pilot blocks, audio blocks delivered
+    long long launches = 0;                                  // kernel launches of the pushes since create / reset
+    bool processed = false;                                  // a push has been launched since create
+    nrsc5::RdsHost *rds = nullptr;                           // RDS (rds.hip), once enabled
+};
+
+namespace nrsc5 {
 // for nrsc5hip_chan_feed_fm: the checks of nrsc5hip_fm_process without its launch, and the launch without a wait, on the caller's stream
 int fm_nchan(const nrsc5hip_fm *fm);
 int fm_device(const nrsc5hip_fm *fm);

@@ -46,32 +46,13 @@ std::vector<double> kaiser_lowpass(int taps, double fc, double att_db)
     return h;
 }
 
-}  // namespace
-
-struct nrsc5hip_fm {
-    int device = 0, nchan = 0, tb = 0;
-    double deemphasis_us = 75.0;
-    float pilot_min = 0.03f, aq = 0, bq = 0, wsum = 0;
-    std::vector<float> ha, tab, scale;                       // tab: host copy [PHASES][tb]
-    hipStream_t stream = nullptr;
-    float *d_ha = nullptr, *d_tab = nullptr, *d_win = nullptr, *d_scale = nullptr, *d_pilot = nullptr;
-    float2 *d_cs = nullptr;
-    int *d_hist[2] = {nullptr, nullptr};
-    float *d_d[2] = {nullptr, nullptr}; long long d_cap = 0, d_base = 0;     // d[m], m in [d_base, m_total), of channel c at d_d[cur][c * d_cap + m - d_base]
-    float2 *d_p[2] = {nullptr, nullptr}; long long p_cap = 0, p_base = 0;    // block sums [p_base, blocks)
-    int cur = 0;
-    unsigned long long *d_clips = nullptr;
-    long long n_total = 0, m_total = 0, blocks = 0, audio_blocks = 0;        // input samples, d samples, complete pilot blocks, audio blocks delivered
-};
-
-namespace {
-
 void free_fm(nrsc5hip_fm *f)
 {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     (void)hipFree(f->d_ha); (void)hipFree(f->d_tab); (void)hipFree(f->d_win); (void)hipFree(f->d_scale); (void)hipFree(f->d_pilot); (void)hipFree(f->d_cs);
     for (int i = 0; i < 2; i++) { (void)hipFree(f->d_hist[i]); (void)hipFree(f->d_d[i]); (void)hipFree(f->d_p[i]); }
     (void)hipFree(f->d_clips);
+    nrsc5::rds_free(f->rds);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -83,8 +64,8 @@ int fm_zero_state(nrsc5hip_fm *f)
     HIPCHK(hipMemsetAsync(f->d_clips, 0, sizeof(unsigned long long) * 2 * f->nchan, f->stream));
     HIPCHK(hipMemsetAsync(f->d_pilot, 0, sizeof(float) * 2 * f->nchan, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
-    f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0;
-    return 0;
+    f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0; f->launches = 0;
+    return f->rds ? nrsc5::rds_reset(f) : 0;
 }
 
 struct Counts { long long n1, m1, b1, a1; };
@@ -130,6 +111,8 @@ int fm_reserve(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1)
 
 }  // namespace
 
+thread_local long long *nrsc5::fm::launch_count = nullptr;
+
 int nrsc5::fm_nchan(const nrsc5hip_fm *f) { return f->nchan; }
 int nrsc5::fm_device(const nrsc5hip_fm *f) { return f->device; }
 
@@ -160,6 +143,8 @@ int nrsc5::fm_check(nrsc5hip_fm *f, long long n_in, const int16_t *dev_out, long
 int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long long in_stride, long long n_in, int16_t *out, long long out_stride)
 {
     if (n_in <= 0) return 0;
+    f->processed = true;
+    CountLaunches counting(&f->launches);
     const Counts c = counts_after(f, n_in);
     int rc = fm_reserve(f, s, c.m1, c.b1);
     if (rc) return rc;
@@ -171,6 +156,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
         launch_front(s, (int)((a.m_count + FT - 1) / FT), f->nchan, a);
         HIPCHK(hipGetLastError());
     }
+    if (f->rds && (rc = nrsc5::rds_launch(f, s, d, c.m1))) return rc;
     if (c.b1 > f->blocks) {
         PilotArgs a;
         a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.cs = f->d_cs; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.j0 = f->blocks;
@@ -189,6 +175,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     long long d_base = (long long)BLOCK * c.a1 - f->tb - 1, p_base = c.a1 - W;
     if (d_base < 0) d_base = 0;
     if (p_base < 0) p_base = 0;
+    if (f->rds && nrsc5::rds_d_need(f) < d_base) d_base = nrsc5::rds_d_need(f);     // ... and d from the first tap of the first grid point not yet summed
     KeepArgs k;
     k.d_old = d; k.d_new = f->d_d[f->cur ^ 1]; k.d_stride = f->d_cap; k.d_shift = d_base - f->d_base; k.d_count = c.m1 - d_base;
     k.p_old = p; k.p_new = f->d_p[f->cur ^ 1]; k.p_stride = f->p_cap; k.p_shift = p_base - f->p_base; k.p_count = c.b1 - p_base;
@@ -340,6 +327,13 @@ extern "C" int nrsc5hip_fm_process(nrsc5hip_fm *f, const int16_t *dev_in, long l
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(f->stream));               // outputs complete, dev_in no longer read
     if (n_out) *n_out = nout;
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_debug_launches(nrsc5hip_fm *f, long long *count)
+{
+    if (!f || !count) FAIL(NRSC5HIP_EINVAL, "null argument");
+    *count = f->launches;
     return 0;
 }
 

@@ -197,21 +197,25 @@ __global__ __launch_bounds__(256) void k_fm_keep(KeepArgs a)
 
 void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a)
 {
+    count_launch();
     hipLaunchKernelGGL(k_fm_front, dim3(tiles, nchan), dim3(256), sizeof(float2) * (2 * FT + TA + FT + 1), s, a);
 }
 
 void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a)
 {
+    count_launch();
     hipLaunchKernelGGL(k_fm_pilot, dim3(blocks, nchan), dim3(64), 0, s, a);
 }
 
 void launch_audio(hipStream_t s, int blocks, int nchan, const AudioArgs &a)
 {
+    count_launch();
     hipLaunchKernelGGL(k_fm_audio, dim3(blocks, nchan), dim3(256), sizeof(float) * (2 * a.tb + 542 + 540 + 512), s, a);
 }
 
 void launch_keep(hipStream_t s, int nchan, const KeepArgs &a)
 {
+    count_launch();
     long long n = a.d_count > a.p_count ? a.d_count : a.p_count;
     if (n < HIST) n = HIST;
     long long blocks = (n + 255) / 256;

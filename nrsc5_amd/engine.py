@@ -19,9 +19,9 @@ if _AB_LIB:
 
 from . import abi
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
-from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig
+from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
-                        sis_utf8, sis_text, _sis_device_info, sis_event_fields, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
+                        sis_utf8, sis_text, _sis_device_info, sis_event_fields, rds_text, rds_callsign, rds_event_fields, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
 
 
 def l2_frame_to_dict(fr: L2Frame) -> dict:
@@ -185,6 +185,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_fm_clip_counts.argtypes = [vp, vp]
     lib.nrsc5hip_fm_pilot.argtypes = [vp, vp, vp]
     lib.nrsc5hip_stage_fm_mpx.argtypes = [vp, vp, ll, ll, vp, vp]
+    abi.bind_rds(lib)
     lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_scan_destroy.argtypes = [vp]
     lib.nrsc5hip_scan_destroy.restype = None
@@ -220,7 +221,9 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_scan_create", "nrsc5hip_scan_destroy", "nrsc5hip_scan_reset", "nrsc5hip_scan_push", "nrsc5hip_scan_info",
     "nrsc5hip_scan_spectrum", "nrsc5hip_scan_detect", "nrsc5hip_scan_detect_psd",
     "nrsc5hip_fm_create", "nrsc5hip_fm_destroy", "nrsc5hip_fm_reset", "nrsc5hip_fm_info", "nrsc5hip_fm_taps", "nrsc5hip_fm_outputs_for",
-    "nrsc5hip_fm_process", "nrsc5hip_fm_clip_counts", "nrsc5hip_fm_pilot", "nrsc5hip_stage_fm_mpx", "nrsc5hip_chan_feed_fm"]
+    "nrsc5hip_fm_process", "nrsc5hip_fm_clip_counts", "nrsc5hip_fm_pilot", "nrsc5hip_stage_fm_mpx", "nrsc5hip_chan_feed_fm",
+    "nrsc5hip_fm_debug_launches", "nrsc5hip_fm_rds_enable", "nrsc5hip_fm_rds_read", "nrsc5hip_fm_rds_get", "nrsc5hip_fm_rds_stats", "nrsc5hip_fm_rds_info", "nrsc5hip_fm_rds_taps",
+    "nrsc5hip_stage_rds_mf", "nrsc5hip_stage_rds_groups"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -905,7 +908,8 @@ class FmDemod:
 
     AUDIO_RATE = FM_AUDIO_RATE
 
-    def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None):
+    def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None,
+                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2):
         self.lib = load_library(lib_path)
         self.nchan, self.device, self.deemphasis_us = int(nchan), device, float(deemphasis_us)
         self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), (self.nchan,)))
@@ -915,8 +919,76 @@ class FmDemod:
         ta, tb, ph, lat = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
         self._check(self.lib.nrsc5hip_fm_info(self._h, ctypes.byref(ta), ctypes.byref(tb), ctypes.byref(ph), ctypes.byref(lat)))
         self.taps_channel, self.taps_audio, self.phases, self.latency_in = ta.value, tb.value, ph.value, lat.value
+        self.rds = False
+        if rds:
+            try:
+                self.rds_enable(rds_raw_groups, rds_correct_burst)
+            except Nrsc5HipError:
+                self.close()                                       # the demodulator that was created goes with the failed constructor
+                raise
 
     _check = Channelizer._check
+
+    # ---- RDS / RBDS of the analog host (nrsc5hip_fm_rds_*) ----------------------------------------------------------------------
+    def rds_enable(self, raw_groups: bool = False, correct_burst: int = 2):
+        """only before the first push; from then on every process() also decodes RDS on the same stream"""
+        self._check(self.lib.nrsc5hip_fm_rds_enable(self._h, ctypes.byref(_RdsConfig(int(raw_groups), int(correct_burst)))))
+        self.rds = True
+        nt, ph, ppb, wb, lat = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_fm_rds_info(self._h, ctypes.byref(nt), ctypes.byref(ph), ctypes.byref(ppb), ctypes.byref(wb), ctypes.byref(lat)))
+        self.rds_taps, self.rds_phases, self.rds_points_per_bit, self.rds_window_bits, self.rds_latency_in = nt.value, ph.value, ppb.value, wb.value, lat.value
+
+    def rds_read(self) -> list:
+        """the events since the last read -> [{"channel", "kind", "group", "bit", "v", "data"}, ...], channel by channel, each channel's in order"""
+        out = []
+
+        def on_event(_opaque, channel, kind, group, bit, v, data, n):
+            out.append({"channel": channel, "kind": RDS_KINDS[kind], "group": group, "bit": bit, "v": [int(v[k]) for k in range(8)], "data": ctypes.string_at(data, n)})
+
+        self._check(min(self.lib.nrsc5hip_fm_rds_read(self._h, RDS_CB(on_event), None), 0))
+        return out
+
+    def rds_get(self, channel: int) -> dict:
+        """the snapshot of one channel: PI (-1: none), PTY, flags, the last name and text reported (None: none yet), clock, synced"""
+        info = RdsInfo()
+        self._check(self.lib.nrsc5hip_fm_rds_get(self._h, channel, ctypes.byref(info)))
+        return {"pi": info.pi, "pty": info.pty, "tp": info.tp, "ta": info.ta, "ms": info.ms, "di": info.di, "synced": info.synced,
+                "ps": bytes(info.ps) if info.ps_len >= 0 else None, "rt": bytes(info.rt[:info.rt_len]) if info.rt_len >= 0 else None, "rt_ab": info.rt_ab,
+                "clock": (info.mjd, info.hour, info.minute, info.offset_half_hours) if info.have_clock else None}
+
+    def rds_stats(self, channel: int) -> dict:
+        out = np.zeros(len(RDS_STATS), dtype=np.int64)
+        self._check(self.lib.nrsc5hip_fm_rds_stats(self._h, channel, out.ctypes.data))
+        return dict(zip(RDS_STATS, (int(x) for x in out)))
+
+    def rds_tables(self) -> np.ndarray:
+        """float32 [rds_phases][rds_taps]: the matched filter as stored"""
+        tab = np.zeros((self.rds_phases, self.rds_taps), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_fm_rds_taps(self._h, tab.ctypes.data))
+        return tab
+
+    def stage_rds_mf(self, dev_in: int, in_stride_elems: int, n_in: int) -> dict:
+        """nrsc5hip_stage_rds_mf -> {"y" complex64 [nchan][points], "energy" float32 [nchan][windows][8], "s" int32 [nchan][windows],
+        "bits": per channel a list of uint8 arrays, one per window}"""
+        m1 = (n_in + 1) // 2
+        points = 0 if m1 < 628 else (304 * (m1 - 628) + 303) // 11907 + 1
+        nw = points // (8 * self.rds_window_bits)
+        y = np.zeros((self.nchan, points), dtype=np.complex64)
+        energy, s = np.zeros((self.nchan, nw, 8), dtype=np.float32), np.zeros((self.nchan, nw), dtype=np.int32)
+        bits, counts = np.zeros((self.nchan, nw, RDS_BITS_STRIDE), dtype=np.uint8), np.zeros((self.nchan, nw), dtype=np.int32)
+        self._check(self.lib.nrsc5hip_stage_rds_mf(self._h, dev_in, in_stride_elems, n_in, y.ctypes.data, energy.ctypes.data, s.ctypes.data, bits.ctypes.data,
+                                                   counts.ctypes.data))
+        return {"y": y, "energy": energy, "s": s, "bits": [[bits[c, w, :counts[c, w]].copy() for w in range(nw)] for c in range(self.nchan)]}
+
+    def stage_rds_groups(self, bits, channels=None, reset_at=None):
+        """nrsc5hip_stage_rds_groups: bits[i] (uint8, one per bit) to the group decoder of channels[i] (default i); events come with rds_read()"""
+        arrs = [np.ascontiguousarray(b, dtype=np.uint8) for b in bits]
+        n = len(arrs)
+        ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrs])
+        counts = np.array([a.size for a in arrs], dtype=np.int32)
+        ch = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        rst = None if reset_at is None else np.ascontiguousarray(reset_at, dtype=np.int32)
+        self._check(self.lib.nrsc5hip_stage_rds_groups(self._h, n, _ptr(ch), ptrs, counts.ctypes.data, _ptr(rst)))
 
     def close(self):
         if self._h:
@@ -950,6 +1022,12 @@ class FmDemod:
         out = np.zeros((self.nchan, 2), dtype=np.int64)
         self._check(self.lib.nrsc5hip_fm_clip_counts(self._h, out.ctypes.data))
         return out
+
+    def launches(self) -> int:
+        """nrsc5hip_fm_debug_launches: kernel launches the pushes have issued since create / reset (test hook)"""
+        n = ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_fm_debug_launches(self._h, ctypes.byref(n)))
+        return n.value
 
     def pilot(self):
         """-> (level float32 [nchan], stereo bool [nchan]) of the last audio block delivered"""

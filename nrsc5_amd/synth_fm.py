@@ -6,7 +6,11 @@
 
 L and R are sums of tones a cos(2 pi f t + ph).  Every term of the MPX is a sinusoid (a tone, a tone times the subcarrier as a sum and a
 difference frequency, the pilot), so the phase integral is written in closed form and evaluated in float64 at every sample: no running
-sum, no drift.  Pre-emphasis is applied as the tone's gain sqrt(1 + (2 pi f tau)^2); the pilot's frequency may be off by some ppm."""
+sum, no drift.  Pre-emphasis is applied as the tone's gain sqrt(1 + (2 pi f tau)^2); the pilot's frequency may be off by some ppm.
+
+RDS / RBDS (the keyword `rds`): a 57 kHz subcarrier, 3 x the pilot's phase (its ppm included) plus `phase`, carrying the biphase symbols of a
+repeating list of groups -- check words with the offset words, differential encoding, two impulses per bit shaped with the closed-form h(t) of
+the standard (RdsSignal).  That term alone is no sinusoid: its phase integral is a float64 Simpson sum (RdsSignal.phase_integral)."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,8 +31,144 @@ def _tones(tones, preemph_us):
     return out
 
 
-def mpx_terms(left, right, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.0, preemph_us=None):
-    """-> [(amplitude, frequency Hz, phase)] of the MPX as a sum of a * sin(2 pi f t + phase) terms"""
+class Terms(list):
+    """the MPX's sinusoids, with the RDS term beside them"""
+    rds = None
+
+
+RDS_POLY = 0x5B9                                   # x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1
+RDS_OFFSETS = {"A": 0x0FC, "B": 0x198, "C": 0x168, "C'": 0x350, "D": 0x1B4}
+RDS_SPAN = 12                                      # bit periods of h(t) kept on either side of an impulse
+
+
+def rds_checkword(data: int) -> int:
+    """the 10 check bits of a 16-bit information word: remainder of data * x^10 by the generator, before the offset word"""
+    reg = (data & 0xFFFF) << 10
+    for k in range(25, 9, -1):
+        if reg >> k & 1:
+            reg ^= RDS_POLY << (k - 10)
+    return reg & 0x3FF
+
+
+def rds_bits(groups) -> np.ndarray:
+    """uint8 [104 * len(groups)]: the groups (a, b, c, d) as transmitted, most significant bit first, block 3 with C' when b names version B"""
+    out = []
+    for a, b, c, d in groups:
+        for word, off in ((a, "A"), (b, "B"), (c, "C'" if b >> 11 & 1 else "C"), (d, "D")):
+            v = (word & 0xFFFF) << 10 | (rds_checkword(word) ^ RDS_OFFSETS[off])
+            out.extend(v >> k & 1 for k in range(25, -1, -1))
+    return np.array(out, dtype=np.uint8)
+
+
+def rds_h(u: np.ndarray) -> np.ndarray:
+    """h at u = 4 t / T: sinc(u + 1/2) + sinc(u - 1/2) = cos(pi u) / (pi (1/4 - u^2)), the cosine-shaped spectrum on |f| <= 2 / T"""
+    return np.sinc(u + 0.5) + np.sinc(u - 0.5)
+
+
+def _rds_norm() -> float:
+    u = np.linspace(-4.0, 6.0, 20001)
+    return float(np.max(np.abs(rds_h(u) - rds_h(u - 2.0))))
+
+
+class RdsSignal:
+    """m(t) sin(3 (wp t + th) + phase): m(t) = sum_i (2 e_i - 1) g(t - (i + bit_offset) T) / max|g|, g(t) = h(t) - h(t - T / 2), e the
+    differentially encoded bits of the repeating group list.  T is 16 pilot cycles, or 1 / (1187.5 (1 + clock_ppm 1e-6)) s when clock_ppm is
+    given.  dev_hz is the peak deviation of an isolated symbol.  h is cut RDS_SPAN bit periods from its impulse (|h| < 1.4e-4 there)."""
+
+    def __init__(self, groups, pilot_hz, pilot_phase, dev_hz=2000.0, phase=0.0, clock_ppm=None, bit_offset=0.0):
+        self.groups = [tuple(int(w) & 0xFFFF for w in g) for g in groups]
+        self.dev_hz, self.phase, self.bit_offset = float(dev_hz), float(phase), float(bit_offset)
+        self.pilot_hz, self.pilot_phase = float(pilot_hz), float(pilot_phase)
+        self.bit_hz = self.pilot_hz / 16 if clock_ppm is None else PILOT_HZ / 16 * (1 + clock_ppm * 1e-6)
+        self.norm = _rds_norm()
+        self._frame = rds_bits(self.groups)
+
+    def bits(self, n: int) -> np.ndarray:
+        """the first n data bits (the group list repeats)"""
+        return np.resize(self._frame, n)
+
+    def envelope(self, t: np.ndarray) -> np.ndarray:
+        """m(t): cos(pi u) is common to every impulse (they sit 2 apart in u), so one cosine and 4 RDS_SPAN + 1 divisions per sample"""
+        t = np.asarray(t, dtype=np.float64)
+        u = 4.0 * (t * self.bit_hz - self.bit_offset)                       # impulse j (two per bit) at u = 2 j
+        nbits = int(np.ceil(max(float(u.max()), 0.0) / 4)) + RDS_SPAN + 2 if u.size else 1
+        e = np.bitwise_xor.accumulate(self.bits(nbits)).astype(np.float64) * 2 - 1
+        pad = 2 * RDS_SPAN + 2
+        c = np.zeros(2 * nbits + 2 * pad)
+        c[pad:pad + 2 * nbits:2] = e
+        c[pad + 1:pad + 2 * nbits:2] = -e
+        out = np.empty(t.size)
+        k = np.arange(-2 * RDS_SPAN, 2 * RDS_SPAN + 1)
+        for a in range(0, t.size, 1 << 16):
+            uu = u[a:a + (1 << 16)]
+            j0 = np.floor(uu / 2 + 0.5).astype(np.int64)
+            du = (uu - 2 * j0)[:, None] - 2 * k[None, :]                   # u relative to impulse j0 + k
+            den = np.pi * (0.25 - du * du)
+            near = np.abs(den) < 1e-6
+            w = np.cos(np.pi * uu)[:, None] / np.where(near, 1.0, den)
+            if near.any():
+                w[near] = rds_h(du[near])
+            idx = j0[:, None] + k[None, :] + pad
+            ok = (idx >= 0) & (idx < c.size)
+            out[a:a + uu.size] = np.sum(np.where(ok, c[np.clip(idx, 0, c.size - 1)], 0.0) * w, axis=1)
+        return out / self.norm
+
+    def value(self, t: np.ndarray) -> np.ndarray:
+        t = np.asarray(t, dtype=np.float64)
+        return self.envelope(t) * np.sin(3 * (2 * np.pi * self.pilot_hz * t + self.pilot_phase) + self.phase)
+
+    def phase_integral(self, n: int, fs: float, over: int = 8) -> np.ndarray:
+        """integral of value() from 0 to k / fs, k < n: composite Simpson with `over` (even, >= 8) steps per sample, float64.  Error: per second of
+        signal at most hs^4 / 180 * max|value''''| <= (2 pi 59.4 kHz hs)^4 / 180 * 1.6 with hs = 1 / (over fs) -- 1.4e-7 s/s at 744 187.5 S/s, so
+        the carrier's phase 2 pi dev_hz * integral is off by less than 1.8e-3 rad per second at dev_hz = 2 kHz if every step erred alike; the
+        integrand alternates and the measured error (against over = 32) is below 1e-6 rad.  The running sum of n float64 terms adds ~1e-13."""
+        assert over >= 8 and over % 2 == 0
+        if n <= 1:
+            return np.zeros(n)
+        t = np.arange((n - 1) * over + 1, dtype=np.float64) / (fs * over)
+        v = self.value(t)
+        w = np.full(over + 1, 2.0)
+        w[1::2] = 4.0
+        w[0] = w[-1] = 1.0
+        cells = v[:-1].reshape(n - 1, over)
+        per = cells @ w[:-1] + v[over::over] * w[-1]
+        out = np.zeros(n)
+        np.cumsum(per / (3.0 * fs * over), out=out[1:])
+        return out
+
+
+def rds_groups(pi: int, ps: str = "        ", text: str | None = None, clock=None, pty: int = 0, tp: int = 0, ta: int = 0, ms: int = 1, ab: int = 0,
+               version_b: bool = False, extra=()) -> list:
+    """a group schedule [(a, b, c, d), ...]: the four 0A (or 0B) groups of the name, then the text as 2A (2B) groups (ended by 0x0D when shorter
+    than the 64 (32) characters), then one 4A group for clock = (mjd, hour, minute, offset in half hours), then `extra` as they are"""
+    ver = 1 if version_b else 0
+    head = lambda gt, v: (gt & 15) << 12 | v << 11 | (tp & 1) << 10 | (pty & 31) << 5
+    name = ps.encode("latin-1").ljust(8)[:8]
+    out = []
+    for seg in range(4):
+        b = head(0, ver) | (ta & 1) << 4 | (ms & 1) << 3 | (1 if seg == 3 else 0) << 2 | seg
+        out.append((pi, b, pi if ver else 0xE0CD, name[2 * seg] << 8 | name[2 * seg + 1]))
+    if text is not None:
+        per = 2 if ver else 4
+        raw = text.encode("latin-1")[:16 * per]
+        if len(raw) < 16 * per:
+            raw += b"\r"
+        raw = raw.ljust(-(-len(raw) // per) * per)
+        for seg in range(len(raw) // per):
+            b = head(2, ver) | (ab & 1) << 4 | seg
+            q = raw[per * seg:per * seg + per]
+            out.append((pi, b, pi, q[0] << 8 | q[1]) if ver else (pi, b, q[0] << 8 | q[1], q[2] << 8 | q[3]))
+    if clock is not None:
+        mjd, hour, minute, off = clock
+        b = head(4, 0) | (mjd >> 15 & 3)
+        out.append((pi, b, (mjd & 0x7FFF) << 1 | (hour >> 4 & 1), (hour & 15) << 12 | (minute & 63) << 6 | (1 if off < 0 else 0) << 5 | (abs(off) & 31)))
+    out.extend(tuple(g) for g in extra)
+    return out
+
+
+def mpx_terms(left, right, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.0, preemph_us=None, rds=None):
+    """-> [(amplitude, frequency Hz, phase)] of the MPX as a sum of a * sin(2 pi f t + phase) terms; with `rds` the list also carries the
+    RDS term as its attribute .rds (an RdsSignal), which mpx() and fm_phase() add"""
     L, R = _tones(left, preemph_us), _tones(right, preemph_us)
     terms = []
     for sign_d, tones in ((1.0, L), (-1.0, R)):
@@ -40,6 +180,9 @@ def mpx_terms(left, right, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.0, preemph_us
                 terms.append((sign_d * 0.9 * a / 4, fs2 - f, th2 - ph))
     if pilot is not None:
         terms.append((float(pilot), PILOT_HZ * (1 + pilot_ppm * 1e-6), pilot_phase))
+    if rds is not None:
+        terms = Terms(terms)
+        terms.rds = RdsSignal(pilot_hz=PILOT_HZ * (1 + pilot_ppm * 1e-6), pilot_phase=pilot_phase, **rds)
     return terms
 
 
@@ -48,6 +191,9 @@ def mpx(n: int, terms, fs: float = FS) -> np.ndarray:
     out = np.zeros(n)
     for a, f, ph in terms:
         out += a * np.sin(2 * np.pi * f * t + ph)
+    rds = getattr(terms, "rds", None)
+    if rds is not None:
+        out += rds.dev_hz / DEV_HZ * rds.value(t)
     return out
 
 
@@ -57,12 +203,15 @@ def fm_phase(n: int, terms, fs: float = FS, dev_hz: float = DEV_HZ) -> np.ndarra
     out = np.zeros(n)
     for a, f, ph in terms:
         out += a * dev_hz / f * (np.cos(ph) - np.cos(2 * np.pi * f * t + ph))
+    rds = getattr(terms, "rds", None)
+    if rds is not None:
+        out += 2 * np.pi * dev_hz * (rds.dev_hz / DEV_HZ) * rds.phase_integral(n, fs)
     return out
 
 
-def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, amp=8000.0, cnr_db=None, seed=0) -> np.ndarray:
+def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, amp=8000.0, cnr_db=None, seed=0, rds=None) -> np.ndarray:
     """int16 [n, 2]: the host as cs16 at 744 187.5 S/s.  cnr_db: white noise over the whole sampled band, carrier power / noise power"""
-    terms = mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us)
+    terms = mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds)
     x = amp * np.exp(1j * fm_phase(n, terms))
     if cnr_db is not None:
         rng = np.random.default_rng(seed)
@@ -74,6 +223,6 @@ def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3
     return out
 
 
-def fm_carrier(n: int, left=(), right=(), fs: float = FS, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None) -> np.ndarray:
+def fm_carrier(n: int, left=(), right=(), fs: float = FS, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, rds=None) -> np.ndarray:
     """complex128 [n]: the unit-amplitude host at any sample rate (for a wideband scene: scale, shift and add it)"""
-    return np.exp(1j * fm_phase(n, mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us), fs))
+    return np.exp(1j * fm_phase(n, mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds), fs))

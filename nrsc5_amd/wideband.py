@@ -13,6 +13,8 @@ audio programs (the reference's NRSC5_EVENT_HDC packets, as `nrsc5 --dump-hdc` f
 DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets N bytes B` line per file at the end.
 --dump-analog DIR writes every station's analog FM programme, demodulated on the device (nrsc5hip_fm_*), as DIR/station<k>_<offset in Hz>_analog.wav
 (44.1 kHz, 16 bit, stereo; --deemphasis 75, 50 or 0 us) and prints one `analog frames N` line per file at the end.
+--rds decodes RDS / RBDS of every station's analog host on the device and prints one line per report: `station 1 (+0.0 kHz): RDS PI 0x3AAB (KQED)`,
+`... RDS PS "KEXP-FM "`, `... RDS RT "..."`, `... RDS clock MJD 60310 13:37 UTC-07:00`.
 --dump-aas-files DIR writes every station's complete LOT files (album art, station logos, text files) as `nrsc5 --dump-aas-files` names them,
 DIR/station<k>_<offset in Hz>_<lot>_<name>, and prints the reference's `SIG Service:` / `Audio component:` / `Data component:` / `LOT file:` lines; the
 Station Information Guide and the files are put together on the device (nrsc5hip_aas_feed), only complete files reach the host.  FILE may be `-` (standard input, read in
@@ -69,11 +71,16 @@ class WidebandReceiver:
     outputs, nrsc5hip_chan_feed_fm: the channelized samples never visit the host; deemphasis_us 75, 50 or 0).  audio[s] collects int16 arrays
     of shape (n, 2) -- 44.1 kS/s stereo frames L, R -- and on_audio(station, pcm), if given, sees each push's new block; stereo[s] and pilot[s]
     hold the flag and the pilot level of the last block, and an ("analog", {"stereo", "pilot"}) event behind that station's other events of the
-    push says when the flag changes.  The demodulator looks 18 359 input samples ahead and has no flush: the last 25 ms of a session stay undelivered."""
+    push says when the flag changes.  The demodulator looks 18 359 input samples ahead and has no flush: the last 25 ms of a session stay undelivered.
+    rds=True: the receiver also decodes RDS / RBDS of every station's analog host on the device (FmDemod(rds=True); it creates the FmDemod if
+    analog did not, and audio is not collected then).  Every report of the decoder becomes an ("rds", {"kind": "pi" / "ps" / "rt" / "clock", ...})
+    event (fields as eng.rds_event_fields) behind that station's other events of the push, and rds_info[s] is the station's snapshot
+    (FmDemod.rds_get: pi, pty, flags, ps, rt, clock, synced).  A timing window of 152 bits is decided 96 431 input samples after its first
+    sample is complete; there is no flush."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
                  programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
-                 lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None):
+                 lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None, rds: bool = False):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -109,7 +116,10 @@ class WidebandReceiver:
         self.sis = eng.SisConsumer(self.engine, self.k) if sis else None
         self.analog = bool(analog)
         self.on_audio = on_audio
-        self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path) if self.analog else None
+        self.rds = bool(rds)
+        self.fm = None
+        if self.analog or self.rds:
+            self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path, **({"rds": True} if self.rds else {}))
         self.audio = [[] for _ in range(self.k)]
         self.stereo = [False] * self.k
         self.pilot = [0.0] * self.k
@@ -118,6 +128,11 @@ class WidebandReceiver:
     def station_info(self) -> list:
         """per station, the SIS snapshot (None without sis=True)"""
         return [None if self.sis is None else self.sis.info(s) for s in range(self.k)]
+
+    @property
+    def rds_info(self) -> list:
+        """per station, the RDS snapshot (None without rds=True)"""
+        return [self.fm.rds_get(s) if self.rds else None for s in range(self.k)]
 
     def _feed_sis(self, fresh, events):
         """fresh[s], events[s]: as for _feed_metadata"""
@@ -197,7 +212,7 @@ class WidebandReceiver:
             self.max_retained = max(self.max_retained, self.held)
             self.trims += 1
         pcm = None
-        if self.analog:
+        if self.fm is not None:
             cap = max(self.fm.outputs_for(m), 1)
             pcm = torch.empty((self.k, cap, 2), dtype=torch.int16, device=chunk.device)
             got = self.chan.feed_fm(self.engine, self.ids, self.fm, chunk.data_ptr(), n, pcm.data_ptr(), 2 * cap, cap)
@@ -227,6 +242,11 @@ class WidebandReceiver:
             self._feed_sis(fresh, new)
         if self.analog:
             self._deliver_audio(pcm, new)
+        if self.rds:
+            for e in self.fm.rds_read():
+                v = {"kind": e["kind"], **eng.rds_event_fields(e["kind"], e["v"], e["data"])}
+                self.logs[e["channel"]].append(("rds", v))
+                new[e["channel"]].append((e["channel"], "rds", v))
         return [ev for per in new for ev in per]
 
     def _deliver_audio(self, pcm, events):
@@ -446,6 +466,17 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} ID3 program {v['program']}" + "".join(f" {k}={v[k]!r}" for k in ("title", "artist", "album", "genre") if k in v)
     if kind in _SIS_LINES:
         return f"{head} " + _SIS_LINES[kind](v)
+    if kind == "rds":
+        if v["kind"] == "pi":
+            return f"{head} RDS PI 0x{v['pi']:04X}" + (f" ({v['callsign']})" if v["callsign"] else "")
+        if v["kind"] == "ps":
+            return f"{head} RDS PS \"{v['raw'].decode('latin-1')}\""
+        if v["kind"] == "rt":
+            return f"{head} RDS RT \"{v['text']}\""
+        if v["kind"] == "clock":
+            off = v["offset_half_hours"]
+            return f"{head} RDS clock MJD {v['mjd']} {v['hour']:02d}:{v['minute']:02d} UTC{'-' if off < 0 else '+'}{abs(off) // 2:02d}:{abs(off) % 2 * 30:02d}"
+        return None
     if kind == "sig":                                               # main.c:416-438
         lines = []
         for sv in v:
@@ -603,6 +634,7 @@ def main(argv=None) -> int:
                     help="write every station's analog FM programme as WAV (44.1 kHz, 16 bit, stereo): DIR/station<k>_<offset in Hz>_analog.wav")
     ap.add_argument("--deemphasis", type=float, default=75.0, choices=[75.0, 50.0, 0.0], help="de-emphasis of the analog audio in us (0: none)")
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
+    ap.add_argument("--rds", action="store_true", help="print RDS / RBDS of every station's analog host: PI (and the call sign it encodes), name, RadioText, clock")
     ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                  # "--offsets -800e3,0,400e3": a value that starts with '-' is still the value
@@ -637,7 +669,7 @@ def main(argv=None) -> int:
                     return 1
         del head
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
-                          data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis)
+                          data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis, rds=a.rds)
     wav = None
     if a.dump_analog is not None:
         wav = AnalogDump(a.dump_analog, offsets)
