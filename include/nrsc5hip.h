@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 19   /* 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 20   /* 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -770,6 +770,36 @@ int nrsc5hip_stage_am_block(nrsc5hip_engine *e, const int16_t *win, const int16_
  * arrays are HOST arrays.  The streams are left freshly reset.  NRSC5HIP_EINVAL with nothing launched: a null pointer; n < 1 or n > max_streams; a stream in AM mode;
  * an engine without the table. */
 int nrsc5hip_stage_nco_exact(nrsc5hip_engine *e, int n, const float *start, const float *inc, const int *active, const int *nco_mode, float *tab, float *end);
+/* ---- the FM symbol transform on caller data (ABI 20; tests/sym_checks.py) ---------------------------------------------------------------------
+ * Runs the PRODUCTION launch (launch_mixfft: k_mixfft<SPW, NPAR> or k_mixfft8 -- timing pick, in-place cu8 half-band, Q15 -> float, oscillator mix, cyclic-prefix
+ * fold, FFT-2048, live-bin cut) once, for one block of 32 symbols, on streams 0 .. n-1 of the engine, freshly reset and in FM mode.  form: the mixfft_syms value
+ * handed to launch_mixfft -- 1, 2, 4, 8 (symbols per 128-lane workgroup), 16 (two symbols side by side in 256 lanes), 32 (the 256-lane kernel); the engine's own
+ * tune knob is neither read nor changed.  ids: null, or a permutation of 0 .. n-1 (the launch's stream list; in[] and out[] stay indexed by STREAM).
+ * Samples of stream s (in[s]): either raw != null -- a cu8 capture of raw_bytes bytes read in place: uploaded `lead` (0, 4, 8 or 12) bytes into a 16-byte aligned
+ * temporary buffer and attached as the zero-copy batch attaches one (StreamState::raw, base 0, wr = raw_bytes / 4) -- or q15 != null: q15_samples Q15 samples
+ * [.][2] written to the start of the stream's FIFO slab.  nco_tab: null, or float [32][2160][2] copied into the stream's row of the oscillator table.
+ * params_mode 0: a00 (first decimated sample of symbol 0), dtheta, theta, growth, active, nco_mode are written to the state words a symbol workgroup reads when
+ *   local_prepare = 0 (rd = a00, samperr_cur = 0, dtheta, theta, growth, active, nco_mode); one launch with local_prepare = 0; `prepare` is ignored.
+ * params_mode 1: the stream is FINE with samperr, cfo, angle, prev_angle, theta, rd, wr as given and has left exact-oscillator mode (nco_exact 0).
+ *   prepare 1: launch_mixfft(local_prepare = 1) alone, as the fused streaming seam launches it; only once the bins are back the hook runs launch_prepare, which
+ *   commits the same bookkeeping the way the block step behind the kernel would, so that *out can be read.  prepare 0: launch_prepare, then
+ *   launch_mixfft(local_prepare = 0).
+ * Before the launch the bins of ALL max_streams streams are filled with 0xA5 bytes.  -> bins float [max_streams][32][534][2], and per stream out[s]: what the
+ * kernel ran on, read back from the state.  The streams are left freshly reset, the record and counters the bookkeeping touched cleared, the bins zeroed.  No
+ * arithmetic lives in the hook.  NRSC5HIP_EINVAL with nothing launched: a null pointer; n < 1 or n > max_streams; a form outside the six; params_mode / prepare
+ * outside 0 .. 1; a stream in AM mode; ids that are no permutation; both or neither of raw / q15; lead outside the four; raw_bytes % 4 != 0 or beyond 2^30;
+ * q15_samples beyond q15_capacity; a00 < 0; the last symbol's last sample (a00 + 32 * 2160 - 1) beyond the capture or the window; nco_mode 1 without nco_tab, or
+ * an engine without the table; (mode 1) rd < 0, wr beyond the samples given, wr - rd < 71280 (no complete window), samperr outside -1080 .. 1080. */
+typedef struct nrsc5hip_sym_stream {
+    const uint8_t *raw; size_t raw_bytes; int32_t lead, pad0;
+    const int16_t *q15; long long q15_samples;
+    const float *nco_tab;
+    long long a00; double dtheta, theta, growth; int32_t active, nco_mode;     /* mode 0 (theta: both modes) */
+    int32_t samperr, cfo; float angle, prev_angle; long long rd, wr;            /* mode 1 */
+} nrsc5hip_sym_stream;
+typedef struct nrsc5hip_sym_params { long long a00; double dtheta, theta, growth; int32_t active, nco_mode; } nrsc5hip_sym_params;
+int nrsc5hip_stage_symbols(nrsc5hip_engine *e, int n, int form, int params_mode, int prepare, const nrsc5hip_sym_stream *in, const int *ids,
+                           float *bins, nrsc5hip_sym_params *out);
 /* one frame, also returning the len+64 survivor-decision words of the forward pass */
 int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out);
 /* micro-benchmark of the Viterbi kernel on random frames: phases bit0 = forward, bit1 = traceback */

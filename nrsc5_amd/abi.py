@@ -169,6 +169,33 @@ def bind_am_block(lib) -> None:
     lib.nrsc5hip_debug_fetch_am_sym.argtypes = [vp, ci, vp]
 
 
+class SymStream(ctypes.Structure):
+    """nrsc5hip_sym_stream: one stream's samples and block parameters for nrsc5hip_stage_symbols"""
+    _fields_ = [("raw", ctypes.c_void_p), ("raw_bytes", ctypes.c_size_t), ("lead", ctypes.c_int32), ("pad0", ctypes.c_int32),
+                ("q15", ctypes.c_void_p), ("q15_samples", ctypes.c_longlong), ("nco_tab", ctypes.c_void_p),
+                ("a00", ctypes.c_longlong), ("dtheta", ctypes.c_double), ("theta", ctypes.c_double), ("growth", ctypes.c_double),
+                ("active", ctypes.c_int32), ("nco_mode", ctypes.c_int32),
+                ("samperr", ctypes.c_int32), ("cfo", ctypes.c_int32), ("angle", ctypes.c_float), ("prev_angle", ctypes.c_float),
+                ("rd", ctypes.c_longlong), ("wr", ctypes.c_longlong)]
+
+
+class SymParams(ctypes.Structure):
+    """nrsc5hip_sym_params: what the symbol kernel ran on, read back from the stream state"""
+    _fields_ = [("a00", ctypes.c_longlong), ("dtheta", ctypes.c_double), ("theta", ctypes.c_double), ("growth", ctypes.c_double),
+                ("active", ctypes.c_int32), ("nco_mode", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(SymStream) == 120 and ctypes.sizeof(SymParams) == 40
+SYM_FORMS = (1, 2, 4, 8, 16, 32)         # the mixfft_syms values launch_mixfft knows: symbols per 128-lane workgroup, NPAR = 2, the 256-lane kernel
+SYM_NSYM, SYM_LIVE = 32, 534             # symbols per block, live bins per symbol (478 .. 744, 1304 .. 1570 after the shift)
+
+
+def bind_symbols(lib) -> None:
+    """argument types of the symbol-transform stage hook (include/nrsc5hip.h, ABI 20)"""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.nrsc5hip_stage_symbols.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp]
+
+
 class _RdsConfig(ctypes.Structure):
     """nrsc5hip_rds_config"""
     _fields_ = [("raw_groups", ctypes.c_int), ("correct_burst", ctypes.c_int)]

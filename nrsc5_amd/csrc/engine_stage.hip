@@ -686,6 +686,113 @@ extern "C" int nrsc5hip_stage_nco_exact(nrsc5hip_engine *e, int n, const float *
     return 0;
 }
 
+// ---- the FM symbol transform on caller data (include/nrsc5hip.h; tests/sym_checks.py) -----------------------------------------------------------------
+// launch_mixfft unchanged on streams 0 .. n-1, freshly reset, whose samples (an attached cu8 capture or a FIFO window) and block parameters the hook wrote; the bins of
+// every stream of the engine are filled with ACQ_FILL bytes first.  Nothing of the arithmetic lives here.
+static void sym_params_out(const StreamState &st, nrsc5hip_sym_params *o)
+{
+    o->a00 = (st.rd - st.base) + st.samperr_cur; o->dtheta = st.dtheta; o->theta = st.theta; o->growth = st.growth; o->active = st.active; o->nco_mode = st.nco_mode;
+}
+
+extern "C" int nrsc5hip_stage_symbols(nrsc5hip_engine *e, int n, int form, int params_mode, int prepare, const nrsc5hip_sym_stream *in, const int *ids,
+                                      float *bins, nrsc5hip_sym_params *out)
+{
+    ON_ENGINE_DEVICE(e);
+    if (!in || !bins || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (n < 1 || n > e->cfg.max_streams) FAIL(NRSC5HIP_EINVAL, "%d streams: 1 .. max_streams (%d)", n, e->cfg.max_streams);
+    if (form != 1 && form != 2 && form != 4 && form != 8 && form != 16 && form != 32) FAIL(NRSC5HIP_EINVAL, "form %d: 1, 2, 4, 8, 16 or 32", form);
+    if ((params_mode != 0 && params_mode != 1) || (prepare != 0 && prepare != 1)) FAIL(NRSC5HIP_EINVAL, "params_mode %d, prepare %d: 0 or 1", params_mode, prepare);
+    if (ids) {
+        std::vector<int> seen((size_t)n, 0);
+        for (int k = 0; k < n; k++) { if (ids[k] < 0 || ids[k] >= n || seen[ids[k]]++) FAIL(NRSC5HIP_EINVAL, "ids must be a permutation of 0 .. %d", n - 1); }
+    }
+    const long long block = (long long)NSYM * SYM_N;
+    size_t raw_total = 0;
+    std::vector<size_t> raw_off((size_t)n, 0);
+    for (int s = 0; s < n; s++) {
+        const nrsc5hip_sym_stream &c = in[s];
+        if (e->mode_host[s] != MODE_FM) FAIL(NRSC5HIP_EINVAL, "stream %d must be in FM mode", s);
+        if ((c.raw != nullptr) == (c.q15 != nullptr)) FAIL(NRSC5HIP_EINVAL, "stream %d: a cu8 capture or a Q15 window, one of the two", s);
+        long long have;
+        if (c.raw) {
+            if (c.lead != 0 && c.lead != 4 && c.lead != 8 && c.lead != 12) FAIL(NRSC5HIP_EINVAL, "stream %d: lead %d: 0, 4, 8 or 12 bytes", s, c.lead);
+            if (c.raw_bytes % 4 || c.raw_bytes > ((size_t)1 << 30)) FAIL(NRSC5HIP_EINVAL, "stream %d: bad capture length", s);
+            have = (long long)(c.raw_bytes / 4);
+            raw_off[s] = raw_total;
+            raw_total += (c.raw_bytes + 16 + 15) & ~(size_t)15;
+        } else {
+            if (c.q15_samples < 0 || c.q15_samples > e->db.q15_cap) FAIL(NRSC5HIP_EINVAL, "stream %d: %lld samples: 0 .. q15_capacity (%lld)", s, c.q15_samples, e->db.q15_cap);
+            have = c.q15_samples;
+        }
+        // decimated sample a reads the dwords a - 7 .. a of a capture (in front of it: history, never memory) and a workgroup nothing beyond its symbol's last sample
+        // (raw_symbol_load / _load8; the FIFO path reads win[0 .. 2159]): the last symbol's last sample bounds every read
+        long long a00;
+        if (params_mode == 0) {
+            a00 = c.a00;
+            if (c.nco_mode && !c.nco_tab) FAIL(NRSC5HIP_EINVAL, "stream %d: exact-oscillator mode without a table", s);
+        } else {
+            if (c.rd < 0 || c.wr > have || c.wr - c.rd < WIN_N) FAIL(NRSC5HIP_EINVAL, "stream %d: rd %lld, wr %lld: a complete window inside the %lld samples given", s, c.rd, c.wr, have);
+            if (c.samperr < -SYM_N / 2 || c.samperr > SYM_N / 2) FAIL(NRSC5HIP_EINVAL, "stream %d: samperr %d: %d .. %d", s, c.samperr, -SYM_N / 2, SYM_N / 2);
+            a00 = c.rd + SYM_N / 2 + c.samperr;                                   // acquire.c:112 (prepare_values)
+        }
+        if (a00 < 0 || a00 > have || block > have - a00) FAIL(NRSC5HIP_EINVAL, "stream %d: symbols at %lld reach beyond the %lld samples given", s, a00, have);
+        if (c.nco_tab && !e->db.nco_tab) FAIL(NRSC5HIP_EINVAL, "the engine has no oscillator table");
+    }
+    int rc;
+    for (int s = 0; s < n; s++) if ((rc = nrsc5hip_stream_fresh(e, s))) return rc;
+    DevTmp draw;
+    if (raw_total) HIPCHK(hipMalloc(&draw.p, raw_total));
+    const size_t row = (size_t)NSYM * SYM_N, S = (size_t)e->cfg.max_streams;
+    for (int s = 0; s < n; s++) {
+        const nrsc5hip_sym_stream &c = in[s];
+        StreamState st;
+        HIPCHK(hipMemcpy(&st, e->db.state + s, sizeof(st), hipMemcpyDeviceToHost));
+        if (c.raw) {
+            uint8_t *at = (uint8_t *)draw.p + raw_off[s] + c.lead;
+            HIPCHK(hipMemcpy(at, c.raw, c.raw_bytes, hipMemcpyHostToDevice));
+            st.raw = at; st.wr = (long long)(c.raw_bytes / 4); st.base = 0;         // k_attach_raw
+        } else {
+            if (c.q15_samples) HIPCHK(hipMemcpy(e->db.q15 + (size_t)s * e->db.q15_cap, c.q15, (size_t)c.q15_samples * sizeof(c16), hipMemcpyHostToDevice));
+            st.wr = c.q15_samples;
+        }
+        if (c.nco_tab) HIPCHK(hipMemcpy(e->db.nco_tab + (size_t)s * row, c.nco_tab, row * sizeof(float2), hipMemcpyHostToDevice));
+        st.theta = c.theta;
+        if (params_mode == 0) {
+            st.rd = c.a00; st.samperr_cur = 0; st.dtheta = c.dtheta; st.growth = c.growth; st.active = c.active ? 1 : 0; st.nco_mode = c.nco_mode ? 1 : 0;
+        } else {
+            st.sync_state = SYNC_FINE; st.samperr = c.samperr; st.cfo = c.cfo; st.angle = c.angle; st.prev_angle = c.prev_angle; st.rd = c.rd; st.wr = c.wr;
+            st.nco_exact = 0;                                                      // a FINE stream's blocks run on the closed form (what local_prepare assumes)
+        }
+        HIPCHK(hipMemcpy(e->db.state + s, &st, sizeof(st), hipMemcpyHostToDevice));
+    }
+    const int *ids_dev = nullptr;
+    if (ids) { HIPCHK(hipMemcpy(e->ids_dev, ids, (size_t)n * sizeof(int), hipMemcpyHostToDevice)); ids_dev = e->ids_dev; }
+    const size_t bins_bytes = S * NSYM * LIVE_N * sizeof(float2);
+    HIPCHK(hipMemset(e->db.bins, ACQ_FILL, bins_bytes));
+    HIPCHK(hipMemsetAsync(e->db.counters, 0, 4 * sizeof(int), e->main));
+    const int local = params_mode == 1 && prepare == 1;
+    if (params_mode == 1 && !local) launch_prepare(e->db, n, ids_dev, 0, e->main);
+    launch_mixfft(e->tb, e->db, n, ids_dev, e->main, form, local);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(e->main));
+    HIPCHK(hipMemcpy(bins, e->db.bins, bins_bytes, hipMemcpyDeviceToHost));
+    if (local) {                                                                   // the commit the block step behind the kernel makes (prepare_block): the same values, now readable
+        launch_prepare(e->db, n, ids_dev, 0, e->main);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(e->main));
+    }
+    for (int s = 0; s < n; s++) {
+        StreamState st;
+        HIPCHK(hipMemcpy(&st, e->db.state + s, sizeof(st), hipMemcpyDeviceToHost));
+        sym_params_out(st, out + s);
+    }
+    if (params_mode == 1) for (int s = 0; s < n; s++) HIPCHK(hipMemset(e->db.records + (size_t)s * e->db.rec_cap, 0, sizeof(BlockRecord)));   // record slot 0: as the engine's creation leaves it
+    HIPCHK(hipMemset(e->db.counters, 0, 4 * sizeof(int)));
+    HIPCHK(hipMemset(e->db.bins, 0, bins_bytes));
+    for (int s = 0; s < n; s++) if ((rc = nrsc5hip_stream_fresh(e, s))) return rc;  // (detaches the captures before draw is freed)
+    return 0;
+}
+
 extern "C" int nrsc5hip_stage_viterbi_k7_debug(nrsc5hip_engine *e, const int8_t *soft, int len, uint8_t *bits, unsigned long long *dec_out)
 {
     ON_ENGINE_DEVICE(e);

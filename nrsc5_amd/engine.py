@@ -100,6 +100,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_stage_am_acquire.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
     lib.nrsc5hip_stage_nco_exact.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     abi.bind_am_block(lib)
+    abi.bind_symbols(lib)
     lib.nrsc5hip_debug_poison_results.argtypes = [vp]
     lib.nrsc5hip_debug_seam_totals.argtypes = [vp, ci]
     lib.nrsc5hip_debug_seam_totals.restype = None
@@ -204,7 +205,7 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_batch_append_cu8", "nrsc5hip_batch_append_cs16", "nrsc5hip_batch_process", "nrsc5hip_batch_trim", "nrsc5hip_drain",
     "nrsc5hip_p1_frame_packed", "nrsc5hip_p1_frame_bits", "nrsc5hip_batch_fetch", "nrsc5hip_unpack_bits",
     "nrsc5hip_stage_halfband_fm_cu8", "nrsc5hip_stage_fft2048", "nrsc5hip_stage_viterbi_k7", "nrsc5hip_debug_fetch", "nrsc5hip_debug_fetch_costas",
-    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_stage_am_block", "nrsc5hip_debug_fetch_am_sym", "nrsc5hip_stage_nco_exact", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
+    "nrsc5hip_debug_fetch_q15", "nrsc5hip_debug_alloc_copy", "nrsc5hip_debug_free", "nrsc5hip_reset_all", "nrsc5hip_profile", "nrsc5hip_stage_selftest", "nrsc5hip_stage_viterbi_k7_debug", "nrsc5hip_stage_viterbi_bench", "nrsc5hip_debug_sync_phases", "nrsc5hip_debug_tune", "nrsc5hip_debug_fwd_stats", "nrsc5hip_debug_flow_stats", "nrsc5hip_debug_host_capture_stats", "nrsc5hip_abi_version", "nrsc5hip_debug_tb_stats", "nrsc5hip_debug_k9_stats", "nrsc5hip_stage_first_header", "nrsc5hip_stage_math", "nrsc5hip_stage_halfband_raw", "nrsc5hip_stage_p1_deint", "nrsc5hip_stage_p1_frame", "nrsc5hip_stage_pids", "nrsc5hip_stage_px_interleave", "nrsc5hip_stage_am_deinterleave", "nrsc5hip_stage_am_epilogue", "nrsc5hip_stage_acquire", "nrsc5hip_stage_acquire_raw", "nrsc5hip_stage_am_acquire", "nrsc5hip_stage_am_block", "nrsc5hip_debug_fetch_am_sym", "nrsc5hip_stage_nco_exact", "nrsc5hip_stage_symbols", "nrsc5hip_debug_seam_totals", "nrsc5hip_debug_seam_counts", "nrsc5hip_drain_ready", "nrsc5hip_stream_set_manual_step", "nrsc5hip_stream_step", "nrsc5hip_stream_step_ahead", "nrsc5hip_debug_poison_results", "nrsc5hip_device_count", "nrsc5hip_device_upload", "nrsc5hip_device_free", "nrsc5hip_batch_fetch_view", "nrsc5hip_batch_fetch_l2_px", "nrsc5hip_batch_fetch_l2_am",
     "nrsc5hip_stream_set_mode", "nrsc5hip_am_frame_bits", "nrsc5hip_stage_viterbi_k9", "nrsc5hip_px_frame_bits",
     "nrsc5hip_batch_fetch_px", "nrsc5hip_debug_fetch_px", "nrsc5hip_stage_viterbi_k9_bench",
     "nrsc5hip_l2_index", "nrsc5hip_stage_l2_index", "nrsc5hip_l2_frame_get", "nrsc5hip_batch_fetch_l2",
@@ -781,6 +782,44 @@ class Engine:
         tab, end = np.zeros((m, 32 * 2160, 2), dtype=np.float32), np.zeros((m, 2), dtype=np.float32)
         self._check(self.lib.nrsc5hip_stage_nco_exact(self._h, n, _ptr(start), _ptr(inc), _ptr(active), _ptr(nco_mode), tab.ctypes.data, end.ctypes.data))
         return tab, end
+
+    def stage_symbols(self, form: int, streams, params_mode: int = 0, prepare: int = 0, ids=None, n: int | None = None):
+        """nrsc5hip_stage_symbols: launch_mixfft in the form `form` (abi.SYM_FORMS), one block, on streams 0 .. n-1.  streams: per stream a dict with either
+        raw (uint8 cu8 capture, read in place; lead 0 / 4 / 8 / 12) or q15 (int16 [., 2] FIFO window), optionally nco_tab (float32 [32, 2160, 2]), and the words
+        of abi.SymStream for the mode: 0 -- a00, dtheta, theta, growth, active (default 1), nco_mode; 1 -- a FINE state samperr, cfo, angle, prev_angle, theta,
+        rd, wr, run with launch_mixfft(local_prepare = 1) alone (prepare = 1) or launch_prepare first (prepare = 0).  ids: the launch's stream list, a
+        permutation of 0 .. n-1, or None ->
+        (bins complex64 [max_streams, 32, 534], rows the kernel left alone still filled with 0xA5 bytes; per stream a dict of abi.SymParams read back)"""
+        n = len(streams) if n is None else n
+        m = max(n, 0)
+        arr, keep = (abi.SymStream * max(m, 1))(), []
+        for s, d in enumerate(list(streams or ())[:m]):
+            d = dict(d)
+            c = arr[s]
+            for key, dt in (("raw", np.uint8), ("q15", np.int16), ("nco_tab", np.float32)):
+                a = d.pop(key, None)
+                if a is None:
+                    continue
+                a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+                if key == "nco_tab" and a.size != 32 * 2160 * 2:
+                    raise ValueError("nco_tab holds %d floats, not 32 * 2160 * 2" % a.size)
+                keep.append(a)
+                setattr(c, key, a.ctypes.data)
+                if key == "raw":
+                    c.raw_bytes = d.pop("raw_bytes", a.size)
+                elif key == "q15":
+                    c.q15_samples = d.pop("q15_samples", a.size // 2)
+            c.active = 1
+            for key, v in d.items():
+                if key not in dict(abi.SymStream._fields_) or key in ("raw", "q15", "nco_tab", "pad0"):
+                    raise ValueError("not a word of nrsc5hip_sym_stream: %s" % key)
+                setattr(c, key, v)
+        idl = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+        bins = np.zeros((self.max_streams, abi.SYM_NSYM, abi.SYM_LIVE), dtype=np.complex64)
+        out = (abi.SymParams * max(m, 1))()
+        self._check(self.lib.nrsc5hip_stage_symbols(self._h, n, form, params_mode, prepare, ctypes.addressof(arr) if streams is not None else None, _ptr(idl),
+                                                    bins.ctypes.data, ctypes.addressof(out)))
+        return bins, [{k: getattr(out[s], k) for k, _ in abi.SymParams._fields_} for s in range(m)]
 
     def stage_selftest(self) -> int:
         n = ctypes.c_int(-1)
