@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 20   /* 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 21   /* 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -1013,6 +1013,25 @@ int  nrsc5hip_scan_detect_psd(const double *psd, int nfft /* a power of two >= 1
                               nrsc5hip_scan_station *stations_out, int max, int *n);
 /* nrsc5hip_scan_spectrum followed by nrsc5hip_scan_detect_psd */
 int  nrsc5hip_scan_detect(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_station *stations_out, int max, int *n);
+/* Detector of analog FM carriers (ABI 21; host, double, deterministic, no device) on the same spectrum:
+ *   floor      as above
+ *   score(c)   for every bin centre c with |c| <= Fs/2 - 198.5 kHz (the channelizer can tune it): 10 log10(the mean power of
+ *              [c - 50 kHz, c + 50 kHz], the PSD taken as constant across each bin, / floor)
+ *   picks      highest score first (ties: lower bin), none below threshold_db, none within +-min_separation_hz of an earlier pick.  params
+ *              NULL: 6 dB and 150 kHz, so that the shoulder of a strong carrier is not picked in front of a weak neighbour on the 200 kHz raster
+ *   centre     offset_hz = the power centroid of max(PSD - floor, 0) over the bins whose centres lie in [c - 100 kHz, c + 100 kHz], added in bin
+ *              order: sum f_i w_i / sum w_i (an FM signal's first spectral moment is its carrier); c itself when the weights sum to 0
+ * Generous on purpose: the sidebands of a hybrid station are nominated too; the carrier measurement ("carrier quality" below; nrsc5_amd/
+ * wideband.py: confirm_analog) removes them. */
+typedef struct nrsc5hip_scan_fm_station {
+    double offset_hz;                    /* the centroid, relative to the capture centre */
+    double bin_hz;                       /* the bin centre picked */
+    float score_db, floor_db;
+} nrsc5hip_scan_fm_station;
+int  nrsc5hip_scan_detect_fm_psd(const double *psd, int nfft /* a power of two >= 16 */, double fs, const nrsc5hip_scan_params *params,
+                                 nrsc5hip_scan_fm_station *stations_out, int max, int *n);
+/* nrsc5hip_scan_spectrum followed by nrsc5hip_scan_detect_fm_psd */
+int  nrsc5hip_scan_detect_fm(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_fm_station *stations_out, int max, int *n);
 
 /* ---- analog FM audio (ABI 16): the analog programme of every station's 744 187.5 S/s cs16 stream as 44.1 kS/s stereo PCM -----------
  * Input: per channel (1 <= nchan <= 512) the cs16 stream the channelizer makes, x[n] (n counted from the last create / reset, x[n] = 0 for
@@ -1060,7 +1079,8 @@ int  nrsc5hip_fm_process(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_st
 int  nrsc5hip_fm_clip_counts(nrsc5hip_fm *fm, long long *counts /* [nchan][2]: L, R, since create / reset */);
 /* test hook (ABI 19): kernel launches the pushes have issued since create / reset -- per push the front end (when a d sample is new), the pilot
  * sums (a block complete), the audio (an audio block due) and the kept tails (always); with RDS also the matched filter (a grid point new) and,
- * when a window was decided, decisions, groups and the kept y.  The stage hooks are not counted */
+ * when a window was decided, decisions, groups and the kept y; with the carrier measurement also, when a block completed, the block sums and the
+ * report (which keeps the tails; the front end writes r in its one launch).  The stage hooks are not counted */
 int  nrsc5hip_fm_debug_launches(nrsc5hip_fm *fm, long long *count);
 /* level a and stereo flag of the last audio block delivered (0 before the first); either pointer may be NULL */
 int  nrsc5hip_fm_pilot(nrsc5hip_fm *fm, float *level /* [nchan] */, int *stereo /* [nchan] */);
@@ -1144,6 +1164,49 @@ int  nrsc5hip_stage_rds_mf(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_
  * (or NULL): channel i's decoder is reset in front of that bit of the call (nbits[i]: behind the last; -1: never).  Events come with
  * nrsc5hip_fm_rds_read */
 int  nrsc5hip_stage_rds_groups(nrsc5hip_fm *fm, int n, const int *channels, const uint8_t *const *bits, const int *nbits, const int *reset_at);
+
+/* ---- carrier quality of the analog host (ABI 21): level, carrier-to-noise ratio and centre error of every channel's FM carrier ----------
+ * Opt-in per analog FM object (nrsc5hip_fm_carrier_enable); it then runs inside every nrsc5hip_fm_process / nrsc5hip_chan_feed_fm on the same
+ * stream.  Notation of "analog FM audio": z[m] the channel filter's output at Fs1, d[m] the discriminator, blocks of 540 Fs1 samples.  Every
+ * quantity is a function of absolute sample indices, there is no recurrence, and every sum has a stated order: any chunking of a session gives
+ * the same bits.  With the measurement disabled nothing changes: not a byte of d or of the audio, not the launch count.
+ *   envelope        r[m] = |z[m]|^2 = fma(Re z, Re z, Im z Im z) in float32, from the z the discriminator uses
+ *   block sums      for every complete block j, in double: s2[j] = sum r[m], s4[j] = sum r[m]^2 (the product is exact in double), s1[j] = sum d[m]
+ *                   over m in [540 j, 540 j + 540); lane l of 64 takes m = 540 j + l + 64 i, i ascending, then an xor butterfly (32, 16, .. 1)
+ *   windowed        of the last audio block delivered, ja: sum over |w| <= 16 of win[w] (s2, s4, s1)[ja + w], win the pilot's window as float32,
+ *                   each product in double, blocks in front of the stream zero; lane w + 16 holds term w, then the butterfly.  count = the sum
+ *                   of the 33 float32 window values in double (17 to rounding); it has the latency of the audio
+ *   running         every complete block since create / reset, added one after the other in block order, in double; count = the blocks
+ *   figures         on the host in double from a triple, the means per sample P = sum2 / (540 count), K = sum4 / (540 count):
+ *                     S = sqrt(max(0, 2 P^2 - K))   carrier power: the second / fourth moment estimator, exact in expectation for a carrier of
+ *                     N = P - S                     constant modulus in complex Gaussian noise (M2 = S + N, M4 = S^2 + 4 S N + 2 N^2)
+ *                     level_db  = 10 log10(S / 32768^2)
+ *                     cnr_db    = 10 log10(S / N), in the channel filter's noise bandwidth: white input noise of power v per sample leaves
+ *                                 v sum hA[i]^2 in z (-5.34 dB for the 112 taps), so the figure is 5.34 dB above a CNR taken over the whole
+ *                                 744 187.5 S/s
+ *                     offset_hz = 75 000 sum1 / (540 count): the MPX has no DC, so the mean discriminator output is the centre error
+ *                   S = 0 or P = 0: level_db = cnr_db = NRSC5HIP_FM_CARRIER_DB_MIN; N <= 0: cnr_db = NRSC5HIP_FM_CARRIER_DB_MAX; both figures
+ *                   are clamped to that range: never NaN, never infinite.  count = 0 (no block yet): every field 0
+ * Inherent: above about 40 dB the estimate saturates under modulation (its passage through the channel filter makes the envelope uneven; an
+ * unmodulated carrier does not saturate), and a signal without a carrier -- noise, OFDM sidebands -- reads below 0 dB or at the lower clamp,
+ * which is what makes the figure a detector of analog carriers. */
+#define NRSC5HIP_FM_CARRIER_DB_MIN (-150.0)
+#define NRSC5HIP_FM_CARRIER_DB_MAX 150.0
+typedef struct nrsc5hip_fm_carrier_report {
+    double sum2, sum4, sum1, count;      /* the triple and what it is divided by */
+    double level_db, cnr_db, offset_hz;
+} nrsc5hip_fm_carrier_report;
+typedef struct nrsc5hip_fm_carrier_info {
+    nrsc5hip_fm_carrier_report windowed, running;
+    long long blocks, audio_blocks;      /* complete blocks and audio blocks delivered since create / reset */
+} nrsc5hip_fm_carrier_info;
+/* Only before the first nrsc5hip_fm_process / nrsc5hip_chan_feed_fm of the object; nrsc5hip_fm_reset keeps it enabled and zeroes the totals */
+int  nrsc5hip_fm_carrier_enable(nrsc5hip_fm *fm);
+/* NRSC5HIP_EINVAL on an object without the measurement.  Only the two triples per channel cross to the host */
+int  nrsc5hip_fm_carrier(nrsc5hip_fm *fm, nrsc5hip_fm_carrier_info *out /* [nchan] */);
+/* stage hook: r (host, [nchan][(n_in + 1) / 2]) and the block triples (host, [nchan][((n_in + 1) / 2) / 540][3]: s2, s4, s1; may be NULL) of
+ * n_in samples taken as a whole session from n = 0; the object's own session is not touched, and the measurement need not be enabled */
+int  nrsc5hip_stage_fm_carrier(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *r_out, double *sums_out);
 
 #ifdef __cplusplus
 }

@@ -231,5 +231,37 @@ def bind_rds(lib) -> None:
     lib.nrsc5hip_stage_rds_groups.argtypes = [vp, ci, vp, vp, vp, vp]
 
 
+class ScanFmStation(ctypes.Structure):
+    """nrsc5hip_scan_fm_station"""
+    _fields_ = [("offset_hz", ctypes.c_double), ("bin_hz", ctypes.c_double), ("score_db", ctypes.c_float), ("floor_db", ctypes.c_float)]
+
+
+class FmCarrierReport(ctypes.Structure):
+    """nrsc5hip_fm_carrier_report"""
+    _fields_ = [(n, ctypes.c_double) for n in ("sum2", "sum4", "sum1", "count", "level_db", "cnr_db", "offset_hz")]
+
+
+class FmCarrierInfo(ctypes.Structure):
+    """nrsc5hip_fm_carrier_info"""
+    _fields_ = [("windowed", FmCarrierReport), ("running", FmCarrierReport), ("blocks", ctypes.c_longlong), ("audio_blocks", ctypes.c_longlong)]
+
+
+assert ctypes.sizeof(FmCarrierInfo) == 128
+FM_CARRIER_DB_MIN, FM_CARRIER_DB_MAX = -150.0, 150.0     # NRSC5HIP_FM_CARRIER_DB_MIN / _MAX
+
+
+def bind_carrier(lib) -> None:
+    """argument types of the carrier measurement and of the analog-carrier detector (include/nrsc5hip.h, ABI 21)"""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    lib.nrsc5hip_abi_version.restype = ci
+    if lib.nrsc5hip_abi_version() < 21:                    # an older library loaded for an A/B comparison: it has everything but these
+        return
+    lib.nrsc5hip_fm_carrier_enable.argtypes = [vp]
+    lib.nrsc5hip_fm_carrier.argtypes = [vp, vp]
+    lib.nrsc5hip_stage_fm_carrier.argtypes = [vp, vp, ll, ll, vp, vp]
+    lib.nrsc5hip_scan_detect_fm_psd.argtypes = [vp, ci, ctypes.c_double, ctypes.POINTER(ScanParams), vp, ci, ctypes.POINTER(ci)]
+    lib.nrsc5hip_scan_detect_fm.argtypes = [vp, ctypes.POINTER(ScanParams), vp, ci, ctypes.POINTER(ci)]
+
+
 class Nrsc5HipError(RuntimeError):
     pass

@@ -6,6 +6,7 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "rds.h"
+#include "fm_carrier.h"
 
 namespace nrsc5 {
 namespace fm {
@@ -26,6 +27,7 @@ struct FrontArgs {
     const float *ha;                          // [TA]
     float *d; long long d_stride, d_base;     // d[m] of channel c at d[c * d_stride + m - d_base]
     long long m0, m_count;                    // the new outputs [m0, m0 + m_count)
+    float *r = nullptr; long long r_stride = 0, r_base = 0;   // carrier measurement: r[m] of channel c at r[c * r_stride + m - r_base]; nullptr: not written
 };
 
 struct PilotArgs {
@@ -56,7 +58,7 @@ struct KeepArgs {
     const int *hist_old; int *hist_new;
 };
 
-// Where the launch_* functions of k_fm_audio.hip and k_rds.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
+// Where the launch_* functions of k_fm_audio.hip, k_fm_carrier.hip and k_rds.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
 // for the length of a push (nrsc5hip_fm_debug_launches); nullptr anywhere else (the stage hooks are not counted)
 extern thread_local long long *launch_count;
 inline void count_launch() { if (launch_count) ++*launch_count; }
@@ -90,6 +92,7 @@ struct nrsc5hip_fm {
     long long launches = 0;                                  // kernel launches of the pushes since create / reset
     bool processed = false;                                  // a push has been launched since create
     nrsc5::RdsHost *rds = nullptr;                           // RDS (rds.hip), once enabled
+    nrsc5::CarrierHost *carrier = nullptr;                   // carrier quality (fm_carrier.hip), once enabled
 };
 
 namespace nrsc5 {

@@ -53,6 +53,7 @@ void free_fm(nrsc5hip_fm *f)
     for (int i = 0; i < 2; i++) { (void)hipFree(f->d_hist[i]); (void)hipFree(f->d_d[i]); (void)hipFree(f->d_p[i]); }
     (void)hipFree(f->d_clips);
     nrsc5::rds_free(f->rds);
+    nrsc5::carrier_free(f->carrier);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -65,6 +66,7 @@ int fm_zero_state(nrsc5hip_fm *f)
     HIPCHK(hipMemsetAsync(f->d_pilot, 0, sizeof(float) * 2 * f->nchan, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
     f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0; f->launches = 0;
+    if (f->carrier) { const int rc = nrsc5::carrier_reset(f); if (rc) return rc; }
     return f->rds ? nrsc5::rds_reset(f) : 0;
 }
 
@@ -139,7 +141,7 @@ int nrsc5::fm_check(nrsc5hip_fm *f, long long n_in, const int16_t *dev_out, long
     return 0;
 }
 
-// front, pilot sums, audio and the kept tails on `stream`; no host wait (but for a buffer that has to grow)
+// front, pilot sums, audio, the carrier sums (when enabled) and the kept tails on `stream`; no host wait (but for a buffer that has to grow)
 int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long long in_stride, long long n_in, int16_t *out, long long out_stride)
 {
     if (n_in <= 0) return 0;
@@ -148,11 +150,13 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     const Counts c = counts_after(f, n_in);
     int rc = fm_reserve(f, s, c.m1, c.b1);
     if (rc) return rc;
+    if (f->carrier && (rc = nrsc5::carrier_reserve(f, s, c.m1, c.b1))) return rc;
     float *d = f->d_d[f->cur]; float2 *p = f->d_p[f->cur];
     if (c.m1 > f->m_total) {
         FrontArgs a;
         a.in = dev_in; a.in_stride = in_stride; a.n0 = f->n_total; a.n_in = n_in; a.hist = f->d_hist[f->cur]; a.ha = f->d_ha;
         a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.m0 = f->m_total; a.m_count = c.m1 - f->m_total;
+        if (f->carrier) { const nrsc5::FrontTarget t = nrsc5::carrier_front(f); a.r = t.r; a.r_stride = t.r_stride; a.r_base = t.r_base; }
         launch_front(s, (int)((a.m_count + FT - 1) / FT), f->nchan, a);
         HIPCHK(hipGetLastError());
     }
@@ -171,6 +175,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
         launch_audio(s, (int)(c.a1 - f->audio_blocks), f->nchan, a);
         HIPCHK(hipGetLastError());
     }
+    if (f->carrier && c.b1 > f->blocks && (rc = nrsc5::carrier_launch(f, s, d, c.m1, c.b1, c.a1))) return rc;
     // what the next call needs: d from the first tap of audio block a1, the block sums from a1 - W, the last HIST input samples
     long long d_base = (long long)BLOCK * c.a1 - f->tb - 1, p_base = c.a1 - W;
     if (d_base < 0) d_base = 0;

@@ -3,7 +3,8 @@
 // Every quantity is a function of absolute sample indices (x[n] = 0 for n < 0), no recurrence anywhere: any chunking gives the same bytes.
 //   k_fm_front  one workgroup = FT consecutive Fs1 outputs of one channel.  The cs16 span (new input and kept history) is staged in LDS as
 //               float2 from 4-byte loads, every work-item sums one z[m] = sum_i hA[i] x[2 m - i] (the tile one more than it emits), and the
-//               discriminator d[m] = atan2(z[m] conj z[m - 1]) goes to the channel's d buffer as float32.
+//               discriminator d[m] = atan2(z[m] conj z[m - 1]) goes to the channel's d buffer as float32; with the carrier measurement enabled
+//               also r[m] = |z[m]|^2 (k_fm_carrier.hip).
 //   k_fm_pilot  one wave = one complete pilot block: p[j] = sum d[m] exp(-j phi19(m)) in a fixed order (9 terms per lane, then a butterfly),
 //               so the sum does not depend on which push completed the block.  No atomics.
 //   k_fm_audio  one workgroup = one pilot block = 64 audio outputs.  Every wave forms the smoothed pilot (33 block sums, a butterfly), the d span
@@ -31,7 +32,9 @@ __device__ __forceinline__ int load_x(const FrontArgs &a, const int *in32, const
     return h >= 0 ? hist[h] : 0;                              // (n >= 0 never reaches back further; n < 0 reads the zeros the history starts with)
 }
 
-__global__ __launch_bounds__(256) void k_fm_front(FrontArgs a)
+// WITH_R: also r[m] = |z[m]|^2 for the carrier measurement (k_fm_carrier.hip).  A template, not a test of the pointer: the instantiation without
+// it is the kernel as it was, instruction for instruction
+template <bool WITH_R> __global__ __launch_bounds__(256) void k_fm_front(FrontArgs a)
 {
     HIP_DYNAMIC_SHARED(float2, sm);
     float2 *xs = sm, *zs = sm + (2 * FT + TA);
@@ -69,6 +72,7 @@ __global__ __launch_bounds__(256) void k_fm_front(FrontArgs a)
         float d = 0.0f;
         if (m > 0 && !(re == 0.0f && im == 0.0f)) d = ref_atan2f(im, re) * DEV_SCALE;
         a.d[(long long)ch * a.d_stride + (m - a.d_base)] = d;
+        if (WITH_R) a.r[(long long)ch * a.r_stride + (m - a.r_base)] = fmaf(z.x, z.x, z.y * z.y);
     }
 }
 
@@ -198,7 +202,9 @@ __global__ __launch_bounds__(256) void k_fm_keep(KeepArgs a)
 void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a)
 {
     count_launch();
-    hipLaunchKernelGGL(k_fm_front, dim3(tiles, nchan), dim3(256), sizeof(float2) * (2 * FT + TA + FT + 1), s, a);
+    const size_t lds = sizeof(float2) * (2 * FT + TA + FT + 1);
+    if (a.r) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fm_front<true>), dim3(tiles, nchan), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fm_front<false>), dim3(tiles, nchan), dim3(256), lds, s, a);
 }
 
 void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a)

@@ -294,6 +294,61 @@ int detect_psd(const double *psd, int nfft, double fs, const nrsc5hip_scan_param
     *n_out = (int)picked.size();
     return 0;
 }
+
+// The detector of analog FM carriers (include/nrsc5hip.h): the same floor and Staircase, the score is the mean power of c +- FM_SCORE_HZ over the
+// floor, and the reported centre is the centroid of the power above the floor over the bins whose centres lie within FM_CENTROID_HZ of the pick.
+// Generous on purpose: a hybrid station's sidebands are nominated as well; measuring the nomination's carrier is what removes them.
+constexpr double FM_SCORE_HZ = 50e3, FM_CENTROID_HZ = 100e3, FM_MIN_SEP_HZ = 150e3;
+
+int detect_fm_psd(const double *psd, int nfft, double fs, const nrsc5hip_scan_params *params, nrsc5hip_scan_fm_station *out, int max, int *n_out)
+{
+    if (!psd || !n_out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (nfft < 16 || (nfft & (nfft - 1))) FAIL(NRSC5HIP_EINVAL, "nfft %d is not a power of two >= 16", nfft);
+    if (!(fs > 0) || !std::isfinite(fs)) FAIL(NRSC5HIP_EINVAL, "bad sample rate");
+    if (max < 0 || (max > 0 && !out)) FAIL(NRSC5HIP_EINVAL, "bad output array (max %d)", max);
+    const double threshold = params ? params->threshold_db : 6.0, min_sep = params ? params->min_separation_hz : FM_MIN_SEP_HZ;
+    if (!std::isfinite(threshold) || !(min_sep >= 0)) FAIL(NRSC5HIP_EINVAL, "bad detector parameters");
+    *n_out = 0;
+    std::vector<double> sorted(psd, psd + nfft);
+    std::sort(sorted.begin(), sorted.end());
+    const double floor_p = sorted[(size_t)(FLOOR_QUANTILE * (nfft - 1))];
+    if (!(floor_p > 0) || !std::isfinite(floor_p)) return 0;
+    const Staircase st(psd, nfft, fs);
+    const double bw = fs / nfft;
+    struct Cand { double score; int bin; };
+    std::vector<Cand> cands;
+    for (int i = 0; i < nfft; i++) {
+        const double c = (i - nfft / 2) * bw;
+        if (!(fabs(c) <= fs / 2 - EDGE_HZ)) continue;
+        const double score = 10.0 * log10(st.mean(c - FM_SCORE_HZ, c + FM_SCORE_HZ) / floor_p);
+        if (std::isfinite(score) && score >= threshold) cands.push_back({score, i});
+    }
+    std::sort(cands.begin(), cands.end(), [](const Cand &a, const Cand &b) { return a.score != b.score ? a.score > b.score : a.bin < b.bin; });
+    std::vector<double> picked;
+    for (const Cand &cd : cands) {
+        const double c = (cd.bin - nfft / 2) * bw;
+        bool near = false;
+        for (double p : picked) if (fabs(p - c) <= min_sep) { near = true; break; }
+        if (near) continue;
+        if ((int)picked.size() < max) {
+            double sw = 0.0, sfw = 0.0;
+            for (int i = 0; i < nfft; i++) {
+                const double fi = (i - nfft / 2) * bw;
+                if (!(fabs(fi - c) <= FM_CENTROID_HZ)) continue;
+                const double w = psd[i] > floor_p ? psd[i] - floor_p : 0.0;
+                sw += w; sfw += fi * w;
+            }
+            nrsc5hip_scan_fm_station &o = out[picked.size()];
+            o.offset_hz = sw > 0 ? sfw / sw : c;
+            o.bin_hz = c;
+            o.score_db = (float)cd.score;
+            o.floor_db = (float)(10.0 * log10(floor_p));
+        }
+        picked.push_back(c);
+    }
+    *n_out = (int)picked.size();
+    return 0;
+}
 }  // namespace
 
 extern "C" int nrsc5hip_scan_create(const nrsc5hip_scan_config *cfg, nrsc5hip_scan **out)
@@ -440,6 +495,22 @@ extern "C" int nrsc5hip_scan_detect_psd(const double *psd, int nfft, double fs, 
                                         nrsc5hip_scan_station *stations_out, int max, int *n)
 {
     return detect_psd(psd, nfft, fs, params, stations_out, max, n);
+}
+
+extern "C" int nrsc5hip_scan_detect_fm_psd(const double *psd, int nfft, double fs, const nrsc5hip_scan_params *params,
+                                           nrsc5hip_scan_fm_station *stations_out, int max, int *n)
+{
+    return detect_fm_psd(psd, nfft, fs, params, stations_out, max, n);
+}
+
+extern "C" int nrsc5hip_scan_detect_fm(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_fm_station *stations_out, int max, int *n)
+{
+    if (!s || !n) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (max < 0 || (max > 0 && !stations_out)) FAIL(NRSC5HIP_EINVAL, "bad output array (max %d)", max);
+    std::vector<double> psd(s->nfft);
+    int rc = nrsc5hip_scan_spectrum(s, psd.data());
+    if (rc) return rc;
+    return detect_fm_psd(psd.data(), s->nfft, s->fs, params, stations_out, max, n);
 }
 
 extern "C" int nrsc5hip_scan_detect(nrsc5hip_scan *s, const nrsc5hip_scan_params *params, nrsc5hip_scan_station *stations_out, int max, int *n)

@@ -187,6 +187,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_fm_pilot.argtypes = [vp, vp, vp]
     lib.nrsc5hip_stage_fm_mpx.argtypes = [vp, vp, ll, ll, vp, vp]
     abi.bind_rds(lib)
+    abi.bind_carrier(lib)
     lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_scan_destroy.argtypes = [vp]
     lib.nrsc5hip_scan_destroy.restype = None
@@ -224,7 +225,8 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_fm_create", "nrsc5hip_fm_destroy", "nrsc5hip_fm_reset", "nrsc5hip_fm_info", "nrsc5hip_fm_taps", "nrsc5hip_fm_outputs_for",
     "nrsc5hip_fm_process", "nrsc5hip_fm_clip_counts", "nrsc5hip_fm_pilot", "nrsc5hip_stage_fm_mpx", "nrsc5hip_chan_feed_fm",
     "nrsc5hip_fm_debug_launches", "nrsc5hip_fm_rds_enable", "nrsc5hip_fm_rds_read", "nrsc5hip_fm_rds_get", "nrsc5hip_fm_rds_stats", "nrsc5hip_fm_rds_info", "nrsc5hip_fm_rds_taps",
-    "nrsc5hip_stage_rds_mf", "nrsc5hip_stage_rds_groups"]
+    "nrsc5hip_stage_rds_mf", "nrsc5hip_stage_rds_groups",
+    "nrsc5hip_fm_carrier_enable", "nrsc5hip_fm_carrier", "nrsc5hip_stage_fm_carrier", "nrsc5hip_scan_detect_fm_psd", "nrsc5hip_scan_detect_fm"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -948,7 +950,7 @@ class FmDemod:
     AUDIO_RATE = FM_AUDIO_RATE
 
     def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None,
-                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2):
+                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2, carrier: bool = False):
         self.lib = load_library(lib_path)
         self.nchan, self.device, self.deemphasis_us = int(nchan), device, float(deemphasis_us)
         self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), (self.nchan,)))
@@ -959,9 +961,13 @@ class FmDemod:
         self._check(self.lib.nrsc5hip_fm_info(self._h, ctypes.byref(ta), ctypes.byref(tb), ctypes.byref(ph), ctypes.byref(lat)))
         self.taps_channel, self.taps_audio, self.phases, self.latency_in = ta.value, tb.value, ph.value, lat.value
         self.rds = False
-        if rds:
+        self.carrier_enabled = False
+        if rds or carrier:
             try:
-                self.rds_enable(rds_raw_groups, rds_correct_burst)
+                if rds:
+                    self.rds_enable(rds_raw_groups, rds_correct_burst)
+                if carrier:
+                    self.carrier_enable()
             except Nrsc5HipError:
                 self.close()                                       # the demodulator that was created goes with the failed constructor
                 raise
@@ -1028,6 +1034,29 @@ class FmDemod:
         ch = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
         rst = None if reset_at is None else np.ascontiguousarray(reset_at, dtype=np.int32)
         self._check(self.lib.nrsc5hip_stage_rds_groups(self._h, n, _ptr(ch), ptrs, counts.ctypes.data, _ptr(rst)))
+
+    # ---- carrier quality of the analog host (nrsc5hip_fm_carrier*) -----------------------------------------------------------------
+    def carrier_enable(self):
+        """only before the first push; from then on every process() also measures every channel's carrier on the same stream"""
+        self._check(self.lib.nrsc5hip_fm_carrier_enable(self._h))
+        self.carrier_enabled = True
+
+    def carrier(self) -> list:
+        """one dict per channel: {"windowed": {...}, "running": {...}, "blocks", "audio_blocks"}; a report holds "level_db", "cnr_db", "offset_hz"
+        and the sums behind them, "sum2", "sum4", "sum1", "count" (windowed: of the last audio block delivered; running: since create / reset)"""
+        out = (FmCarrierInfo * self.nchan)()
+        self._check(self.lib.nrsc5hip_fm_carrier(self._h, ctypes.addressof(out)))
+        names = [n for n, _ in FmCarrierReport._fields_]
+        return [{"windowed": {n: float(getattr(o.windowed, n)) for n in names}, "running": {n: float(getattr(o.running, n)) for n in names},
+                 "blocks": int(o.blocks), "audio_blocks": int(o.audio_blocks)} for o in out]
+
+    def stage_carrier(self, dev_in: int, in_stride_elems: int, n_in: int):
+        """nrsc5hip_stage_fm_carrier -> (r float32 [nchan][(n_in + 1) // 2], block triples float64 [nchan][blocks][3]: s2, s4, s1)"""
+        m1 = (n_in + 1) // 2
+        r = np.zeros((self.nchan, m1), dtype=np.float32)
+        t = np.zeros((self.nchan, m1 // 540, 3), dtype=np.float64)
+        self._check(self.lib.nrsc5hip_stage_fm_carrier(self._h, dev_in, in_stride_elems, n_in, r.ctypes.data, t.ctypes.data))
+        return r, t
 
     def close(self):
         if self._h:
@@ -1124,6 +1153,27 @@ def detect_psd(psd, fs: float, threshold_db: float = 6.0, min_separation_hz: flo
     return _stations(out, min(n.value, max_stations))
 
 
+def _fm_stations(out, n: int) -> list:
+    return [{"offset_hz": float(s.offset_hz), "bin_hz": float(s.bin_hz), "score_db": float(s.score_db), "floor_db": float(s.floor_db)} for s in out[:n]]
+
+
+def detect_fm_psd(psd, fs: float, threshold_db: float = 6.0, min_separation_hz: float = 150e3, max_stations: int = 512,
+                  lib: ctypes.CDLL | None = None, lib_path: str | None = None) -> list:
+    """nrsc5hip_scan_detect_fm_psd: the library's host detector of analog FM carriers on any spectrum; no device, no scan object.
+    -> [{"offset_hz" (the centroid), "bin_hz" (the bin picked), "score_db", "floor_db"}, ...], highest score first"""
+    lib = lib or load_library(lib_path)
+    psd = np.ascontiguousarray(psd, dtype=np.float64)
+    out = (ScanFmStation * max(max_stations, 1))()
+    n = ctypes.c_int()
+    rc = lib.nrsc5hip_scan_detect_fm_psd(psd.ctypes.data, psd.size, float(fs), ctypes.byref(ScanParams(threshold_db, min_separation_hz)),
+                                         ctypes.addressof(out), max_stations, ctypes.byref(n))
+    if rc != 0:
+        err = Nrsc5HipError(f"libnrsc5hip error {rc}: {lib.nrsc5hip_last_error().decode()}")
+        err.code = rc
+        raise err
+    return _fm_stations(out, min(n.value, max_stations))
+
+
 class Scanner:
     """Band scan (nrsc5hip_scan_*): the averaged power spectrum of one capture at rate = rate_num / rate_den S/s in `fmt` (IQ_CU8 /
     IQ_CS16 / IQ_CF32) and the hybrid-FM stations in it.  nfft: a power of two in 512..8192, or 0 for the rate's default.  Input
@@ -1193,6 +1243,14 @@ class Scanner:
         self._check(self.lib.nrsc5hip_scan_detect(self._h, ctypes.byref(ScanParams(threshold_db, min_separation_hz)), ctypes.addressof(out),
                                                   max_stations, ctypes.byref(n)))
         return _stations(out, min(n.value, max_stations))
+
+    def detect_fm(self, threshold_db: float = 6.0, min_separation_hz: float = 150e3, max_stations: int = 512) -> list:
+        """the analog FM carriers of the spectrum (nrsc5hip_scan_detect_fm) -> [{"offset_hz", "bin_hz", "score_db", "floor_db"}, ...]"""
+        out = (ScanFmStation * max(max_stations, 1))()
+        n = ctypes.c_int()
+        self._check(self.lib.nrsc5hip_scan_detect_fm(self._h, ctypes.byref(ScanParams(threshold_db, min_separation_hz)), ctypes.addressof(out),
+                                                     max_stations, ctypes.byref(n)))
+        return _fm_stations(out, min(n.value, max_stations))
 
 
 def l2_jobs_from_records(stream: int, recs: np.ndarray, mode: int = 0):

@@ -1,6 +1,6 @@
 """Wideband multi-station capture generator -- TEST / BENCH SIGNAL SOURCE ONLY, like synth_torch.py.
 
-K hybrid-FM MP1 stations, each: clean baseband from synth_torch.modulate at 1 488 375 S/s with its own payload seed, an optional
+K hybrid-FM MP1 stations (or, with digital=False, analog-only FM stations: the host alone), each: clean baseband from synth_torch.modulate at 1 488 375 S/s with its own payload seed, an optional
 channel (channel.Impairments, e.g. an analog host), a carrier offset, a timing offset, the receiver-side conjugation synth / synth_torch
 apply, an optional analog FM stereo host (synth_fm), an FFT (zero-padding) resampler to Fs_in, a shift to +f_k and a level; the stations are summed, white noise is added and the
 result is quantised to cu8, cs16 or cf32.  float64 (complex128) throughout, fixed seeds."""
@@ -29,6 +29,7 @@ class Station:
     pids: object = None                  # the PIDS frames to transmit, cycled ([n, 80] bits, synth.sis_frame), None: reserved-id frames only
     host: dict | None = None             # analog FM host in the middle of the station: synth_fm.fm_carrier's programme (left, right, pilot, preemph_us, ...)
     host_db: float = 20.0                # ... its carrier power over the total digital power, dB
+    digital: bool = True                 # False: an analog-only station, the host alone at `level` (host_db has nothing to refer to)
 
 
 @dataclass
@@ -84,17 +85,24 @@ def capture(stations, rate, fmt: str = "cs16", n_frames: int = 3, noise_rms: flo
     cap = WidebandCapture(None, rate, fmt, list(stations))
     fs_in = float(rate)
     for st in stations:
-        p1, pids, m = synth_torch.payload_stream(n_frames, seed=st.seed, psd_stream=st.psd, pids=st.pids)
-        sig = synth_torch.modulate(m, dev)
-        if st.chan is not None:
-            from . import channel
-            sig = channel.apply_torch(sig, synth.FS_CU8, st.chan)
-        sig = sig.to(torch.complex128)
-        n0 = sig.shape[0]
-        t = torch.arange(n0, device=dev, dtype=torch.float64)
-        sig = sig * torch.exp(1j * (2 * np.pi * st.cfo_hz / synth.FS_CU8) * t)
-        sig = sig.conj()
-        if st.host is not None:                              # as transmitted (the conjugation above is the digital receiver's), with the station's carrier offset
+        if not st.digital:                                   # the host alone, as long as a digital station's transmission; no frames
+            from . import synth_fm
+            n0 = n_frames * 512 * 4320                       # 512 symbols of 4320 samples at 1 488 375 S/s per L1 frame
+            car = synth_fm.fm_carrier(n0, fs=synth.FS_CU8, **(st.host or {})) * np.exp(-2j * np.pi * st.cfo_hz / synth.FS_CU8 * np.arange(n0))
+            sig = torch.from_numpy(car).to(dev)
+            p1, pids = np.zeros((0, 146176), dtype=np.uint8), np.zeros((0, 80), dtype=np.uint8)
+        else:
+            p1, pids, m = synth_torch.payload_stream(n_frames, seed=st.seed, psd_stream=st.psd, pids=st.pids)
+            sig = synth_torch.modulate(m, dev)
+            if st.chan is not None:
+                from . import channel
+                sig = channel.apply_torch(sig, synth.FS_CU8, st.chan)
+            sig = sig.to(torch.complex128)
+            n0 = sig.shape[0]
+            t = torch.arange(n0, device=dev, dtype=torch.float64)
+            sig = sig * torch.exp(1j * (2 * np.pi * st.cfo_hz / synth.FS_CU8) * t)
+            sig = sig.conj()
+        if st.digital and st.host is not None:                              # as transmitted (the conjugation above is the digital receiver's), with the station's carrier offset
             from . import synth_fm
             amp = float(torch.sqrt(torch.mean(torch.abs(sig) ** 2))) * 10 ** (st.host_db / 20)
             car = synth_fm.fm_carrier(n0, fs=synth.FS_CU8, **st.host) * np.exp(-2j * np.pi * st.cfo_hz / synth.FS_CU8 * np.arange(n0))

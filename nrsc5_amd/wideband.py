@@ -15,6 +15,9 @@ DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets
 (44.1 kHz, 16 bit, stereo; --deemphasis 75, 50 or 0 us) and prints one `analog frames N` line per file at the end.
 --rds decodes RDS / RBDS of every station's analog host on the device and prints one line per report: `station 1 (+0.0 kHz): RDS PI 0x3AAB (KQED)`,
 `... RDS PS "KEXP-FM "`, `... RDS RT "..."`, `... RDS clock MJD 60310 13:37 UTC-07:00`.
+--carrier measures every station's analog carrier on the device and prints `station 1 (+0.0 kHz): carrier -21.3 dBFS CNR 31.2 dB offset +0.41 kHz`
+whenever the CNR has moved by 1 dB; --scan-analog makes the scan find analog-only FM stations as well (the spectrum nominates carriers, a measurement
+of each one's CNR and centre error confirms them) and receives both kinds: `found +400.3 kHz analog score 18.8 dB carrier -54.7 dBFS CNR 15.3 dB ...`.
 --dump-aas-files DIR writes every station's complete LOT files (album art, station logos, text files) as `nrsc5 --dump-aas-files` names them,
 DIR/station<k>_<offset in Hz>_<lot>_<name>, and prints the reference's `SIG Service:` / `Audio component:` / `Data component:` / `LOT file:` lines; the
 Station Information Guide and the files are put together on the device (nrsc5hip_aas_feed), only complete files reach the host.  FILE may be `-` (standard input, read in
@@ -76,11 +79,16 @@ class WidebandReceiver:
     analog did not, and audio is not collected then).  Every report of the decoder becomes an ("rds", {"kind": "pi" / "ps" / "rt" / "clock", ...})
     event (fields as eng.rds_event_fields) behind that station's other events of the push, and rds_info[s] is the station's snapshot
     (FmDemod.rds_get: pi, pty, flags, ps, rt, clock, synced).  A timing window of 152 bits is decided 96 431 input samples after its first
-    sample is complete; there is no flush."""
+    sample is complete; there is no flush.
+    carrier=True: the receiver also measures every station's analog carrier on the device (FmDemod(carrier=True); it creates the FmDemod if
+    neither analog nor rds did).  carrier[s] is the station's snapshot after every push (FmDemod.carrier: the windowed and the running level_db,
+    cnr_db, offset_hz and the sums behind them), and a ("carrier", {"level_db", "cnr_db", "offset_hz"}) event is returned by the push whenever the
+    windowed cnr_db has moved by 1 dB or more; the logs are those of a receiver without the measurement."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
                  programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
-                 lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None, rds: bool = False):
+                 lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None, rds: bool = False,
+                 carrier: bool = False):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -117,9 +125,13 @@ class WidebandReceiver:
         self.analog = bool(analog)
         self.on_audio = on_audio
         self.rds = bool(rds)
+        self.carrier_enabled = bool(carrier)
         self.fm = None
-        if self.analog or self.rds:
-            self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path, **({"rds": True} if self.rds else {}))
+        if self.analog or self.rds or self.carrier_enabled:
+            self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path, **({"rds": True} if self.rds else {}),
+                                  **({"carrier": True} if self.carrier_enabled else {}))
+        self.carrier = [None] * self.k
+        self._carrier_said = [None] * self.k
         self.audio = [[] for _ in range(self.k)]
         self.stereo = [False] * self.k
         self.pilot = [0.0] * self.k
@@ -247,7 +259,19 @@ class WidebandReceiver:
                 v = {"kind": e["kind"], **eng.rds_event_fields(e["kind"], e["v"], e["data"])}
                 self.logs[e["channel"]].append(("rds", v))
                 new[e["channel"]].append((e["channel"], "rds", v))
+        if self.carrier_enabled:
+            self._measure_carrier(new)
         return [ev for per in new for ev in per]
+
+    def _measure_carrier(self, events):
+        """carrier[s]: the snapshot after this push; a ("carrier", {...}) event whenever the windowed cnr_db has moved by 1 dB or more since the
+        last one (an event of the push only: the station's log is that of a receiver without the measurement)"""
+        self.carrier = self.fm.carrier()
+        for s, snap in enumerate(self.carrier):
+            w = snap["windowed"]
+            if snap["audio_blocks"] and (self._carrier_said[s] is None or abs(w["cnr_db"] - self._carrier_said[s]) >= 1.0):
+                self._carrier_said[s] = w["cnr_db"]
+                events[s].append((s, "carrier", {"level_db": w["level_db"], "cnr_db": w["cnr_db"], "offset_hz": w["offset_hz"]}))
 
     def _deliver_audio(self, pcm, events):
         """pcm: int16 [k, frames, 2], this push's new frames; events[s]: as for _feed_metadata"""
@@ -342,6 +366,12 @@ class FoundStation:
     country: str | None = None           # ... its country code and FCC facility id (SIS station id)
     facility_id: int | None = None
     first_name_s: float | None = None    # capture time at the end of the push that delivered the name
+    kind: str = "hd"                     # "hd": a station that decodes; "analog": scan(analog=True) found a carrier without one
+    cnr_db: float | None = None          # scan(analog=True): the running figures of the carrier measurement at offset_hz (cnr_db at the lower
+    level_db: float | None = None        # ... clamp: no analog carrier there, e.g. an all-digital station)
+    carrier_offset_hz: float | None = None   # ... the carrier sits at offset_hz + carrier_offset_hz
+    stereo: bool | None = None           # ... the pilot flag and level of the last audio block
+    pilot: float | None = None
 
 
 def _device_samples(raw, fmt: int, device: int):
@@ -426,22 +456,120 @@ def confirm_stations(raw, rate, fmt: str, found, *, confirm_seconds: float = CON
     return sorted(kept, key=lambda s: s.offset_hz)
 
 
+MIN_CNR_DB = 10.0           # confirm_analog: the FM threshold
+MAX_OFFSET_HZ = 5e3         # ... transmitters hold +-2 kHz, and a 20 ppm SDR adds 2 kHz at 100 MHz
+HD_GUARD_HZ = 100e3         # scan(analog=True): an analog nomination this close to a confirmed HD station is that station's host or sideband
+
+
+def survey_fm(raw, rate, fmt: str, *, seconds: float | None = None, nfft: int = 0, threshold_db: float = 6.0, device: int = 0,
+              lib_path: str | None = None) -> list:
+    """the analog-carrier detector's nominations over the first `seconds` of the capture -> [FoundStation(kind="analog"), ...] by ascending offset"""
+    code = eng.IQ_FORMATS[fmt]
+    x = _device_samples(raw, code, device)
+    n = x.numel() // 2
+    if seconds is not None:
+        n = min(n, int(seconds * float(Fraction(rate) if not isinstance(rate, float) else rate)))
+    sc = eng.Scanner(Fraction(rate) if not isinstance(rate, float) else rate, code, nfft=nfft, device=device, lib_path=lib_path)
+    try:
+        sc.push_tensor(x[:2 * n])
+        picks = sc.detect_fm(threshold_db=threshold_db)
+    finally:
+        sc.close()
+    return sorted((FoundStation(p["offset_hz"], p["score_db"], 0.0, 0.0, p["floor_db"], kind="analog") for p in picks), key=lambda s: s.offset_hz)
+
+
+def measure_carriers(x, n: int, rate, code: int, centres, *, chunk: int = 1 << 22, device: int = 0, lib_path: str | None = None, rds: bool = False,
+                     seconds_rds: float | None = None):
+    """the first n samples of the device tensor x through a Channelizer at `centres` and an FmDemod(carrier=True) behind it, no engine
+    -> (FmDemod.carrier() snapshots, pilot levels, stereo flags, rds snapshots or None)"""
+    import torch
+    ch = eng.Channelizer(rate, code, centres, device=device, lib_path=lib_path)
+    fm = eng.FmDemod(len(centres), device=device, lib_path=lib_path, carrier=True, rds=rds)
+    try:
+        for p in range(0, n, chunk):
+            y = ch.process_tensor(x[2 * p:2 * min(n, p + chunk)])
+            if y.shape[1]:
+                fm.process_tensor(y)
+        level, flag = fm.pilot()
+        return fm.carrier(), level, flag, ([fm.rds_get(k) for k in range(len(centres))] if rds else None)
+    finally:
+        fm.close()
+        ch.close()
+
+
+def confirm_analog(raw, rate, fmt: str, found, *, confirm_seconds: float = CONFIRM_SECONDS, min_cnr_db: float = MIN_CNR_DB,
+                   max_offset_hz: float = MAX_OFFSET_HZ, chunk: int = 1 << 22, device: int = 0, lib_path: str | None = None, names: bool = False,
+                   name_seconds: float | None = None, keep_all: bool = False) -> list:
+    """measure the carriers of the nominated centres (the CONFIRM_MAX best scores) over the first confirm_seconds of the capture, twice: at the
+    nominated centres, then at the centres corrected by the running offset_hz of the first pass.  Kept: second-pass running cnr_db >= min_cnr_db
+    and |offset_hz| <= max_offset_hz; a kept station's offset_hz is the corrected centre.  keep_all=True returns every candidate with its
+    figures (the hosts of HD stations: scan(analog=True)), uncorrected.  names=True: the second pass also decodes RDS, over name_seconds
+    (default NAME_SECONDS), and name is rds_callsign(PI) or else the PS."""
+    cands = sorted(found, key=lambda s: -s.score_db)[:CONFIRM_MAX]
+    if not cands:
+        return []
+    rate = Fraction(rate) if not isinstance(rate, float) else rate
+    fs = float(rate)
+    code = eng.IQ_FORMATS[fmt]
+    x = _device_samples(raw, code, device)
+    n = min(x.numel() // 2, int(confirm_seconds * fs))
+    centres = [s.offset_hz for s in cands]
+    if not keep_all:
+        first, _, _, _ = measure_carriers(x, n, rate, code, centres, chunk=chunk, device=device, lib_path=lib_path)
+        centres = [c + v["running"]["offset_hz"] for c, v in zip(centres, first)]
+    n2 = max(n, min(x.numel() // 2, int((NAME_SECONDS if name_seconds is None else name_seconds) * fs))) if names else n
+    snaps, level, flag, rds = measure_carriers(x, n2, rate, code, centres, chunk=chunk, device=device, lib_path=lib_path, rds=names)
+    kept = []
+    for k, s in enumerate(cands):
+        r = snaps[k]["running"]
+        s.offset_hz = centres[k]
+        s.cnr_db, s.level_db, s.carrier_offset_hz, s.stereo, s.pilot = r["cnr_db"], r["level_db"], r["offset_hz"], bool(flag[k]), float(level[k])
+        if names and s.name is None and rds[k]["pi"] >= 0:
+            s.name = eng.rds_callsign(rds[k]["pi"]) or (rds[k]["ps"].decode("latin-1").strip() if rds[k]["ps"] else None)
+        if keep_all or (r["cnr_db"] >= min_cnr_db and abs(r["offset_hz"]) <= max_offset_hz):
+            kept.append(s)
+    return sorted(kept, key=lambda s: s.offset_hz)
+
+
 def scan(raw, rate, fmt: str, *, seconds: float | None = None, confirm: bool = True, confirm_seconds: float = CONFIRM_SECONDS,
-         threshold_db: float = 6.0, device: int = 0, lib_path: str | None = None, names: bool = False, name_seconds: float | None = None) -> list:
+         threshold_db: float = 6.0, device: int = 0, lib_path: str | None = None, names: bool = False, name_seconds: float | None = None,
+         analog: bool = False, min_cnr_db: float = MIN_CNR_DB, max_offset_hz: float = MAX_OFFSET_HZ) -> list:
     """Find the HD stations of a capture.  raw: interleaved samples (numpy array, or torch tensor on the device) in `fmt` at `rate` S/s.
     The spectrum is taken over the first `seconds` (None: everything); confirm=False returns the detector's nominations, confirm=True
     only those that decode (fine sync and a PIDS frame with a good CRC) within the first confirm_seconds.  names=True: the confirmation decode
     also reads the stations' SIS and keeps decoding a confirmed station until its name arrived, up to name_seconds (default NAME_SECONDS) of the
-    capture: FoundStation.name / country / facility_id.  -> [FoundStation, ...] by ascending offset."""
+    capture: FoundStation.name / country / facility_id.  analog=True: analog-only FM stations are found as well (scan_analog: kind "analog", their
+    name from RDS with names=True), and the HD stations carry the figures of their hosts' carriers.  -> [FoundStation, ...] by ascending offset."""
     _, _, found = survey(raw, rate, fmt, seconds=seconds, threshold_db=threshold_db, device=device, lib_path=lib_path)
     if not confirm:
         return found
-    return confirm_stations(raw, rate, fmt, found, confirm_seconds=confirm_seconds, device=device, lib_path=lib_path, names=names, name_seconds=name_seconds)
+    hd = confirm_stations(raw, rate, fmt, found, confirm_seconds=confirm_seconds, device=device, lib_path=lib_path, names=names, name_seconds=name_seconds)
+    if not analog:
+        return hd
+    return scan_analog(raw, rate, fmt, hd, seconds=seconds, confirm_seconds=confirm_seconds, threshold_db=threshold_db, device=device, lib_path=lib_path,
+                       names=names, name_seconds=name_seconds, min_cnr_db=min_cnr_db, max_offset_hz=max_offset_hz)
+
+
+def scan_analog(raw, rate, fmt: str, hd, *, seconds: float | None = None, confirm_seconds: float = CONFIRM_SECONDS, threshold_db: float = 6.0,
+                device: int = 0, lib_path: str | None = None, names: bool = False, name_seconds: float | None = None,
+                min_cnr_db: float = MIN_CNR_DB, max_offset_hz: float = MAX_OFFSET_HZ) -> list:
+    """the analog half of scan(analog=True): hd (the confirmed HD stations) gain the figures of their hosts, and every kept analog nomination
+    that is not within HD_GUARD_HZ of one of them -- its host, or one of its sidebands -- joins them.  -> [FoundStation, ...] by ascending offset"""
+    nominated = survey_fm(raw, rate, fmt, seconds=seconds, threshold_db=threshold_db, device=device, lib_path=lib_path)
+    kept = confirm_analog(raw, rate, fmt, nominated, confirm_seconds=confirm_seconds, min_cnr_db=min_cnr_db, max_offset_hz=max_offset_hz, device=device,
+                          lib_path=lib_path, names=names, name_seconds=name_seconds)
+    kept = [s for s in kept if all(abs(s.offset_hz - h.offset_hz) > HD_GUARD_HZ for h in hd)]
+    confirm_analog(raw, rate, fmt, hd, confirm_seconds=confirm_seconds, device=device, lib_path=lib_path, keep_all=True)
+    return sorted(list(hd) + kept, key=lambda s: s.offset_hz)
 
 
 def format_found(s: FoundStation) -> str:
     line = f"found {s.offset_hz / 1e3:+.1f} kHz score {s.score_db:.1f} dB lower {s.lower_db:.1f} upper {s.upper_db:.1f}"
+    if s.kind == "analog":
+        line = f"found {s.offset_hz / 1e3:+.1f} kHz analog score {s.score_db:.1f} dB"
     line += f" psmi {s.psmi}" if s.psmi is not None else ""
+    if s.cnr_db is not None:
+        line += f" carrier {s.level_db:.1f} dBFS CNR {s.cnr_db:.1f} dB offset {s.carrier_offset_hz / 1e3:+.2f} kHz {'stereo' if s.stereo else 'mono'}"
     return line + (f" name {s.name}" if s.name is not None else "")
 
 
@@ -466,6 +594,8 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} ID3 program {v['program']}" + "".join(f" {k}={v[k]!r}" for k in ("title", "artist", "album", "genre") if k in v)
     if kind in _SIS_LINES:
         return f"{head} " + _SIS_LINES[kind](v)
+    if kind == "carrier":
+        return f"{head} carrier {v['level_db']:.1f} dBFS CNR {v['cnr_db']:.1f} dB offset {v['offset_hz'] / 1e3:+.2f} kHz"
     if kind == "rds":
         if v["kind"] == "pi":
             return f"{head} RDS PI 0x{v['pi']:04X}" + (f" ({v['callsign']})" if v["callsign"] else "")
@@ -635,6 +765,8 @@ def main(argv=None) -> int:
     ap.add_argument("--deemphasis", type=float, default=75.0, choices=[75.0, 50.0, 0.0], help="de-emphasis of the analog audio in us (0: none)")
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
     ap.add_argument("--rds", action="store_true", help="print RDS / RBDS of every station's analog host: PI (and the call sign it encodes), name, RadioText, clock")
+    ap.add_argument("--carrier", action="store_true", help="print level, CNR and centre error of every station's analog carrier whenever the CNR has moved by 1 dB")
+    ap.add_argument("--scan-analog", action="store_true", help="scan for analog-only FM stations as well as HD stations, and receive both")
     ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
     for i in range(len(argv) - 1):                  # "--offsets -800e3,0,400e3": a value that starts with '-' is still the value
@@ -647,7 +779,7 @@ def main(argv=None) -> int:
     fmt = eng.IQ_FORMATS[a.format]
     dtype = eng.IQ_DTYPES[fmt]
     stdin = a.file == "-"
-    do_scan = a.scan or a.scan_only or offsets is None
+    do_scan = a.scan or a.scan_only or a.scan_analog or offsets is None
     if stdin and (do_scan or a.spectrum):
         ap.error("standard input cannot be scanned (the scan reads the head of a real file): give --offsets, without --scan / --spectrum")
     if do_scan or a.spectrum:
@@ -658,6 +790,9 @@ def main(argv=None) -> int:
             write_spectrum_csv(a.spectrum, freqs, psd)
         if do_scan:
             found = confirm_stations(head, rate, a.format, found, confirm_seconds=a.scan_seconds, device=a.device, names=a.sis)
+            if a.scan_analog:
+                found = scan_analog(head, rate, a.format, found, seconds=a.scan_seconds, confirm_seconds=a.scan_seconds, threshold_db=a.threshold_db,
+                                    device=a.device, names=a.rds)
             for s in found:
                 print(format_found(s), flush=True)
             if a.scan_only:
@@ -669,7 +804,8 @@ def main(argv=None) -> int:
                     return 1
         del head
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
-                          data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis, rds=a.rds)
+                          data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis, rds=a.rds,
+                          carrier=a.carrier)
     wav = None
     if a.dump_analog is not None:
         wav = AnalogDump(a.dump_analog, offsets)
