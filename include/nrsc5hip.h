@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 21   /* 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 22   /* 22: + reception steering of the analog FM audio (nrsc5hip_fm_steer_enable, nrsc5hip_fm_steer, nrsc5hip_fm_steer_taps, nrsc5hip_stage_fm_steer); 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -1080,7 +1080,8 @@ int  nrsc5hip_fm_clip_counts(nrsc5hip_fm *fm, long long *counts /* [nchan][2]: L
 /* test hook (ABI 19): kernel launches the pushes have issued since create / reset -- per push the front end (when a d sample is new), the pilot
  * sums (a block complete), the audio (an audio block due) and the kept tails (always); with RDS also the matched filter (a grid point new) and,
  * when a window was decided, decisions, groups and the kept y; with the carrier measurement also, when a block completed, the block sums and the
- * report (which keeps the tails; the front end writes r in its one launch).  The stage hooks are not counted */
+ * report (which keeps the tails; the front end writes r in its one launch).  Reception steering adds no launch of its own: a steered object
+ * issues what an object with the carrier measurement does, the block sums in front of the audio.  The stage hooks are not counted */
 int  nrsc5hip_fm_debug_launches(nrsc5hip_fm *fm, long long *count);
 /* level a and stereo flag of the last audio block delivered (0 before the first); either pointer may be NULL */
 int  nrsc5hip_fm_pilot(nrsc5hip_fm *fm, float *level /* [nchan] */, int *stereo /* [nchan] */);
@@ -1207,6 +1208,50 @@ int  nrsc5hip_fm_carrier(nrsc5hip_fm *fm, nrsc5hip_fm_carrier_info *out /* [ncha
 /* stage hook: r (host, [nchan][(n_in + 1) / 2]) and the block triples (host, [nchan][((n_in + 1) / 2) / 540][3]: s2, s4, s1; may be NULL) of
  * n_in samples taken as a whole session from n = 0; the object's own session is not touched, and the measurement need not be enabled */
 int  nrsc5hip_stage_fm_carrier(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *r_out, double *sums_out);
+
+/* ---- reception steering (ABI 22): stereo blend, high-cut and soft mute of the analog FM audio by the carrier quality of its own block ------
+ * Opt-in per analog FM object (nrsc5hip_fm_steer_enable; it enables the carrier measurement when that is off).  Notation of "analog FM audio"
+ * and "carrier quality": blocks of 540 Fs1 samples, audio block j = 64 outputs, win[w] the pilot's float32 window (|w| <= 16), (s2, s4, s1)[j]
+ * the block triples.  Every quantity is a function of absolute block indices, there is no recurrence and no host round trip: any chunking of a
+ * session gives identical bytes.  With steering off nothing changes: not a byte of the audio, not the order or the count of the launches.
+ *   quality         of audio block j: W2_j = sum over |w| <= 16 of win[w] s2[j + w], W4_j likewise, in the arithmetic of the windowed report (each
+ *                   product in double, blocks in front of the stream zero, lane w + 16 holds term w, the xor butterfly): for the last block of a
+ *                   push they are the report's own bits.  c_j = the sum of (double)win[w] over the terms with j + w >= 0, same lanes, same
+ *                   butterfly (not the constant 17: the first 16 blocks of a session would read as bad reception only because half their window
+ *                   lies in front of the stream).  In double: kappa_j = W4_j (540 c_j) / (W2_j W2_j), q_j = min(1, max(0, 2 - kappa_j)) when
+ *                   W2_j > 0, else 0.  This is (S / P)^2 of the second / fourth moment estimator; for a good carrier q ~ 1 - 2 N / S, so a ramp
+ *                   linear in q is linear in the noise-to-carrier ratio, which the audio noise is proportional to
+ *   ramps           a threshold of t dB CNR (in the channel filter's bandwidth, as cnr_db) is, on the host in double, rho = 10^(t / 10),
+ *                   u = rho / (1 + rho), qt = u u; a ramp [lo_db, hi_db] is stored as float32 (q_lo, inv = 1 / (q_hi - q_lo)); on the device in
+ *                   float32 f_j = min(1, max(0, ((float)q_j - q_lo) inv)).  blend b_j = f_j (weight of the difference path; 18 .. 30 dB);
+ *                   high-cut h_j = f_j (weight of the wide table against the narrow one; 10 .. 20 dB); mute g_j = fma(f_j, 1 - floor, floor)
+ *                   (2 .. 8 dB, floor = 10^(mute_floor_db / 20), -20 dB), which is exactly 1 at f_j = 1.  A control that is off has factor 1
+ *   inside a block  the controls move linearly from block j - 1's value to block j's: for output i = k mod 64,
+ *                   c(k) = fma(c_j - c_{j-1}, (float)(i + 1) / 64, c_{j-1}), c_{-1} = c_0.  Only blocks up to j + 16 are read: the audio's latency
+ *   narrow table    a second prototype built like the first (same Kaiser attenuation and length, same de-emphasis convolution and cut, DC gain
+ *                   16), pass edge 4 kHz, stop edge 8 kHz: the transition width and with it taps_audio and phases are unchanged
+ *   output          Sw, Dw the two sums of "resampler", Sn, Dn the same sums on the narrow table; S' = fma(h, Sw, (1 - h) Sn), D' likewise;
+ *                   L = (S' + b D') g, R = (S' - b D') g, then scale, round, clamp and clip count as before.  In a block whose two end values of
+ *                   h are 1 the narrow sums are not formed (Sn = Dn = 0); in one whose two end values of b are 0 the difference path is not
+ *                   formed (D = 0, L == R byte for byte); with b = h = g = 1 at both ends the block's bytes are the unsteered ones.  A mono block
+ *                   (pilot below pilot_min) has D = 0 as before */
+enum { NRSC5HIP_FM_STEER_BLEND = 1, NRSC5HIP_FM_STEER_HIGHCUT = 2, NRSC5HIP_FM_STEER_MUTE = 4, NRSC5HIP_FM_STEER_ALL = 7 };
+typedef struct nrsc5hip_fm_steer_config {
+    unsigned controls;                   /* NRSC5HIP_FM_STEER_* or'ed; a control that is off has factor 1 */
+    double blend_db[2], highcut_db[2], mute_db[2];   /* [lo_db, hi_db], hi > lo, finite */
+    double mute_floor_db;                /* <= 0 */
+} nrsc5hip_fm_steer_config;
+typedef struct nrsc5hip_fm_steer_info { float q, blend, highcut, mute; } nrsc5hip_fm_steer_info;
+/* cfg NULL: every control, blend 18 .. 30 dB, high-cut 10 .. 20 dB, mute 2 .. 8 dB with a floor of -20 dB.  Only before the first
+ * nrsc5hip_fm_process / nrsc5hip_chan_feed_fm of the object and only once; nrsc5hip_fm_reset keeps it enabled */
+int  nrsc5hip_fm_steer_enable(nrsc5hip_fm *fm, const nrsc5hip_fm_steer_config *cfg);
+/* q and the three factors at the end of the last audio block delivered (all 0 before the first).  NRSC5HIP_EINVAL on an unsteered object */
+int  nrsc5hip_fm_steer(nrsc5hip_fm *fm, nrsc5hip_fm_steer_info *out /* [nchan] */);
+/* the narrow table, laid out as nrsc5hip_fm_taps' audio table */
+int  nrsc5hip_fm_steer_taps(nrsc5hip_fm *fm, float *audio_narrow /* [phases][taps_audio] */);
+/* stage hook: (q, b, h, g) of every audio block of n_in samples taken as a whole session from n = 0 (host, [nchan][audio blocks][4], audio
+ * blocks = max(0, ((n_in + 1) / 2) / 540 - 16)); the object's own session is not touched, and its launches are not counted */
+int  nrsc5hip_stage_fm_steer(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *out);
 
 #ifdef __cplusplus
 }

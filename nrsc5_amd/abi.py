@@ -263,5 +263,28 @@ def bind_carrier(lib) -> None:
     lib.nrsc5hip_scan_detect_fm.argtypes = [vp, ctypes.POINTER(ScanParams), vp, ci, ctypes.POINTER(ci)]
 
 
+FM_STEER_BLEND, FM_STEER_HIGHCUT, FM_STEER_MUTE, FM_STEER_ALL = 1, 2, 4, 7      # NRSC5HIP_FM_STEER_*
+FM_STEER_CONTROLS = {"blend": FM_STEER_BLEND, "highcut": FM_STEER_HIGHCUT, "mute": FM_STEER_MUTE}
+FM_STEER_DEFAULTS = dict(blend_db=(18.0, 30.0), highcut_db=(10.0, 20.0), mute_db=(2.0, 8.0), mute_floor_db=-20.0, controls=FM_STEER_ALL)
+
+
+class _FmSteerConfig(ctypes.Structure):
+    """nrsc5hip_fm_steer_config"""
+    _fields_ = [("controls", ctypes.c_uint), ("blend_db", ctypes.c_double * 2), ("highcut_db", ctypes.c_double * 2), ("mute_db", ctypes.c_double * 2),
+                ("mute_floor_db", ctypes.c_double)]
+
+
+def bind_steer(lib) -> None:
+    """argument types of reception steering on the analog FM object (include/nrsc5hip.h, ABI 22)"""
+    vp, ll = ctypes.c_void_p, ctypes.c_longlong
+    lib.nrsc5hip_abi_version.restype = ctypes.c_int
+    if lib.nrsc5hip_abi_version() < 22:                    # an older library loaded for an A/B comparison: it has everything but these
+        return
+    lib.nrsc5hip_fm_steer_enable.argtypes = [vp, ctypes.POINTER(_FmSteerConfig)]
+    lib.nrsc5hip_fm_steer.argtypes = [vp, vp]
+    lib.nrsc5hip_fm_steer_taps.argtypes = [vp, vp]
+    lib.nrsc5hip_stage_fm_steer.argtypes = [vp, vp, ll, ll, vp]
+
+
 class Nrsc5HipError(RuntimeError):
     pass

@@ -20,6 +20,12 @@ constexpr int PILOT_NUM = 608, PILOT_DEN = 11907;   // 19 kHz = 608 / 11907 cycl
 constexpr float DEV_SCALE = (float)(372093.75 / (2.0 * 3.14159265358979323846 * 75000.0));   // Fs1 / (2 pi 75 kHz): +-75 kHz -> +-1
 constexpr int W = 16;                         // pilot smoothing over 2 W + 1 blocks
 
+// reception steering: the three ramps in q as the device applies them, f = min(1, max(0, ((float)q - lo) * inv)); a control that is off has factor 1
+struct SteerRamps {
+    unsigned controls;                        // NRSC5HIP_FM_STEER_*
+    float blend_lo, blend_inv, highcut_lo, highcut_inv, mute_lo, mute_inv, mute_floor;
+};
+
 struct FrontArgs {
     const int16_t *in; long long in_stride;   // channel c's new input at in + c * in_stride: absolute samples [n0, n0 + n_in)
     long long n0, n_in;
@@ -51,6 +57,16 @@ struct AudioArgs {
     float *pilot;                             // [nchan][2]: level and stereo flag of the last block
 };
 
+// reception steering (k_fm_audio<true>): what the steered kernel reads on top.  A struct of its own: the unsteered kernel's arguments
+// stay as they were, to the byte
+struct SteeredAudioArgs : AudioArgs {
+    const double *t; long long t_stride, t_base;             // k_fm_carrier's block triples: block j of channel c at t[3 * (c * t_stride + j - t_base)]
+    const float *tab_n;                       // [tb][PHASES]: the narrow table, laid out as tab
+    SteerRamps ramps;
+    float4 *steer; long long steer_stride;    // (q, b, h, g) of channel c's last block at steer[c * steer_stride] ...
+    int steer_every;                          // ... or, for the stage hook, of every block: block j0 + i at steer[c * steer_stride + i]
+};
+
 struct KeepArgs {
     const float *d_old; float *d_new; long long d_stride, d_shift, d_count;     // d_new[i] = d_old[i + d_shift], i < d_count
     const float2 *p_old; float2 *p_new; long long p_stride, p_shift, p_count;
@@ -70,6 +86,7 @@ struct CountLaunches {
 void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a);
 void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a);
 void launch_audio(hipStream_t s, int blocks, int nchan, const AudioArgs &a);
+void launch_audio_steered(hipStream_t s, int blocks, int nchan, const SteeredAudioArgs &a);
 void launch_keep(hipStream_t s, int nchan, const KeepArgs &a);
 
 }  // namespace fm
@@ -93,6 +110,11 @@ struct nrsc5hip_fm {
     bool processed = false;                                  // a push has been launched since create
     nrsc5::RdsHost *rds = nullptr;                           // RDS (rds.hip), once enabled
     nrsc5::CarrierHost *carrier = nullptr;                   // carrier quality (fm_carrier.hip), once enabled
+    bool steer = false;                                      // reception steering, once enabled: needs carrier
+    nrsc5::fm::SteerRamps ramps = {};
+    std::vector<float> tab_n;                                // the narrow table, host copy [PHASES][tb]
+    float *d_tab_n = nullptr;
+    float4 *d_steer = nullptr;                               // [nchan]: (q, b, h, g) of the last audio block delivered
 };
 
 namespace nrsc5 {

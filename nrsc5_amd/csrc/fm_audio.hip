@@ -16,6 +16,7 @@ namespace {
 constexpr double FS = 744187.5, FS1 = FS / 2;
 constexpr double PASS_A = 95e3, STOP_A = 129361.0, ATT_A = 80.0;     // channel filter: passband edge, first primary-main carrier, design target
 constexpr double PASS_B = 15e3, STOP_B = 19e3, ATT_B = 66.0;          // audio prototype at 16 Fs1
+constexpr double PASS_N = 4e3, STOP_N = 8e3;                          // the narrow prototype of reception steering: the same transition width
 constexpr double EQ_F0 = 28000.0, EQ_F1 = 48000.0;                    // the droop equaliser is exact at these two frequencies
 constexpr int MAX_CHANNELS = 512;
 constexpr long long KEEP_MAX_BLOCKS = 2 * W + 3;
@@ -46,12 +47,46 @@ std::vector<double> kaiser_lowpass(int taps, double fc, double att_db)
     return h;
 }
 
+// audio prototype at 16 Fs1 with the given pass and stop edge: Kaiser lowpass convolved with the sampled one-pole, DC gain 16 -> [PHASES][tb]
+std::vector<float> audio_prototype(double pass, double stop, double deemphasis_us, int *tb_out)
+{
+    const double fv = PHASES * FS1, dw = 2 * M_PI * (stop - pass) / fv;
+    const int nk = (int)ceil((ATT_B - 7.95) / (2.285 * dw)) + 1;
+    std::vector<double> g = kaiser_lowpass(nk, 0.5 * (pass + stop) / fv, ATT_B);
+    if (deemphasis_us > 0) {
+        const double tf = deemphasis_us * 1e-6 * fv;
+        const int ne = (int)ceil(30.0 * log(2.0) * tf);                 // exp(-v / tf) < 2^-30 from here on
+        std::vector<double> e(ne), y(nk + ne - 1, 0.0);
+        for (int v = 0; v < ne; v++) e[v] = exp(-v / tf);
+        e[0] = 0.5;                                                     // the step at t = 0 sampled at its mid value
+        for (int i = 0; i < nk; i++)
+            for (int v = 0; v < ne; v++) y[i + v] += g[i] * e[v];
+        g.swap(y);
+    }
+    double sum = 0;
+    for (double v : g) sum += v;
+    const int tb = ((int)g.size() + PHASES - 1) / PHASES;
+    std::vector<float> tab((size_t)PHASES * tb, 0.0f);
+    for (size_t v = 0; v < g.size(); v++) tab[(v % PHASES) * tb + v / PHASES] = (float)(g[v] * PHASES / sum);
+    *tb_out = tb;
+    return tab;
+}
+
+// [PHASES][tb] -> [tb][PHASES], as the kernel reads it
+std::vector<float> device_layout(const std::vector<float> &tab, int tb)
+{
+    std::vector<float> dev((size_t)PHASES * tb);
+    for (int p = 0; p < PHASES; p++)
+        for (int j = 0; j < tb; j++) dev[(size_t)j * PHASES + p] = tab[(size_t)p * tb + j];
+    return dev;
+}
+
 void free_fm(nrsc5hip_fm *f)
 {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     (void)hipFree(f->d_ha); (void)hipFree(f->d_tab); (void)hipFree(f->d_win); (void)hipFree(f->d_scale); (void)hipFree(f->d_pilot); (void)hipFree(f->d_cs);
     for (int i = 0; i < 2; i++) { (void)hipFree(f->d_hist[i]); (void)hipFree(f->d_d[i]); (void)hipFree(f->d_p[i]); }
-    (void)hipFree(f->d_clips);
+    (void)hipFree(f->d_clips); (void)hipFree(f->d_tab_n); (void)hipFree(f->d_steer);
     nrsc5::rds_free(f->rds);
     nrsc5::carrier_free(f->carrier);
     if (f->stream) (void)hipStreamDestroy(f->stream);
@@ -64,6 +99,7 @@ int fm_zero_state(nrsc5hip_fm *f)
     HIPCHK(hipMemsetAsync(f->d_hist[1], 0, sizeof(int) * HIST * f->nchan, f->stream));
     HIPCHK(hipMemsetAsync(f->d_clips, 0, sizeof(unsigned long long) * 2 * f->nchan, f->stream));
     HIPCHK(hipMemsetAsync(f->d_pilot, 0, sizeof(float) * 2 * f->nchan, f->stream));
+    if (f->d_steer) HIPCHK(hipMemsetAsync(f->d_steer, 0, sizeof(float4) * f->nchan, f->stream));
     HIPCHK(hipStreamSynchronize(f->stream));
     f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0; f->launches = 0;
     if (f->carrier) { const int rc = nrsc5::carrier_reset(f); if (rc) return rc; }
@@ -141,7 +177,8 @@ int nrsc5::fm_check(nrsc5hip_fm *f, long long n_in, const int16_t *dev_out, long
     return 0;
 }
 
-// front, pilot sums, audio, the carrier sums (when enabled) and the kept tails on `stream`; no host wait (but for a buffer that has to grow)
+// front, pilot sums, audio, the carrier sums and report (when enabled; steered, the sums in front of the audio) and the kept tails on `stream`; no
+// host wait (but for a buffer that has to grow)
 int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long long in_stride, long long n_in, int16_t *out, long long out_stride)
 {
     if (n_in <= 0) return 0;
@@ -167,15 +204,22 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
         launch_pilot(s, (int)(c.b1 - f->blocks), f->nchan, a);
         HIPCHK(hipGetLastError());
     }
+    const bool new_blocks = f->carrier && c.b1 > f->blocks;
+    if (f->steer && new_blocks && (rc = nrsc5::carrier_launch_sums(f, s, d, c.b1))) return rc;      // steered: the audio reads the new blocks' triples
     if (c.a1 > f->audio_blocks) {
-        AudioArgs a;
+        SteeredAudioArgs a;
         a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.cs = f->d_cs;
         a.tab = f->d_tab; a.tb = f->tb; a.win = f->d_win; a.wsum = f->wsum; a.aq = f->aq; a.bq = f->bq; a.pilot_min = f->pilot_min; a.scale = f->d_scale;
         a.j0 = f->audio_blocks; a.k0 = BLOCK_OUT * f->audio_blocks; a.out = out; a.out_stride = out_stride; a.clips = f->d_clips; a.pilot = f->d_pilot;
-        launch_audio(s, (int)(c.a1 - f->audio_blocks), f->nchan, a);
+        if (f->steer) {
+            const nrsc5::Triples t = nrsc5::carrier_triples(f);
+            a.t = t.t; a.t_stride = t.t_stride; a.t_base = t.t_base; a.tab_n = f->d_tab_n; a.ramps = f->ramps; a.steer = f->d_steer; a.steer_stride = 1; a.steer_every = 0;
+            launch_audio_steered(s, (int)(c.a1 - f->audio_blocks), f->nchan, a);
+        } else launch_audio(s, (int)(c.a1 - f->audio_blocks), f->nchan, a);
         HIPCHK(hipGetLastError());
     }
-    if (f->carrier && c.b1 > f->blocks && (rc = nrsc5::carrier_launch(f, s, d, c.m1, c.b1, c.a1))) return rc;
+    if (!f->steer && new_blocks && (rc = nrsc5::carrier_launch_sums(f, s, d, c.b1))) return rc;
+    if (new_blocks && (rc = nrsc5::carrier_launch_report(f, s, c.m1, c.b1, c.a1))) return rc;
     // what the next call needs: d from the first tap of audio block a1, the block sums from a1 - W, the last HIST input samples
     long long d_base = (long long)BLOCK * c.a1 - f->tb - 1, p_base = c.a1 - W;
     if (d_base < 0) d_base = 0;
@@ -219,29 +263,9 @@ extern "C" int nrsc5hip_fm_create(const nrsc5hip_fm_config *cfg, nrsc5hip_fm **o
         const double a = (r0 - r1) / (2 * (c0 - c1));
         f->aq = (float)a; f->bq = (float)(r0 - 2 * a * c0);
     }
-    {   // audio prototype at 16 Fs1: Kaiser lowpass convolved with the sampled one-pole, DC gain 16
-        const double fv = PHASES * FS1, dw = 2 * M_PI * (STOP_B - PASS_B) / fv;
-        const int nk = (int)ceil((ATT_B - 7.95) / (2.285 * dw)) + 1;
-        std::vector<double> g = kaiser_lowpass(nk, 0.5 * (PASS_B + STOP_B) / fv, ATT_B);
-        if (cfg->deemphasis_us > 0) {
-            const double tf = cfg->deemphasis_us * 1e-6 * fv;
-            const int ne = (int)ceil(30.0 * log(2.0) * tf);                 // exp(-v / tf) < 2^-30 from here on
-            std::vector<double> e(ne), y(nk + ne - 1, 0.0);
-            for (int v = 0; v < ne; v++) e[v] = exp(-v / tf);
-            e[0] = 0.5;                                                     // the step at t = 0 sampled at its mid value
-            for (int i = 0; i < nk; i++)
-                for (int v = 0; v < ne; v++) y[i + v] += g[i] * e[v];
-            g.swap(y);
-        }
-        double sum = 0;
-        for (double v : g) sum += v;
-        f->tb = ((int)g.size() + PHASES - 1) / PHASES;
-        f->tab.assign((size_t)PHASES * f->tb, 0.0f);
-        for (size_t v = 0; v < g.size(); v++) f->tab[(v % PHASES) * f->tb + v / PHASES] = (float)(g[v] * PHASES / sum);
-    }
-    std::vector<float> dev_tab((size_t)PHASES * f->tb), win(2 * W + 1);
-    for (int p = 0; p < PHASES; p++)
-        for (int j = 0; j < f->tb; j++) dev_tab[(size_t)j * PHASES + p] = f->tab[(size_t)p * f->tb + j];
+    f->tab = audio_prototype(PASS_B, STOP_B, cfg->deemphasis_us, &f->tb);
+    const std::vector<float> dev_tab = device_layout(f->tab, f->tb);
+    std::vector<float> win(2 * W + 1);
     double wsum = 0;
     for (int w = -W; w <= W; w++) { const double v = 0.5 * (1 + cos(M_PI * w / (W + 1))); win[w + W] = (float)v; wsum += v; }
     f->wsum = (float)wsum;
@@ -393,5 +417,129 @@ extern "C" int nrsc5hip_stage_fm_mpx(nrsc5hip_fm *f, const int16_t *dev_in, long
     HIPCHK(hipStreamSynchronize(f->stream));
     HIPCHK(hipMemcpy(d_out, d.p, sizeof(float) * (size_t)m1 * f->nchan, hipMemcpyDeviceToHost));
     if (psum_out && b1 > 0) HIPCHK(hipMemcpy(psum_out, p.p, sizeof(float2) * (size_t)b1 * f->nchan, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- reception steering (include/nrsc5hip.h, "reception steering") ------------------------------------------------------------
+namespace {
+
+// a threshold in dB CNR as a value of q = (S / P)^2, in double
+double steer_q_of_db(double db)
+{
+    const double rho = pow(10.0, db / 10.0), u = rho / (1.0 + rho);
+    return u * u;
+}
+
+bool steer_ramp_of(const double db[2], float *lo, float *inv)
+{
+    if (!std::isfinite(db[0]) || !std::isfinite(db[1]) || !(db[1] > db[0])) return false;
+    const double q_lo = steer_q_of_db(db[0]), q_hi = steer_q_of_db(db[1]);
+    if (!(q_hi > q_lo)) return false;                        // (thresholds so high that both round to 1)
+    *lo = (float)q_lo; *inv = (float)(1.0 / (q_hi - q_lo));
+    return std::isfinite(*inv);
+}
+
+}  // namespace
+
+extern "C" int nrsc5hip_fm_steer_enable(nrsc5hip_fm *f, const nrsc5hip_fm_steer_config *cfg)
+{
+    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
+    if (f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is enabled already");
+    if (f->processed) FAIL(NRSC5HIP_EINVAL, "reception steering can be enabled only before the first push");
+    nrsc5hip_fm_steer_config c = {NRSC5HIP_FM_STEER_ALL, {18.0, 30.0}, {10.0, 20.0}, {2.0, 8.0}, -20.0};
+    if (cfg) c = *cfg;
+    if (c.controls & ~(unsigned)NRSC5HIP_FM_STEER_ALL) FAIL(NRSC5HIP_EINVAL, "controls 0x%x: unknown bits", c.controls);
+    SteerRamps r = {};
+    r.controls = c.controls;
+    if (!steer_ramp_of(c.blend_db, &r.blend_lo, &r.blend_inv)) FAIL(NRSC5HIP_EINVAL, "blend thresholds %g, %g dB: finite, the second above the first", c.blend_db[0], c.blend_db[1]);
+    if (!steer_ramp_of(c.highcut_db, &r.highcut_lo, &r.highcut_inv))
+        FAIL(NRSC5HIP_EINVAL, "high-cut thresholds %g, %g dB: finite, the second above the first", c.highcut_db[0], c.highcut_db[1]);
+    if (!steer_ramp_of(c.mute_db, &r.mute_lo, &r.mute_inv)) FAIL(NRSC5HIP_EINVAL, "mute thresholds %g, %g dB: finite, the second above the first", c.mute_db[0], c.mute_db[1]);
+    if (!std::isfinite(c.mute_floor_db) || c.mute_floor_db > 0.0) FAIL(NRSC5HIP_EINVAL, "mute_floor_db %g: finite, at most 0", c.mute_floor_db);
+    r.mute_floor = (float)pow(10.0, c.mute_floor_db / 20.0);
+    int tb = 0;
+    std::vector<float> tab_n = audio_prototype(PASS_N, STOP_N, f->deemphasis_us, &tb);
+    if (tb != f->tb) FAIL(NRSC5HIP_EINVAL, "the narrow table has %d taps per phase, the wide one %d", tb, f->tb);      // (the same transition width: never)
+    const std::vector<float> dev = device_layout(tab_n, tb);
+    nrsc5::DeviceGuard guard(f->device);
+    nrsc5::DevTmp d_tab, d_steer;
+    HIPCHK(hipMalloc(&d_tab.p, sizeof(float) * dev.size()));
+    HIPCHK(hipMalloc(&d_steer.p, sizeof(float4) * f->nchan));
+    HIPCHK(hipMemcpy(d_tab.p, dev.data(), sizeof(float) * dev.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_steer.p, 0, sizeof(float4) * f->nchan));
+    if (!f->carrier) { const int rc = nrsc5::carrier_enable(f); if (rc) return rc; }
+    f->d_tab_n = (float *)d_tab.p; f->d_steer = (float4 *)d_steer.p; d_tab.p = d_steer.p = nullptr;
+    f->tab_n.swap(tab_n); f->ramps = r; f->steer = true;
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_steer(nrsc5hip_fm *f, nrsc5hip_fm_steer_info *out)
+{
+    if (!f || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is not enabled on this object");
+    static_assert(sizeof(nrsc5hip_fm_steer_info) == sizeof(float4), "the device writes (q, b, h, g) as one float4");
+    nrsc5::DeviceGuard guard(f->device);
+    HIPCHK(hipStreamSynchronize(f->stream));
+    HIPCHK(hipMemcpy(out, f->d_steer, sizeof(float4) * f->nchan, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int nrsc5hip_fm_steer_taps(nrsc5hip_fm *f, float *audio_narrow)
+{
+    if (!f || !audio_narrow) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is not enabled on this object");
+    memcpy(audio_narrow, f->tab_n.data(), sizeof(float) * f->tab_n.size());
+    return 0;
+}
+
+extern "C" int nrsc5hip_stage_fm_steer(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *out)
+{
+    if (!f || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
+    if (!f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is not enabled on this object");
+    if (n_in <= 0) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
+    int rc = fm_check_input(f, dev_in, in_stride_elems, n_in);
+    if (rc) return rc;
+    const long long m1 = (n_in + 1) >> 1, b1 = m1 / BLOCK, a1 = b1 > W ? b1 - W : 0;
+    if ((m1 + FT - 1) / FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
+    if (a1 == 0) return 0;
+    const size_t K = (size_t)f->nchan;
+    nrsc5::DeviceGuard guard(f->device);
+    nrsc5::DevTmp d, r, p, t, hist, pcm, fac, clips, pilot;
+    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * K));
+    HIPCHK(hipMalloc(&r.p, sizeof(float) * (size_t)m1 * K));
+    HIPCHK(hipMalloc(&p.p, sizeof(float2) * (size_t)b1 * K));
+    HIPCHK(hipMalloc(&t.p, sizeof(double) * 3 * (size_t)b1 * K));
+    HIPCHK(hipMalloc(&hist.p, sizeof(int) * HIST * K));
+    HIPCHK(hipMalloc(&pcm.p, sizeof(int16_t) * 2 * BLOCK_OUT * (size_t)a1 * K));
+    HIPCHK(hipMalloc(&fac.p, sizeof(float4) * (size_t)a1 * K));
+    HIPCHK(hipMalloc(&clips.p, sizeof(unsigned long long) * 2 * K));
+    HIPCHK(hipMalloc(&pilot.p, sizeof(float) * 2 * K));
+    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * HIST * K, f->stream));
+    HIPCHK(hipMemsetAsync(clips.p, 0, sizeof(unsigned long long) * 2 * K, f->stream));
+    FrontArgs a;
+    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
+    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
+    a.r = (float *)r.p; a.r_stride = m1; a.r_base = 0;
+    launch_front(f->stream, (int)((m1 + FT - 1) / FT), f->nchan, a);
+    HIPCHK(hipGetLastError());
+    PilotArgs q;
+    q.d = (const float *)d.p; q.d_stride = m1; q.d_base = 0; q.cs = f->d_cs; q.p = (float2 *)p.p; q.p_stride = b1; q.p_base = 0; q.j0 = 0;
+    launch_pilot(f->stream, (int)b1, f->nchan, q);
+    HIPCHK(hipGetLastError());
+    CarrierArgs c;
+    c.r = (const float *)r.p; c.r_stride = m1; c.r_base = 0; c.d = (const float *)d.p; c.d_stride = m1; c.d_base = 0;
+    c.t = (double *)t.p; c.t_stride = b1; c.t_base = 0; c.j0 = 0;
+    launch_carrier(f->stream, (int)b1, f->nchan, c);
+    HIPCHK(hipGetLastError());
+    SteeredAudioArgs u;
+    u.d = (const float *)d.p; u.d_stride = m1; u.d_base = 0; u.p = (const float2 *)p.p; u.p_stride = b1; u.p_base = 0; u.cs = f->d_cs;
+    u.tab = f->d_tab; u.tb = f->tb; u.win = f->d_win; u.wsum = f->wsum; u.aq = f->aq; u.bq = f->bq; u.pilot_min = f->pilot_min; u.scale = f->d_scale;
+    u.j0 = 0; u.k0 = 0; u.out = (int16_t *)pcm.p; u.out_stride = 2 * BLOCK_OUT * a1; u.clips = (unsigned long long *)clips.p; u.pilot = (float *)pilot.p;
+    u.t = (const double *)t.p; u.t_stride = b1; u.t_base = 0; u.tab_n = f->d_tab_n; u.ramps = f->ramps;
+    u.steer = (float4 *)fac.p; u.steer_stride = a1; u.steer_every = 1;
+    launch_audio_steered(f->stream, (int)a1, f->nchan, u);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(f->stream));
+    HIPCHK(hipMemcpy(out, fac.p, sizeof(float4) * (size_t)a1 * K, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -10,7 +10,9 @@ struct nrsc5hip_fm;
 namespace nrsc5 {
 namespace fm {
 
-constexpr int TRIPLES_KEPT = 33;              // 2 W + 1: the block triples the windowed report of the next audio block reads
+// 2 W + 1: the block triples the windowed report of the next audio block reads.  The steered audio kernel reads one audio block further back, the
+// window of block a1 - 1 in front of the push's first new block a1, that is from block a1 - 1 - W = b1 - 2 W - 1 of the push before: the oldest kept
+constexpr int TRIPLES_KEPT = 33;
 
 struct CarrierArgs {
     const float *r; long long r_stride, r_base;      // r[m] of channel c at r[c * r_stride + m - r_base]
@@ -38,8 +40,14 @@ struct FrontTarget { float *r; long long r_stride, r_base; };
 // room for r[540 blocks, m1) and the triples up to b1: grown once the work queued on `s` has finished; what is kept moves over
 int carrier_reserve(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1);
 FrontTarget carrier_front(const nrsc5hip_fm *f);         // where k_fm_front writes r in this push
-// the block sums of the new blocks [f->blocks, b1), the reports and the kept tails; called while f still holds the counts in front of the push
-int carrier_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long m1, long long b1, long long a1);
+// the block sums of the new blocks [f->blocks, b1), then the reports and the kept tails: two launches, called in this order while f still holds
+// the counts in front of the push.  Unsteered both follow the audio; a steered object runs the sums in front of it, and its audio
+// kernel reads the triples where carrier_triples says
+int carrier_launch_sums(nrsc5hip_fm *f, hipStream_t s, const float *d, long long b1);
+int carrier_launch_report(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1, long long a1);
+struct Triples { const double *t; long long t_stride, t_base; };
+Triples carrier_triples(const nrsc5hip_fm *f);           // in this push, in front of carrier_launch_report
+int carrier_enable(nrsc5hip_fm *f);                      // nrsc5hip_fm_carrier_enable behind its checks
 int carrier_reset(nrsc5hip_fm *f);
 void carrier_free(CarrierHost *c);
 }  // namespace nrsc5

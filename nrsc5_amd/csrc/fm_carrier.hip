@@ -96,16 +96,28 @@ nrsc5::FrontTarget nrsc5::carrier_front(const nrsc5hip_fm *f)
     return FrontTarget{C->d_r[C->cur], C->r_cap, (long long)BLOCK * f->blocks};
 }
 
-int nrsc5::carrier_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long m1, long long b1, long long a1)
+int nrsc5::carrier_launch_sums(nrsc5hip_fm *f, hipStream_t s, const float *d, long long b1)
 {
     CarrierHost *C = f->carrier;
-    const long long r_base = (long long)BLOCK * f->blocks;
     CarrierArgs a;
-    a.r = C->d_r[C->cur]; a.r_stride = C->r_cap; a.r_base = r_base;
+    a.r = C->d_r[C->cur]; a.r_stride = C->r_cap; a.r_base = (long long)BLOCK * f->blocks;
     a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base;
     a.t = C->d_t[C->cur]; a.t_stride = C->t_cap; a.t_base = C->t_base; a.j0 = f->blocks;
     launch_carrier(s, (int)(b1 - f->blocks), f->nchan, a);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+nrsc5::Triples nrsc5::carrier_triples(const nrsc5hip_fm *f)
+{
+    const CarrierHost *C = f->carrier;
+    return Triples{C->d_t[C->cur], C->t_cap, C->t_base};
+}
+
+int nrsc5::carrier_launch_report(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1, long long a1)
+{
+    CarrierHost *C = f->carrier;
+    const long long r_base = (long long)BLOCK * f->blocks;
     ReportArgs q;
     q.t = C->d_t[C->cur]; q.t_new = C->d_t[C->cur ^ 1]; q.t_stride = C->t_cap; q.t_base = C->t_base;
     q.t_base_new = b1 > TRIPLES_KEPT ? b1 - TRIPLES_KEPT : 0;
@@ -122,6 +134,12 @@ extern "C" int nrsc5hip_fm_carrier_enable(nrsc5hip_fm *f)
     if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
     if (f->carrier) FAIL(NRSC5HIP_EINVAL, "the carrier measurement is enabled already");
     if (f->processed) FAIL(NRSC5HIP_EINVAL, "the carrier measurement can be enabled only before the first push");
+    return nrsc5::carrier_enable(f);
+}
+
+int nrsc5::carrier_enable(nrsc5hip_fm *f)
+{
+    static_assert(TRIPLES_KEPT >= 2 * W + 1, "the steered audio kernel reads the window of the audio block in front of the push");
     nrsc5::DeviceGuard guard(f->device);
     CarrierHost *C = new (std::nothrow) CarrierHost;
     if (!C) FAIL(NRSC5HIP_ENOMEM, "out of host memory");

@@ -9,12 +9,16 @@
 //               so the sum does not depend on which push completed the block.  No atomics.
 //   k_fm_audio  one workgroup = one pilot block = 64 audio outputs.  Every wave forms the smoothed pilot (33 block sums, a butterfly), the d span
 //               and the difference path 2 eq(d) sub go to LDS, and the block's 4 waves each sum a quarter of the taps of the 64 outputs for
-//               both paths from one table load; wave 0 adds the quarters in order, rounds, clamps and writes L, R.
+//               both paths from one table load; wave 0 adds the quarters in order, rounds, clamps and writes L, R.  Steered by reception
+//               (k_fm_audio<true>) every wave also forms the windowed carrier moments of blocks j - 1 and j from k_fm_carrier's
+//               triples and from them blend, high-cut and mute; the tap loop reads a second, narrow table only in a block whose high-cut is
+//               live, and wave 0 mixes.
 //   k_fm_keep   what the next call needs: the tail of d, of the block sums and of the input (as k_chan_history).
 // The pilot phase (608 m mod 11907) indexes a table of 11907 (cos, sin) pairs computed in double on the host: exact to float32 rounding,
 // the same bits on the device and in the CPU twin.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <type_traits>
 #include "fm_audio.h"
 #include "fastmath.h"
 
@@ -98,13 +102,50 @@ __global__ __launch_bounds__(64) void k_fm_pilot(PilotArgs a)
     if (threadIdx.x == 0) a.p[(long long)ch * a.p_stride + (j - a.p_base)] = make_float2(re, im);
 }
 
-__global__ __launch_bounds__(256) void k_fm_audio(AudioArgs a)
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
+// reception steering: the quality q of audio block jq from k_fm_carrier's block triples under the pilot's window, in
+// k_fm_carrier_report's arithmetic (lane w + W holds term w, each product in double, the xor butterfly): the same bits in every wave.  c is the
+// window's weight over the blocks that exist, not the constant 17: the first 16 blocks of a session lose the part in front of the stream
+__device__ __forceinline__ double steer_quality(const SteeredAudioArgs &a, int ch, long long jq, int lane)
+{
+    double w2 = 0.0, w4 = 0.0, c = 0.0;
+    const long long jb = jq + lane - W;
+    if (lane <= 2 * W && jb >= 0) {
+        const double *v = a.t + 3 * ((long long)ch * a.t_stride + (jb - a.t_base));
+        const double w = (double)a.win[lane];
+        w2 = v[0] * w; w4 = v[1] * w; c = w;
+    }
+    w2 = wave_sum(w2); w4 = wave_sum(w4); c = wave_sum(c);
+    if (!(w2 > 0.0)) return 0.0;
+    const double kappa = w4 * (540.0 * c) / (w2 * w2);
+    return fmin(1.0, fmax(0.0, 2.0 - kappa));
+}
+
+__device__ __forceinline__ float steer_ramp(float q, float lo, float inv) { return fminf(1.0f, fmaxf(0.0f, (q - lo) * inv)); }
+
+// the three factors (b, h, g) of a block of quality q; a control that is off has factor 1
+__device__ __forceinline__ void steer_factors(const SteerRamps &r, double q, float &b, float &h, float &g)
+{
+    const float qf = (float)q;
+    b = (r.controls & NRSC5HIP_FM_STEER_BLEND) ? steer_ramp(qf, r.blend_lo, r.blend_inv) : 1.0f;
+    h = (r.controls & NRSC5HIP_FM_STEER_HIGHCUT) ? steer_ramp(qf, r.highcut_lo, r.highcut_inv) : 1.0f;
+    g = (r.controls & NRSC5HIP_FM_STEER_MUTE) ? fmaf(steer_ramp(qf, r.mute_lo, r.mute_inv), 1.0f - r.mute_floor, r.mute_floor) : 1.0f;   // exactly 1 at the top
+}
+
+// STEER: the audio steered by reception.  A template: the instantiation without it is the kernel as it was, instruction for
+// instruction
+template <bool STEER> __global__ __launch_bounds__(256) void k_fm_audio(std::conditional_t<STEER, SteeredAudioArgs, AudioArgs> a)
 {
     HIP_DYNAMIC_SHARED(float, lds);
     const int tb = a.tb, ch = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     float *ds = lds;                                         // [tb + 542]: d[mlo ..], mlo = 540 j - tb - 1
     float *dd = lds + (tb + 542);                            // [tb + 540]: the difference path at m = mlo + 1 ..
-    float *part = dd + (tb + 540);                           // [4][64][2]
+    float *part = dd + (tb + 540);                           // [4][64][2], steered [4][4][64]
     const long long j = a.j0 + blockIdx.x;
     const long long mlo = (long long)BLOCK * j - tb - 1;
 
@@ -123,13 +164,26 @@ __global__ __launch_bounds__(256) void k_fm_audio(AudioArgs a)
     const float level = 2.0f * mag / (float)BLOCK / a.wsum;
     const bool stereo = level >= a.pilot_min;
 
+    // steered: the factors at the end of block j - 1 (c0; block 0 starts at its own) and of block j (c1), the same bits in every wave; `narrow`
+    // and `diff` are uniform over the block
+    float q1 = 0.0f, b0 = 1.0f, b1 = 1.0f, h0 = 1.0f, h1 = 1.0f, g0 = 1.0f, g1 = 1.0f;
+    bool narrow = false, diff = stereo;
+    if constexpr (STEER) {
+        const double qa = steer_quality(a, ch, j > 0 ? j - 1 : 0, lane), qb = steer_quality(a, ch, j, lane);
+        steer_factors(a.ramps, qa, b0, h0, g0);
+        steer_factors(a.ramps, qb, b1, h1, g1);
+        q1 = (float)qb;
+        narrow = !(h0 == 1.0f && h1 == 1.0f);                // both ends wide: the narrow sums are skipped
+        diff = stereo && !(b0 == 0.0f && b1 == 0.0f);        // both ends mono: the difference path is skipped, L == R
+    }
+
     const float *d = a.d + (long long)ch * a.d_stride;
     for (int i = tid; i < tb + 542; i += 256) {
         const long long m = mlo + i;
         ds[i] = m >= 0 ? d[m - a.d_base] : 0.0f;
     }
     __syncthreads();
-    if (stereo) {
+    if (diff) {
         const float ur = pr / mag, ui = pi / mag;            // exp(j 2 theta) = -(p / |p|)^2: the pilot is a sine
         const float c2 = -(ur * ur - ui * ui), s2 = -(2.0f * ur * ui);
         for (int i = tid; i < tb + 540; i += 256) {
@@ -151,8 +205,23 @@ __global__ __launch_bounds__(256) void k_fm_audio(AudioArgs a)
     const int base = (int)((t16 >> 4) - mlo), ph = (int)(t16 & 15);
     const int tq = (tb + 3) / 4, j0 = qtr * tq, j1 = min(tb, j0 + tq);
     const float *tab = a.tab + ph;
-    float s = 0.0f, dl = 0.0f;
-    if (stereo) {
+    float s = 0.0f, dl = 0.0f, sn = 0.0f, dn = 0.0f;
+    const float *tabn = tab;
+    if constexpr (STEER) tabn = a.tab_n + ph;
+    if (STEER && narrow) {                                   // both tables from the same two LDS reads
+        if (diff) {
+            for (int jj = j0; jj < j1; jj++) {
+                const float t = tab[jj * PHASES], tn = tabn[jj * PHASES], x = ds[base - jj], y = dd[base - 1 - jj];
+                s = fmaf(t, x, s); dl = fmaf(t, y, dl);
+                sn = fmaf(tn, x, sn); dn = fmaf(tn, y, dn);
+            }
+        } else {
+            for (int jj = j0; jj < j1; jj++) {
+                const float x = ds[base - jj];
+                s = fmaf(tab[jj * PHASES], x, s); sn = fmaf(tabn[jj * PHASES], x, sn);
+            }
+        }
+    } else if (diff) {
         for (int jj = j0; jj < j1; jj++) {
             const float t = tab[jj * PHASES];
             s = fmaf(t, ds[base - jj], s);
@@ -161,13 +230,31 @@ __global__ __launch_bounds__(256) void k_fm_audio(AudioArgs a)
     } else {
         for (int jj = j0; jj < j1; jj++) s = fmaf(tab[jj * PHASES], ds[base - jj], s);
     }
-    part[(qtr * 64 + lane) * 2] = s; part[(qtr * 64 + lane) * 2 + 1] = dl;
+    if (STEER) {                                             // [4 sums][4 quarters][64]
+        part[qtr * 64 + lane] = s; part[(4 + qtr) * 64 + lane] = dl; part[(8 + qtr) * 64 + lane] = sn; part[(12 + qtr) * 64 + lane] = dn;
+    } else {
+        part[(qtr * 64 + lane) * 2] = s; part[(qtr * 64 + lane) * 2 + 1] = dl;
+    }
     __syncthreads();
     if (tid < 64) {
-        float S = part[lane * 2], D = part[lane * 2 + 1];
-        for (int q = 1; q < 4; q++) { S += part[(q * 64 + lane) * 2]; D += part[(q * 64 + lane) * 2 + 1]; }
+        float S, D;
+        if (STEER) {
+            float4 v = make_float4(part[lane], part[256 + lane], part[512 + lane], part[768 + lane]);      // (Sw, Dw, Sn, Dn), the quarters in order
+            for (int q = 1; q < 4; q++) { v.x += part[q * 64 + lane]; v.y += part[(4 + q) * 64 + lane]; v.z += part[(8 + q) * 64 + lane]; v.w += part[(12 + q) * 64 + lane]; }
+            // the controls move linearly from block j - 1's value to block j's; with h = b = g = 1 at both ends every operation here is a
+            // multiplication by 1 or an fma with weight 0: the bytes of the unsteered kernel
+            const float frac = (float)(lane + 1) / 64.0f;
+            const float b = fmaf(b1 - b0, frac, b0), h = fmaf(h1 - h0, frac, h0), gm = fmaf(g1 - g0, frac, g0);
+            const float Sp = fmaf(h, v.x, (1.0f - h) * v.z), Dp = fmaf(h, v.y, (1.0f - h) * v.w);
+            S = (Sp + b * Dp) * gm; D = (Sp - b * Dp) * gm;
+        } else {
+            S = part[lane * 2]; D = part[lane * 2 + 1];
+            for (int q = 1; q < 4; q++) { S += part[(q * 64 + lane) * 2]; D += part[(q * 64 + lane) * 2 + 1]; }
+        }
         const float g = a.scale[ch];
-        float yl = rintf((S + D) * g), yr = rintf((S - D) * g);
+        float yl, yr;
+        if (STEER) { yl = rintf(S * g); yr = rintf(D * g); }    // S and D hold L and R here
+        else { yl = rintf((S + D) * g); yr = rintf((S - D) * g); }
         int cl = 0, cr = 0;
         if (yl > 32767.0f) { yl = 32767.0f; cl = 1; } else if (yl < -32768.0f) { yl = -32768.0f; cl = 1; }
         if (yr > 32767.0f) { yr = 32767.0f; cr = 1; } else if (yr < -32768.0f) { yr = -32768.0f; cr = 1; }
@@ -178,6 +265,10 @@ __global__ __launch_bounds__(256) void k_fm_audio(AudioArgs a)
             if (bl) atomicAdd(a.clips + 2 * ch, (unsigned long long)__popcll(bl));
             if (br) atomicAdd(a.clips + 2 * ch + 1, (unsigned long long)__popcll(br));
             if (blockIdx.x == gridDim.x - 1) { a.pilot[2 * ch] = level; a.pilot[2 * ch + 1] = stereo ? 1.0f : 0.0f; }
+            if constexpr (STEER) {
+                if (a.steer_every) a.steer[(long long)ch * a.steer_stride + blockIdx.x] = make_float4(q1, b1, h1, g1);
+                else if (blockIdx.x == gridDim.x - 1) a.steer[(long long)ch * a.steer_stride] = make_float4(q1, b1, h1, g1);
+            }
         }
     }
 }
@@ -216,7 +307,13 @@ void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a)
 void launch_audio(hipStream_t s, int blocks, int nchan, const AudioArgs &a)
 {
     count_launch();
-    hipLaunchKernelGGL(k_fm_audio, dim3(blocks, nchan), dim3(256), sizeof(float) * (2 * a.tb + 542 + 540 + 512), s, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fm_audio<false>), dim3(blocks, nchan), dim3(256), sizeof(float) * (2 * a.tb + 542 + 540 + 512), s, a);
+}
+
+void launch_audio_steered(hipStream_t s, int blocks, int nchan, const SteeredAudioArgs &a)
+{
+    count_launch();
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fm_audio<true>), dim3(blocks, nchan), dim3(256), sizeof(float) * (2 * a.tb + 542 + 540 + 1024), s, a);
 }
 
 void launch_keep(hipStream_t s, int nchan, const KeepArgs &a)

@@ -19,7 +19,7 @@ if _AB_LIB:
 
 from . import abi
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
-from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig
+from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig, _FmSteerConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
                         sis_utf8, sis_text, _sis_device_info, sis_event_fields, rds_text, rds_callsign, rds_event_fields, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
 
@@ -188,6 +188,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     lib.nrsc5hip_stage_fm_mpx.argtypes = [vp, vp, ll, ll, vp, vp]
     abi.bind_rds(lib)
     abi.bind_carrier(lib)
+    abi.bind_steer(lib)
     lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_scan_destroy.argtypes = [vp]
     lib.nrsc5hip_scan_destroy.restype = None
@@ -226,7 +227,8 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_fm_process", "nrsc5hip_fm_clip_counts", "nrsc5hip_fm_pilot", "nrsc5hip_stage_fm_mpx", "nrsc5hip_chan_feed_fm",
     "nrsc5hip_fm_debug_launches", "nrsc5hip_fm_rds_enable", "nrsc5hip_fm_rds_read", "nrsc5hip_fm_rds_get", "nrsc5hip_fm_rds_stats", "nrsc5hip_fm_rds_info", "nrsc5hip_fm_rds_taps",
     "nrsc5hip_stage_rds_mf", "nrsc5hip_stage_rds_groups",
-    "nrsc5hip_fm_carrier_enable", "nrsc5hip_fm_carrier", "nrsc5hip_stage_fm_carrier", "nrsc5hip_scan_detect_fm_psd", "nrsc5hip_scan_detect_fm"]
+    "nrsc5hip_fm_carrier_enable", "nrsc5hip_fm_carrier", "nrsc5hip_stage_fm_carrier", "nrsc5hip_scan_detect_fm_psd", "nrsc5hip_scan_detect_fm",
+    "nrsc5hip_fm_steer_enable", "nrsc5hip_fm_steer", "nrsc5hip_fm_steer_taps", "nrsc5hip_stage_fm_steer"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -950,7 +952,7 @@ class FmDemod:
     AUDIO_RATE = FM_AUDIO_RATE
 
     def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None,
-                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2, carrier: bool = False):
+                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2, carrier: bool = False, steer=False):
         self.lib = load_library(lib_path)
         self.nchan, self.device, self.deemphasis_us = int(nchan), device, float(deemphasis_us)
         self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), (self.nchan,)))
@@ -962,12 +964,15 @@ class FmDemod:
         self.taps_channel, self.taps_audio, self.phases, self.latency_in = ta.value, tb.value, ph.value, lat.value
         self.rds = False
         self.carrier_enabled = False
-        if rds or carrier:
+        self.steer_config = None
+        if rds or carrier or steer:
             try:
                 if rds:
                     self.rds_enable(rds_raw_groups, rds_correct_burst)
                 if carrier:
                     self.carrier_enable()
+                if steer:
+                    self.steer_enable(**({} if steer is True else dict(steer)))
             except Nrsc5HipError:
                 self.close()                                       # the demodulator that was created goes with the failed constructor
                 raise
@@ -1057,6 +1062,43 @@ class FmDemod:
         t = np.zeros((self.nchan, m1 // 540, 3), dtype=np.float64)
         self._check(self.lib.nrsc5hip_stage_fm_carrier(self._h, dev_in, in_stride_elems, n_in, r.ctypes.data, t.ctypes.data))
         return r, t
+
+    # ---- reception steering: blend, high-cut and mute by the carrier quality of the block (nrsc5hip_fm_steer*) ------------------------------
+    def steer_enable(self, blend_db=None, highcut_db=None, mute_db=None, mute_floor_db=None, controls=None):
+        """only before the first push, and once; enables the carrier measurement when it is off.  Thresholds are (lo_db, hi_db) in dB CNR as
+        carrier() reports it; controls: FM_STEER_* or'ed, or names ("blend", "highcut", "mute").  No argument: the defaults (FM_STEER_DEFAULTS)"""
+        cfg = dict(FM_STEER_DEFAULTS)
+        for k, v in (("blend_db", blend_db), ("highcut_db", highcut_db), ("mute_db", mute_db), ("mute_floor_db", mute_floor_db), ("controls", controls)):
+            if v is not None:
+                cfg[k] = v
+        if not isinstance(cfg["controls"], int):
+            bits = 0
+            for name in cfg["controls"]:
+                bits |= FM_STEER_CONTROLS[name]
+            cfg["controls"] = bits
+        pair = lambda v: (ctypes.c_double * 2)(float(v[0]), float(v[1]))
+        c = _FmSteerConfig(int(cfg["controls"]), pair(cfg["blend_db"]), pair(cfg["highcut_db"]), pair(cfg["mute_db"]), float(cfg["mute_floor_db"]))
+        self._check(self.lib.nrsc5hip_fm_steer_enable(self._h, ctypes.byref(c)))
+        self.steer_config = cfg
+        self.carrier_enabled = True
+
+    def steer(self) -> list:
+        """one dict per channel: {"q", "blend", "highcut", "mute"} at the end of the last audio block delivered (all 0 before the first)"""
+        out = np.zeros((self.nchan, 4), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_fm_steer(self._h, out.ctypes.data))
+        return [{"q": float(v[0]), "blend": float(v[1]), "highcut": float(v[2]), "mute": float(v[3])} for v in out]
+
+    def steer_taps(self) -> np.ndarray:
+        """float32 [phases][taps_audio]: the narrow table as stored"""
+        tab = np.zeros((self.phases, self.taps_audio), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_fm_steer_taps(self._h, tab.ctypes.data))
+        return tab
+
+    def stage_steer(self, dev_in: int, in_stride_elems: int, n_in: int) -> np.ndarray:
+        """nrsc5hip_stage_fm_steer -> float32 [nchan][audio blocks][4]: (q, b, h, g) of every audio block of the input taken as a whole session"""
+        out = np.zeros((self.nchan, max(0, ((n_in + 1) // 2) // 540 - 16), 4), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_stage_fm_steer(self._h, dev_in, in_stride_elems, n_in, out.ctypes.data))
+        return out
 
     def close(self):
         if self._h:

@@ -15,6 +15,8 @@ DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets
 (44.1 kHz, 16 bit, stereo; --deemphasis 75, 50 or 0 us) and prints one `analog frames N` line per file at the end.
 --rds decodes RDS / RBDS of every station's analog host on the device and prints one line per report: `station 1 (+0.0 kHz): RDS PI 0x3AAB (KQED)`,
 `... RDS PS "KEXP-FM "`, `... RDS RT "..."`, `... RDS clock MJD 60310 13:37 UTC-07:00`.
+--steer steers the analog audio by the reception of its own block -- stereo blend, high-cut, soft mute; --blend-db / --highcut-db / --mute-db LO,HI
+set the CNR thresholds and imply it -- and prints `station 1 (+0.0 kHz): reception blend 0.42 high-cut 1.00 mute 1.00`.
 --carrier measures every station's analog carrier on the device and prints `station 1 (+0.0 kHz): carrier -21.3 dBFS CNR 31.2 dB offset +0.41 kHz`
 whenever the CNR has moved by 1 dB; --scan-analog makes the scan find analog-only FM stations as well (the spectrum nominates carriers, a measurement
 of each one's CNR and centre error confirms them) and receives both kinds: `found +400.3 kHz analog score 18.8 dB carrier -54.7 dBFS CNR 15.3 dB ...`.
@@ -83,12 +85,17 @@ class WidebandReceiver:
     carrier=True: the receiver also measures every station's analog carrier on the device (FmDemod(carrier=True); it creates the FmDemod if
     neither analog nor rds did).  carrier[s] is the station's snapshot after every push (FmDemod.carrier: the windowed and the running level_db,
     cnr_db, offset_hz and the sums behind them), and a ("carrier", {"level_db", "cnr_db", "offset_hz"}) event is returned by the push whenever the
-    windowed cnr_db has moved by 1 dB or more; the logs are those of a receiver without the measurement."""
+    windowed cnr_db has moved by 1 dB or more; the logs are those of a receiver without the measurement.
+    steer=True (or a dict of FmDemod.steer_enable's arguments: blend_db, highcut_db, mute_db, mute_floor_db, controls): the analog audio is steered by
+    the reception of its own block -- stereo blend, high-cut and soft mute on the device (FmDemod(steer=...)); it implies analog=True.  steer[s] is
+    the station's snapshot after every push (FmDemod.steer: q, blend, highcut, mute at the end of the last audio block), and a ("steer", {...})
+    event is returned by the push with the station's first audio and whenever its blend crosses 0.5 or its mute crosses the midpoint of its range:
+    rare by design.  The logs are those of a receiver without steering."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
                  programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
                  lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None, rds: bool = False,
-                 carrier: bool = False):
+                 carrier: bool = False, steer=False):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -122,17 +129,21 @@ class WidebandReceiver:
         self.now_playing = [{} for _ in range(self.k)]
         self.aas = [[] for _ in range(self.k)]
         self.sis = eng.SisConsumer(self.engine, self.k) if sis else None
-        self.analog = bool(analog)
+        self.steer_enabled = bool(steer)
+        self.analog = bool(analog) or self.steer_enabled
         self.on_audio = on_audio
         self.rds = bool(rds)
         self.carrier_enabled = bool(carrier)
         self.fm = None
         if self.analog or self.rds or self.carrier_enabled:
             self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path, **({"rds": True} if self.rds else {}),
-                                  **({"carrier": True} if self.carrier_enabled else {}))
+                                  **({"carrier": True} if self.carrier_enabled else {}), **({"steer": steer} if self.steer_enabled else {}))
+        self.steer = [None] * self.k
+        self._steer_side = [None] * self.k
         self.carrier = [None] * self.k
         self._carrier_said = [None] * self.k
         self.audio = [[] for _ in range(self.k)]
+        self._audio_seen = False             # (the CLI clears audio[s] after every push)
         self.stereo = [False] * self.k
         self.pilot = [0.0] * self.k
 
@@ -261,7 +272,22 @@ class WidebandReceiver:
                 new[e["channel"]].append((e["channel"], "rds", v))
         if self.carrier_enabled:
             self._measure_carrier(new)
+        if self.steer_enabled:
+            self._measure_steer(new)
         return [ev for per in new for ev in per]
+
+    def _measure_steer(self, events):
+        """steer[s]: the snapshot after this push; a ("steer", {...}) event with the first audio and whenever the blend has crossed 0.5 or the mute
+        the midpoint of its range since the last one (an event of the push only, as "carrier" is)"""
+        self.steer = self.fm.steer()
+        if not self._audio_seen:
+            return
+        mid = 0.5 * (1.0 + 10.0 ** (self.fm.steer_config["mute_floor_db"] / 20.0))
+        for s, snap in enumerate(self.steer):
+            side = (snap["blend"] >= 0.5, snap["mute"] >= mid)
+            if side != self._steer_side[s]:
+                self._steer_side[s] = side
+                events[s].append((s, "steer", dict(snap)))
 
     def _measure_carrier(self, events):
         """carrier[s]: the snapshot after this push; a ("carrier", {...}) event whenever the windowed cnr_db has moved by 1 dB or more since the
@@ -277,6 +303,7 @@ class WidebandReceiver:
         """pcm: int16 [k, frames, 2], this push's new frames; events[s]: as for _feed_metadata"""
         if pcm.shape[1] == 0:
             return
+        self._audio_seen = True
         level, flag = self.fm.pilot()
         for s in range(self.k):
             block = np.ascontiguousarray(pcm[s])
@@ -596,6 +623,8 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} " + _SIS_LINES[kind](v)
     if kind == "carrier":
         return f"{head} carrier {v['level_db']:.1f} dBFS CNR {v['cnr_db']:.1f} dB offset {v['offset_hz'] / 1e3:+.2f} kHz"
+    if kind == "steer":
+        return f"{head} reception blend {v['blend']:.2f} high-cut {v['highcut']:.2f} mute {v['mute']:.2f}"
     if kind == "rds":
         if v["kind"] == "pi":
             return f"{head} RDS PI 0x{v['pi']:04X}" + (f" ({v['callsign']})" if v["callsign"] else "")
@@ -766,6 +795,12 @@ def main(argv=None) -> int:
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
     ap.add_argument("--rds", action="store_true", help="print RDS / RBDS of every station's analog host: PI (and the call sign it encodes), name, RadioText, clock")
     ap.add_argument("--carrier", action="store_true", help="print level, CNR and centre error of every station's analog carrier whenever the CNR has moved by 1 dB")
+    ap.add_argument("--steer", action="store_true", help="steer the analog audio by reception: stereo blend, high-cut and soft mute (with --dump-analog); prints "
+                    "`reception blend B high-cut H mute G` with a station's first audio and when its blend crosses 0.5 or its mute the midpoint of its range")
+    pair = lambda t: tuple(float(v) for v in t.split(","))
+    ap.add_argument("--blend-db", type=pair, metavar="LO,HI", default=None, help="CNR in dB where the stereo blend starts and where it is complete (18,30); implies --steer")
+    ap.add_argument("--highcut-db", type=pair, metavar="LO,HI", default=None, help="CNR in dB where the high-cut is full and where it ends (10,20); implies --steer")
+    ap.add_argument("--mute-db", type=pair, metavar="LO,HI", default=None, help="CNR in dB where the soft mute is at its floor and where it ends (2,8); implies --steer")
     ap.add_argument("--scan-analog", action="store_true", help="scan for analog-only FM stations as well as HD stations, and receive both")
     ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -773,6 +808,11 @@ def main(argv=None) -> int:
         if argv[i] == "--offsets":
             argv[i:i + 2] = ["--offsets=" + argv[i + 1]]
             break
+    for name in ("--blend-db", "--highcut-db", "--mute-db"):
+        for i in range(len(argv) - 1):
+            if argv[i] == name:
+                argv[i:i + 2] = [name + "=" + argv[i + 1]]
+                break
     a = ap.parse_args(argv)
     rate = Fraction(a.rate)
     offsets = None if a.offsets is None else [float(x) for x in a.offsets.split(",") if x]
@@ -803,9 +843,15 @@ def main(argv=None) -> int:
                     print("no station found", file=sys.stderr)
                     return 1
         del head
+    steer = False
+    if a.steer or a.blend_db or a.highcut_db or a.mute_db:
+        steer = {k: v for k, v in (("blend_db", a.blend_db), ("highcut_db", a.highcut_db), ("mute_db", a.mute_db)) if v is not None} or True
+        for v in (a.blend_db, a.highcut_db, a.mute_db):
+            if v is not None and len(v) != 2:
+                ap.error("a threshold pair is LO,HI")
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
                           data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis, rds=a.rds,
-                          carrier=a.carrier)
+                          carrier=a.carrier, steer=steer)
     wav = None
     if a.dump_analog is not None:
         wav = AnalogDump(a.dump_analog, offsets)
@@ -827,8 +873,8 @@ def main(argv=None) -> int:
                 line = format_event(rx, s, kind, v)
                 if line:
                     print(line, flush=True)
-            if wav is not None:
-                for kept in rx.audio:                          # written and flushed by on_audio
+            if wav is not None or steer:
+                for kept in rx.audio:                          # written and flushed by on_audio (or, steered without a dump, not wanted)
                     kept.clear()
             if dump is not None:
                 dump.flush()
