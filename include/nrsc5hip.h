@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 22   /* 22: + reception steering of the analog FM audio (nrsc5hip_fm_steer_enable, nrsc5hip_fm_steer, nrsc5hip_fm_steer_taps, nrsc5hip_stage_fm_steer); 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 23   /* 23: + EAS alerts (SAME) of the analog host (nrsc5hip_fm_same_enable, _same_read, _same_get, _same_stats, _same_info, _same_table, nrsc5hip_stage_same_tones, _stage_same_frames); 22: + reception steering of the analog FM audio (nrsc5hip_fm_steer_enable, nrsc5hip_fm_steer, nrsc5hip_fm_steer_taps, nrsc5hip_stage_fm_steer); 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -1252,6 +1252,80 @@ int  nrsc5hip_fm_steer_taps(nrsc5hip_fm *fm, float *audio_narrow /* [phases][tap
 /* stage hook: (q, b, h, g) of every audio block of n_in samples taken as a whole session from n = 0 (host, [nchan][audio blocks][4], audio
  * blocks = max(0, ((n_in + 1) / 2) / 540 - 16)); the object's own session is not touched, and its launches are not counted */
 int  nrsc5hip_stage_fm_steer(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *out);
+
+/* ---- EAS alerts (SAME) of the analog host (ABI 23): the headers and end-of-message bursts of the Emergency Alert System in the programme audio ----
+ * Opt-in per analog FM object (nrsc5hip_fm_same_enable); it then runs inside every nrsc5hip_fm_process / nrsc5hip_chan_feed_fm on the same
+ * stream, from the discriminator output d[m] at Fs1 = 372 093.75 S/s (before de-emphasis).  SAME is AFSK at 3125 / 6 bit/s: mark (1) 6250 / 3 Hz,
+ * four cycles per bit, space (0) 1562.5 Hz, three cycles per bit; bytes of 8 bits, the least significant first, no start or stop bits; a burst
+ * is 16 bytes 0xAB and then ASCII: the header ZCZC-ORG-EEE-PSSCCC(-PSSCCC ..)+TTTT-JJJHHMM-LLLLLLLL- or the end of message NNNN, each sent three
+ * times about 1 s apart.  On the Fs1 grid every rate is exact: a bit is 35721 / 50 samples, mark 200 / 35721 and space 150 / 35721 cycles per
+ * sample, so timing is a function of absolute sample indices (64-bit integers): no NCO, no loop filter, no recurrence in the signal path, and
+ * any chunking of a session gives identical bits, events and counters.  With SAME off nothing changes: no byte, no event, no launch count.
+ *   tone sums       a grid of 8 points per bit: point r starts at g(r) = floor(35721 r / 400).  Segment sums, f = 1 (mark, k_1 = 200) and
+ *                   f = 0 (space, k_0 = 150): c_f[r] = sum over m = g(r) .. g(r + 1) - 1 (89 or 90 samples) of
+ *                   d[m] exp(-j 2 pi ((k_f m) mod 35721) / 35721), from one table of 35 721 (cos, sin) pairs computed in double and stored
+ *                   float32; in float32, m ascending, Re += fma(d, cos, .), Im likewise with sin, negated at the end.  Bit sums
+ *                   C_f[r] = c_f[r] + c_f[r + 1] + .. + c_f[r + 7], added in that order: exactly one bit length from g(r).  Decision value
+ *                   q[r] = (Re C_1^2 + Im C_1^2) - (Re C_0^2 + Im C_0^2)
+ *   timing          windows of 64 bits = 512 grid points: M_w[s] = sum over k < 64 of |q[512 w + 8 k + s]| (lane 8 g + s sums k = g, g + 8, ..
+ *                   in order, then a butterfly over g), s_w = argmax, ties to the lowest s; sampling points 512 w + 8 k + s_w.  Seam to
+ *                   window w - 1: gap = 8 + s_w - s_{w-1}; gap < 4: the first point of w is dropped; gap > 12: one point is inserted 8 grid
+ *                   steps behind the last point of w - 1.  Every point yields a bit: the first window of a session has 64
+ *   decisions       bit = 1 where q > 0.  A window is decided once every c it reads exists, c[512 w + 518] the last: window w after
+ *                   2 floor(35721 (512 w + 519) / 400) - 1 input samples (latency_in of nrsc5hip_fm_same_info: window 0, 92 693).  No flush
+ *   framing         per channel, in order over the bit stream; bit positions count from the last reset.  Search: a position matches when the
+ *                   16 bits that end there are 0xAB 0xAB; a match while not in a message sets the byte boundary and enters preamble (and is
+ *                   counted, and remembered as the burst's preamble match, when it comes from search).  Preamble: whole bytes; 0xAB stays, Z or
+ *                   N opens a message, any other byte goes back to search.  Message: bytes accumulate; abort, counted, on a byte outside
+ *                   0x20 .. 0x7E, when the first four bytes are neither ZCZC nor NNNN, and at 268 bytes; NNNN is complete at four bytes,
+ *                   ZCZC.. at the third '-' behind the first '+'.  A complete burst is an NRSC5HIP_SAME_BURST event; the search resumes
+ *   vote            a burst joins the current group when the group holds one or two bursts of its kind (header, end of message) and its
+ *                   preamble match lies at most 2604 bits (5 s) behind the last bit of the group's newest burst; else it opens a new group.
+ *                   One NRSC5HIP_SAME_MESSAGE event per group: the first time a burst equals an earlier one of the group byte for byte, or at
+ *                   the third burst when all three have one length and every byte position a 2-of-3 majority (the text is the majority's).
+ *                   A group that never agrees is counted when its third burst fails or when the next group opens
+ * The fields of a header are not parsed on the device. */
+#define NRSC5HIP_SAME_TEXT_MAX 268
+typedef struct nrsc5hip_same_config {
+    int burst_events;                    /* 1: also an NRSC5HIP_SAME_BURST event per burst; 0: messages only */
+} nrsc5hip_same_config;
+enum { NRSC5HIP_SAME_BURST = 1, NRSC5HIP_SAME_MESSAGE = 2 };
+enum { NRSC5HIP_SAME_HEADER = 1, NRSC5HIP_SAME_EOM = 2 };
+/* first, last: bit index of the first bit of the burst's text and of its last bit (MESSAGE: of the burst that decided it).  v: BURST {kind
+ * (NRSC5HIP_SAME_HEADER / _EOM), place in its group 1 .. 3, bits from the preamble match to the first bit}; MESSAGE {kind, bursts of the group
+ * so far}.  data: the text */
+typedef void (*nrsc5hip_same_cb)(void *opaque, int channel, int kind, long long first_bit, long long last_bit, const int32_t v[8], const uint8_t *data,
+                                 unsigned len);
+typedef struct nrsc5hip_same_info {
+    int32_t text_len;                    /* the last message; -1: none yet */
+    int32_t kind;                        /* NRSC5HIP_SAME_HEADER / _EOM, 0: none */
+    long long first_bit, last_bit;       /* of the burst that decided it; -1: none */
+    int32_t group_bursts, group_kind;    /* the current group */
+    int32_t in_message, pad;             /* the framer is inside a message */
+    uint8_t text[272];
+} nrsc5hip_same_info;
+/* bits, preamble matches, bursts complete, bursts aborted, groups with a message, groups without, end-of-message messages, seam drops, seam
+ * inserts, events */
+#define NRSC5HIP_SAME_NSTATS 10
+/* cfg NULL: burst events on.  Only before the first nrsc5hip_fm_process / nrsc5hip_chan_feed_fm of the object; nrsc5hip_fm_reset resets the
+ * SAME state as well */
+int  nrsc5hip_fm_same_enable(nrsc5hip_fm *fm, const nrsc5hip_same_config *cfg);
+/* the events appended since the last read, channel by channel, each channel's in order; -> events delivered, or < 0 */
+int  nrsc5hip_fm_same_read(nrsc5hip_fm *fm, nrsc5hip_same_cb cb, void *opaque);
+int  nrsc5hip_fm_same_get(nrsc5hip_fm *fm, int channel, nrsc5hip_same_info *out);
+int  nrsc5hip_fm_same_stats(nrsc5hip_fm *fm, int channel, long long stats[NRSC5HIP_SAME_NSTATS]);
+int  nrsc5hip_fm_same_info(nrsc5hip_fm *fm, int *table, int *points_per_bit, int *window_bits, long long *latency_in);   /* any pointer may be NULL */
+int  nrsc5hip_fm_same_table(nrsc5hip_fm *fm, float *cs /* [table][2]: cos, sin */);
+/* stage hook: n_in samples taken as a whole session from n = 0 -> on the host c [nchan][segments][4] (Re c_1, Im c_1, Re c_0, Im c_0), q
+ * [nchan][windows][512], the metrics [nchan][windows][8], s_w [nchan][windows], the decisions [nchan][windows][72] (one byte per bit) and
+ * their counts [nchan][windows], before any framing; segments = (400 (m + 1) - 1) / 35721 for m = (n_in + 1) / 2, windows =
+ * (segments - 7) / 512 (0 below 7).  Any pointer may be NULL.  The object's own session is not touched */
+int  nrsc5hip_stage_same_tones(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *c_out, float *q_out,
+                               float *metric_out, int32_t *s_out, uint8_t *bits_out, int32_t *counts_out);
+/* stage hook: bits (host, one byte each) fed straight to the framer of the listed channels (channels NULL: 0 .. n - 1); reset_at[i] (or NULL):
+ * channel i's framer and vote are reset in front of that bit of the call (nbits[i]: behind the last; -1: never).  Events come with
+ * nrsc5hip_fm_same_read */
+int  nrsc5hip_stage_same_frames(nrsc5hip_fm *fm, int n, const int *channels, const uint8_t *const *bits, const int *nbits, const int *reset_at);
 
 #ifdef __cplusplus
 }

@@ -286,5 +286,48 @@ def bind_steer(lib) -> None:
     lib.nrsc5hip_stage_fm_steer.argtypes = [vp, vp, ll, ll, vp]
 
 
+class _SameConfig(ctypes.Structure):
+    """nrsc5hip_same_config"""
+    _fields_ = [("burst_events", ctypes.c_int)]
+
+
+class SameInfo(ctypes.Structure):
+    """nrsc5hip_same_info"""
+    _fields_ = [("text_len", ctypes.c_int32), ("kind", ctypes.c_int32), ("first_bit", ctypes.c_longlong), ("last_bit", ctypes.c_longlong),
+                ("group_bursts", ctypes.c_int32), ("group_kind", ctypes.c_int32), ("in_message", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("text", ctypes.c_uint8 * 272)]
+
+
+assert ctypes.sizeof(SameInfo) == 312
+SAME_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int32),
+                           ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint)                                    # nrsc5hip_same_cb
+SAME_KINDS = (None, "burst", "message")                                                                 # NRSC5HIP_SAME_BURST / _MESSAGE
+SAME_BURST_KINDS = (None, "header", "eom")                                                              # NRSC5HIP_SAME_HEADER / _EOM
+SAME_STATS = ("bits", "preambles", "bursts", "bursts_aborted", "messages", "groups_no_message", "eom_messages", "seam_drops", "seam_inserts",
+              "events")                                                                                  # nrsc5hip_fm_same_stats
+SAME_TABLE, SAME_GRID, SAME_WIN_PTS, SAME_BITS_STRIDE, SAME_TEXT_MAX = 35721, 400, 512, 72, 268
+
+
+def same_segments(n_in: int) -> int:
+    """segments of the SAME grid that lie inside n_in input samples (nrsc5hip_stage_same_tones)"""
+    return (SAME_GRID * ((n_in + 1) // 2 + 1) - 1) // SAME_TABLE
+
+
+def bind_same(lib) -> None:
+    """argument types of EAS alerts (SAME) on the analog FM object (include/nrsc5hip.h, ABI 23)"""
+    vp, ci, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    lib.nrsc5hip_abi_version.restype = ci
+    if lib.nrsc5hip_abi_version() < 23:                    # an older library loaded for an A/B comparison: it has everything but these
+        return
+    lib.nrsc5hip_fm_same_enable.argtypes = [vp, ctypes.POINTER(_SameConfig)]
+    lib.nrsc5hip_fm_same_read.argtypes = [vp, SAME_CB, vp]
+    lib.nrsc5hip_fm_same_get.argtypes = [vp, ci, ctypes.POINTER(SameInfo)]
+    lib.nrsc5hip_fm_same_stats.argtypes = [vp, ci, vp]
+    lib.nrsc5hip_fm_same_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ll)]
+    lib.nrsc5hip_fm_same_table.argtypes = [vp, vp]
+    lib.nrsc5hip_stage_same_tones.argtypes = [vp, vp, ll, ll, vp, vp, vp, vp, vp, vp]
+    lib.nrsc5hip_stage_same_frames.argtypes = [vp, ci, vp, vp, vp, vp]
+
+
 class Nrsc5HipError(RuntimeError):
     pass

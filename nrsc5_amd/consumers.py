@@ -265,6 +265,47 @@ def rds_event_fields(kind: str, v, data: bytes) -> dict:
     raise ValueError(kind)
 
 
+def same_fields(text) -> dict | None:
+    """A SAME header ZCZC-ORG-EEE-PSSCCC(-PSSCCC ..)+TTTT-JJJHHMM-LLLLLLLL- as named fields: originator, event code, the location codes, purge time
+    in minutes (TTTT is hours and minutes), issue day of the year / hour / minute (UTC) and the sender; None for text that does not have the form
+    (the end of message NNNN included)"""
+    import re
+    if isinstance(text, (bytes, bytearray)):
+        text = bytes(text).decode("latin-1")
+    m = re.fullmatch(r"ZCZC-([A-Z]{3})-([A-Z0-9]{3})((?:-[0-9]{6}){1,31})\+([0-9]{4})-([0-9]{3})([0-9]{2})([0-9]{2})-([\x20-\x2c\x2e-\x7e]{8})-", text)
+    if not m:
+        return None
+    purge = int(m.group(4))
+    return {"originator": m.group(1), "event": m.group(2), "locations": m.group(3)[1:].split("-"), "purge_minutes": 60 * (purge // 100) + purge % 100,
+            "day": int(m.group(5)), "hour": int(m.group(6)), "minute": int(m.group(7)), "sender": m.group(8).rstrip(" ")}
+
+
+def same_event_fields(kind: str, v, data: bytes) -> dict:
+    """An event of k_same_frames as named fields: the text, its kind ("header" / "eom"), for a header its same_fields (None when it has not the
+    form), and the burst's place in its group / the bursts the group had when the message was decided"""
+    from .abi import SAME_BURST_KINDS
+    text = bytes(data).decode("latin-1")
+    out = {"text": text, "kind": SAME_BURST_KINDS[v[0]], "fields": same_fields(text) if v[0] == 1 else None, "bursts": v[1]}
+    if kind == "burst":
+        out["preamble_bits"] = v[2]
+    elif kind != "message":
+        raise ValueError(kind)
+    return out
+
+
+def same_line(text) -> str:
+    """what the command line prints for a message: `EAS WXR TOR 029095,029097 +0030 day 123 14:05 KXYZ/FM`, `EAS end of message`"""
+    if isinstance(text, (bytes, bytearray)):
+        text = bytes(text).decode("latin-1")
+    if text == "NNNN":
+        return "EAS end of message"
+    f = same_fields(text)
+    if f is None:
+        return "EAS " + text
+    return "EAS %s %s %s +%02d%02d day %03d %02d:%02d %s" % (f["originator"], f["event"], ",".join(f["locations"]), f["purge_minutes"] // 60,
+                                                             f["purge_minutes"] % 60, f["day"], f["hour"], f["minute"], f["sender"])
+
+
 def _sis_device_info(p) -> dict:
     """manufacturer id, versions and status of parameters 4..7 / 8..11 (pids.c:698-744)"""
     ver = lambda a, b: [(a >> 11) & 0x1f, (a >> 6) & 0x1f, (a >> 1) & 0x1f, b]

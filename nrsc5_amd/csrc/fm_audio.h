@@ -6,6 +6,7 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "rds.h"
+#include "same.h"
 #include "fm_carrier.h"
 
 namespace nrsc5 {
@@ -74,7 +75,7 @@ struct KeepArgs {
     const int *hist_old; int *hist_new;
 };
 
-// Where the launch_* functions of k_fm_audio.hip, k_fm_carrier.hip and k_rds.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
+// Where the launch_* functions of k_fm_audio.hip, k_fm_carrier.hip, k_rds.hip and k_same.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
 // for the length of a push (nrsc5hip_fm_debug_launches); nullptr anywhere else (the stage hooks are not counted)
 extern thread_local long long *launch_count;
 inline void count_launch() { if (launch_count) ++*launch_count; }
@@ -109,6 +110,7 @@ struct nrsc5hip_fm {
     long long launches = 0;                                  // kernel launches of the pushes since create / reset
     bool processed = false;                                  // a push has been launched since create
     nrsc5::RdsHost *rds = nullptr;                           // RDS (rds.hip), once enabled
+    nrsc5::SameHost *same = nullptr;                         // EAS alerts (same.hip), once enabled
     nrsc5::CarrierHost *carrier = nullptr;                   // carrier quality (fm_carrier.hip), once enabled
     bool steer = false;                                      // reception steering, once enabled: needs carrier
     nrsc5::fm::SteerRamps ramps = {};

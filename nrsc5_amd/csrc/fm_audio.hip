@@ -88,6 +88,7 @@ void free_fm(nrsc5hip_fm *f)
     for (int i = 0; i < 2; i++) { (void)hipFree(f->d_hist[i]); (void)hipFree(f->d_d[i]); (void)hipFree(f->d_p[i]); }
     (void)hipFree(f->d_clips); (void)hipFree(f->d_tab_n); (void)hipFree(f->d_steer);
     nrsc5::rds_free(f->rds);
+    nrsc5::same_free(f->same);
     nrsc5::carrier_free(f->carrier);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
@@ -103,6 +104,7 @@ int fm_zero_state(nrsc5hip_fm *f)
     HIPCHK(hipStreamSynchronize(f->stream));
     f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0; f->launches = 0;
     if (f->carrier) { const int rc = nrsc5::carrier_reset(f); if (rc) return rc; }
+    if (f->same) { const int rc = nrsc5::same_reset(f); if (rc) return rc; }
     return f->rds ? nrsc5::rds_reset(f) : 0;
 }
 
@@ -198,6 +200,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
         HIPCHK(hipGetLastError());
     }
     if (f->rds && (rc = nrsc5::rds_launch(f, s, d, c.m1))) return rc;
+    if (f->same && (rc = nrsc5::same_launch(f, s, d, c.m1))) return rc;
     if (c.b1 > f->blocks) {
         PilotArgs a;
         a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.cs = f->d_cs; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.j0 = f->blocks;
@@ -225,6 +228,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     if (d_base < 0) d_base = 0;
     if (p_base < 0) p_base = 0;
     if (f->rds && nrsc5::rds_d_need(f) < d_base) d_base = nrsc5::rds_d_need(f);     // ... and d from the first tap of the first grid point not yet summed
+    if (f->same && nrsc5::same_d_need(f) < d_base) d_base = nrsc5::same_d_need(f);  // ... and from the first SAME segment not yet summed
     KeepArgs k;
     k.d_old = d; k.d_new = f->d_d[f->cur ^ 1]; k.d_stride = f->d_cap; k.d_shift = d_base - f->d_base; k.d_count = c.m1 - d_base;
     k.p_old = p; k.p_new = f->d_p[f->cur ^ 1]; k.p_stride = f->p_cap; k.p_shift = p_base - f->p_base; k.p_count = c.b1 - p_base;

@@ -19,9 +19,9 @@ if _AB_LIB:
 
 from . import abi
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
-from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig, _FmSteerConfig
+from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig, _FmSteerConfig, _SameConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
-                        sis_utf8, sis_text, _sis_device_info, sis_event_fields, rds_text, rds_callsign, rds_event_fields, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
+                        sis_utf8, sis_text, _sis_device_info, sis_event_fields, rds_text, rds_callsign, rds_event_fields, same_fields, same_event_fields, same_line, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
 
 
 def l2_frame_to_dict(fr: L2Frame) -> dict:
@@ -189,6 +189,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     abi.bind_rds(lib)
     abi.bind_carrier(lib)
     abi.bind_steer(lib)
+    abi.bind_same(lib)
     lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_scan_destroy.argtypes = [vp]
     lib.nrsc5hip_scan_destroy.restype = None
@@ -228,7 +229,9 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_fm_debug_launches", "nrsc5hip_fm_rds_enable", "nrsc5hip_fm_rds_read", "nrsc5hip_fm_rds_get", "nrsc5hip_fm_rds_stats", "nrsc5hip_fm_rds_info", "nrsc5hip_fm_rds_taps",
     "nrsc5hip_stage_rds_mf", "nrsc5hip_stage_rds_groups",
     "nrsc5hip_fm_carrier_enable", "nrsc5hip_fm_carrier", "nrsc5hip_stage_fm_carrier", "nrsc5hip_scan_detect_fm_psd", "nrsc5hip_scan_detect_fm",
-    "nrsc5hip_fm_steer_enable", "nrsc5hip_fm_steer", "nrsc5hip_fm_steer_taps", "nrsc5hip_stage_fm_steer"]
+    "nrsc5hip_fm_steer_enable", "nrsc5hip_fm_steer", "nrsc5hip_fm_steer_taps", "nrsc5hip_stage_fm_steer",
+    "nrsc5hip_fm_same_enable", "nrsc5hip_fm_same_read", "nrsc5hip_fm_same_get", "nrsc5hip_fm_same_stats", "nrsc5hip_fm_same_info", "nrsc5hip_fm_same_table",
+    "nrsc5hip_stage_same_tones", "nrsc5hip_stage_same_frames"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -952,7 +955,8 @@ class FmDemod:
     AUDIO_RATE = FM_AUDIO_RATE
 
     def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None,
-                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2, carrier: bool = False, steer=False):
+                 rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2, carrier: bool = False, steer=False,
+                 same: bool = False, same_burst_events: bool = True):
         self.lib = load_library(lib_path)
         self.nchan, self.device, self.deemphasis_us = int(nchan), device, float(deemphasis_us)
         self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), (self.nchan,)))
@@ -965,7 +969,8 @@ class FmDemod:
         self.rds = False
         self.carrier_enabled = False
         self.steer_config = None
-        if rds or carrier or steer:
+        self.same = False
+        if rds or carrier or steer or same:
             try:
                 if rds:
                     self.rds_enable(rds_raw_groups, rds_correct_burst)
@@ -973,6 +978,8 @@ class FmDemod:
                     self.carrier_enable()
                 if steer:
                     self.steer_enable(**({} if steer is True else dict(steer)))
+                if same:
+                    self.same_enable(same_burst_events)
             except Nrsc5HipError:
                 self.close()                                       # the demodulator that was created goes with the failed constructor
                 raise
@@ -1039,6 +1046,65 @@ class FmDemod:
         ch = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
         rst = None if reset_at is None else np.ascontiguousarray(reset_at, dtype=np.int32)
         self._check(self.lib.nrsc5hip_stage_rds_groups(self._h, n, _ptr(ch), ptrs, counts.ctypes.data, _ptr(rst)))
+
+    # ---- EAS alerts (SAME) of the analog host (nrsc5hip_fm_same_*) ------------------------------------------------------------------
+    def same_enable(self, burst_events: bool = True):
+        """only before the first push; from then on every process() also watches every channel's audio for SAME bursts on the same stream"""
+        self._check(self.lib.nrsc5hip_fm_same_enable(self._h, ctypes.byref(_SameConfig(int(burst_events)))))
+        self.same = True
+        tb, ppb, wb, lat = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        self._check(self.lib.nrsc5hip_fm_same_info(self._h, ctypes.byref(tb), ctypes.byref(ppb), ctypes.byref(wb), ctypes.byref(lat)))
+        self.same_table_size, self.same_points_per_bit, self.same_window_bits, self.same_latency_in = tb.value, ppb.value, wb.value, lat.value
+
+    def same_read(self) -> list:
+        """the events since the last read -> [{"channel", "kind", "first", "last", "v", "data"}, ...], channel by channel, each channel's in order"""
+        out = []
+
+        def on_event(_opaque, channel, kind, first, last, v, data, n):
+            out.append({"channel": channel, "kind": SAME_KINDS[kind], "first": first, "last": last, "v": [int(v[k]) for k in range(8)], "data": ctypes.string_at(data, n)})
+
+        self._check(min(self.lib.nrsc5hip_fm_same_read(self._h, SAME_CB(on_event), None), 0))
+        return out
+
+    def same_get(self, channel: int) -> dict:
+        """the snapshot of one channel: the last message (None: none yet), its kind and bit indices, the bursts of the current group, in_message"""
+        info = SameInfo()
+        self._check(self.lib.nrsc5hip_fm_same_get(self._h, channel, ctypes.byref(info)))
+        return {"text": bytes(info.text[:info.text_len]) if info.text_len >= 0 else None, "kind": SAME_BURST_KINDS[info.kind], "first": info.first_bit,
+                "last": info.last_bit, "group_bursts": info.group_bursts, "group_kind": SAME_BURST_KINDS[info.group_kind], "in_message": int(info.in_message)}
+
+    def same_stats(self, channel: int) -> dict:
+        out = np.zeros(len(SAME_STATS), dtype=np.int64)
+        self._check(self.lib.nrsc5hip_fm_same_stats(self._h, channel, out.ctypes.data))
+        return dict(zip(SAME_STATS, (int(x) for x in out)))
+
+    def same_table(self) -> np.ndarray:
+        """float32 [35721][2]: (cos, sin) of 2 pi k / 35721 as stored"""
+        tab = np.zeros((self.same_table_size, 2), dtype=np.float32)
+        self._check(self.lib.nrsc5hip_fm_same_table(self._h, tab.ctypes.data))
+        return tab
+
+    def stage_same_tones(self, dev_in: int, in_stride_elems: int, n_in: int) -> dict:
+        """nrsc5hip_stage_same_tones -> {"c" complex64 [nchan][segments][2] (mark, space), "q" float32 [nchan][windows * 512], "metric" float32
+        [nchan][windows][8], "s" int32 [nchan][windows], "bits": per channel a list of uint8 arrays, one per window}"""
+        segs = same_segments(n_in)
+        nw = max(0, (segs - 7) // SAME_WIN_PTS)
+        c = np.zeros((self.nchan, segs, 2), dtype=np.complex64)
+        q, metric, s = np.zeros((self.nchan, nw * SAME_WIN_PTS), dtype=np.float32), np.zeros((self.nchan, nw, 8), dtype=np.float32), np.zeros((self.nchan, nw), dtype=np.int32)
+        bits, counts = np.zeros((self.nchan, nw, SAME_BITS_STRIDE), dtype=np.uint8), np.zeros((self.nchan, nw), dtype=np.int32)
+        self._check(self.lib.nrsc5hip_stage_same_tones(self._h, dev_in, in_stride_elems, n_in, c.ctypes.data, q.ctypes.data, metric.ctypes.data, s.ctypes.data,
+                                                       bits.ctypes.data, counts.ctypes.data))
+        return {"c": c, "q": q, "metric": metric, "s": s, "bits": [[bits[k, w, :counts[k, w]].copy() for w in range(nw)] for k in range(self.nchan)]}
+
+    def stage_same_frames(self, bits, channels=None, reset_at=None):
+        """nrsc5hip_stage_same_frames: bits[i] (uint8, one per bit) to the framer of channels[i] (default i); events come with same_read()"""
+        arrs = [np.ascontiguousarray(b, dtype=np.uint8) for b in bits]
+        n = len(arrs)
+        ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrs])
+        counts = np.array([a.size for a in arrs], dtype=np.int32)
+        ch = None if channels is None else np.ascontiguousarray(channels, dtype=np.int32)
+        rst = None if reset_at is None else np.ascontiguousarray(reset_at, dtype=np.int32)
+        self._check(self.lib.nrsc5hip_stage_same_frames(self._h, n, _ptr(ch), ptrs, counts.ctypes.data, _ptr(rst)))
 
     # ---- carrier quality of the analog host (nrsc5hip_fm_carrier*) -----------------------------------------------------------------
     def carrier_enable(self):

@@ -10,7 +10,11 @@ sum, no drift.  Pre-emphasis is applied as the tone's gain sqrt(1 + (2 pi f tau)
 
 RDS / RBDS (the keyword `rds`): a 57 kHz subcarrier, 3 x the pilot's phase (its ppm included) plus `phase`, carrying the biphase symbols of a
 repeating list of groups -- check words with the offset words, differential encoding, two impulses per bit shaped with the closed-form h(t) of
-the standard (RdsSignal).  That term alone is no sinusoid: its phase integral is a float64 Simpson sum (RdsSignal.phase_integral)."""
+the standard (RdsSignal).  That term alone is no sinusoid: its phase integral is a float64 Simpson sum (RdsSignal.phase_integral).
+
+EAS alerts (the keyword `same`): SAME bursts as mono AFSK on the sum path (SameSignal) -- 16 bytes 0xAB and the text, least significant bit
+first, mark 6250/3 Hz and space 1562.5 Hz at 3125/6 bit/s.  Every bit holds a whole number of tone cycles, so the tone restarts at each bit
+boundary without a step and its phase integral is closed form: whole bits contribute nothing."""
 from __future__ import annotations
 
 import numpy as np
@@ -32,8 +36,9 @@ def _tones(tones, preemph_us):
 
 
 class Terms(list):
-    """the MPX's sinusoids, with the RDS term beside them"""
+    """the MPX's sinusoids, with the RDS term and the SAME bursts beside them"""
     rds = None
+    same = None
 
 
 RDS_POLY = 0x5B9                                   # x^10 + x^8 + x^7 + x^5 + x^4 + x^3 + 1
@@ -137,6 +142,53 @@ class RdsSignal:
         return out
 
 
+SAME_BIT_HZ = 3125.0 / 6.0
+SAME_PREAMBLE = bytes([0xAB] * 16)
+
+
+def same_bits(text, preamble: bytes = SAME_PREAMBLE) -> np.ndarray:
+    """uint8 [8 * (16 + len(text))]: a SAME burst as transmitted, the preamble and then the text, every byte least significant bit first"""
+    raw = preamble + (text.encode("latin-1") if isinstance(text, str) else bytes(text))
+    return np.unpackbits(np.frombuffer(raw, dtype=np.uint8), bitorder="little")
+
+
+class SameSignal:
+    """level * sin(2 pi f_b (t - t_b)) inside bit b of a burst (f_b = 4 / T for a 1, 3 / T for a 0, t_b the bit's start), 0 between the bursts.
+    bursts: [(start_s, text), ...], not overlapping; T = 6 / 3125 s / (1 + clock_ppm 1e-6) -- the tones move with the bit clock, as they do in
+    an encoder that derives both from one oscillator.  preemph_us: each tone at its pre-emphasised level"""
+
+    def __init__(self, bursts, level=0.3, clock_ppm=0.0, preemph_us=None):
+        self.level, self.bit_hz = float(level), SAME_BIT_HZ * (1 + float(clock_ppm) * 1e-6)
+        self.bursts = [(float(t0), same_bits(text)) for t0, text in bursts]
+        g = lambda f: float(np.sqrt(1.0 + (2 * np.pi * f * preemph_us * 1e-6) ** 2)) if preemph_us else 1.0
+        self.gain = (g(3 * self.bit_hz), g(4 * self.bit_hz))            # space, mark
+        ends = [t0 + b.size / self.bit_hz for t0, b in self.bursts]
+        assert all(a <= t0 for a, (t0, _) in zip(ends, self.bursts[1:])), "bursts overlap"
+
+    def _tone(self, t: np.ndarray):
+        """-> (amplitude, frequency, time since the bit's start) of every t; amplitude 0 outside the bursts"""
+        t = np.asarray(t, dtype=np.float64)
+        amp, f, tau = np.zeros(t.shape), np.ones(t.shape), np.zeros(t.shape)
+        for t0, bits in self.bursts:
+            u = (t - t0) * self.bit_hz
+            k = np.floor(u).astype(np.int64)
+            on = (u >= 0) & (k < bits.size)
+            b = bits[np.clip(k, 0, bits.size - 1)]
+            amp = np.where(on, self.level * np.where(b == 1, self.gain[1], self.gain[0]), amp)
+            f = np.where(on, np.where(b == 1, 4.0, 3.0) * self.bit_hz, f)
+            tau = np.where(on, (u - k) / self.bit_hz, tau)
+        return amp, f, tau
+
+    def value(self, t: np.ndarray) -> np.ndarray:
+        amp, f, tau = self._tone(t)
+        return amp * np.sin(2 * np.pi * f * tau)
+
+    def phase_integral(self, t: np.ndarray) -> np.ndarray:
+        """integral of value() from 0 to t: the part of the bit t lies in, every whole bit integrating to zero"""
+        amp, f, tau = self._tone(t)
+        return amp / (2 * np.pi * f) * (1.0 - np.cos(2 * np.pi * f * tau))
+
+
 def rds_groups(pi: int, ps: str = "        ", text: str | None = None, clock=None, pty: int = 0, tp: int = 0, ta: int = 0, ms: int = 1, ab: int = 0,
                version_b: bool = False, extra=()) -> list:
     """a group schedule [(a, b, c, d), ...]: the four 0A (or 0B) groups of the name, then the text as 2A (2B) groups (ended by 0x0D when shorter
@@ -166,9 +218,10 @@ def rds_groups(pi: int, ps: str = "        ", text: str | None = None, clock=Non
     return out
 
 
-def mpx_terms(left, right, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.0, preemph_us=None, rds=None):
+def mpx_terms(left, right, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.0, preemph_us=None, rds=None, same=None):
     """-> [(amplitude, frequency Hz, phase)] of the MPX as a sum of a * sin(2 pi f t + phase) terms; with `rds` the list also carries the
-    RDS term as its attribute .rds (an RdsSignal), which mpx() and fm_phase() add"""
+    RDS term as its attribute .rds (an RdsSignal), with `same` = dict(bursts=[(start_s, text), ...], level=..) the SAME bursts as .same (a
+    SameSignal), which mpx() and fm_phase() add"""
     L, R = _tones(left, preemph_us), _tones(right, preemph_us)
     terms = []
     for sign_d, tones in ((1.0, L), (-1.0, R)):
@@ -183,6 +236,9 @@ def mpx_terms(left, right, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.0, preemph_us
     if rds is not None:
         terms = Terms(terms)
         terms.rds = RdsSignal(pilot_hz=PILOT_HZ * (1 + pilot_ppm * 1e-6), pilot_phase=pilot_phase, **rds)
+    if same is not None:
+        terms = terms if isinstance(terms, Terms) else Terms(terms)
+        terms.same = SameSignal(preemph_us=preemph_us, **same)
     return terms
 
 
@@ -194,6 +250,9 @@ def mpx(n: int, terms, fs: float = FS) -> np.ndarray:
     rds = getattr(terms, "rds", None)
     if rds is not None:
         out += rds.dev_hz / DEV_HZ * rds.value(t)
+    same = getattr(terms, "same", None)
+    if same is not None:
+        out += same.value(t)
     return out
 
 
@@ -206,12 +265,15 @@ def fm_phase(n: int, terms, fs: float = FS, dev_hz: float = DEV_HZ) -> np.ndarra
     rds = getattr(terms, "rds", None)
     if rds is not None:
         out += 2 * np.pi * dev_hz * (rds.dev_hz / DEV_HZ) * rds.phase_integral(n, fs)
+    same = getattr(terms, "same", None)
+    if same is not None:
+        out += 2 * np.pi * dev_hz * same.phase_integral(t)
     return out
 
 
-def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, amp=8000.0, cnr_db=None, seed=0, rds=None) -> np.ndarray:
+def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, amp=8000.0, cnr_db=None, seed=0, rds=None, same=None) -> np.ndarray:
     """int16 [n, 2]: the host as cs16 at 744 187.5 S/s.  cnr_db: white noise over the whole sampled band, carrier power / noise power"""
-    terms = mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds)
+    terms = mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds, same)
     x = amp * np.exp(1j * fm_phase(n, terms))
     if cnr_db is not None:
         rng = np.random.default_rng(seed)
@@ -223,6 +285,6 @@ def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3
     return out
 
 
-def fm_carrier(n: int, left=(), right=(), fs: float = FS, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, rds=None) -> np.ndarray:
+def fm_carrier(n: int, left=(), right=(), fs: float = FS, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, rds=None, same=None) -> np.ndarray:
     """complex128 [n]: the unit-amplitude host at any sample rate (for a wideband scene: scale, shift and add it)"""
-    return np.exp(1j * fm_phase(n, mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds), fs))
+    return np.exp(1j * fm_phase(n, mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds, same), fs))

@@ -15,6 +15,8 @@ DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets
 (44.1 kHz, 16 bit, stereo; --deemphasis 75, 50 or 0 us) and prints one `analog frames N` line per file at the end.
 --rds decodes RDS / RBDS of every station's analog host on the device and prints one line per report: `station 1 (+0.0 kHz): RDS PI 0x3AAB (KQED)`,
 `... RDS PS "KEXP-FM "`, `... RDS RT "..."`, `... RDS clock MJD 60310 13:37 UTC-07:00`.
+--eas watches every station's analog audio for Emergency Alert System bursts (SAME) on the device and prints one line per message:
+`station 1 (+0.0 kHz): EAS WXR TOR 029095,029097 +0030 day 123 14:05 KXYZ/FM`, `... EAS end of message`.
 --steer steers the analog audio by the reception of its own block -- stereo blend, high-cut, soft mute; --blend-db / --highcut-db / --mute-db LO,HI
 set the CNR thresholds and imply it -- and prints `station 1 (+0.0 kHz): reception blend 0.42 high-cut 1.00 mute 1.00`.
 --carrier measures every station's analog carrier on the device and prints `station 1 (+0.0 kHz): carrier -21.3 dBFS CNR 31.2 dB offset +0.41 kHz`
@@ -82,6 +84,11 @@ class WidebandReceiver:
     event (fields as eng.rds_event_fields) behind that station's other events of the push, and rds_info[s] is the station's snapshot
     (FmDemod.rds_get: pi, pty, flags, ps, rt, clock, synced).  A timing window of 152 bits is decided 96 431 input samples after its first
     sample is complete; there is no flush.
+    eas=True: the receiver also watches every station's analog audio for EAS alerts -- SAME headers and end-of-message bursts, demodulated, framed
+    and voted on the device (FmDemod(same=True); it creates the FmDemod if nothing else did, and audio is not collected then).  Every message
+    the three-burst vote produces becomes an ("eas", {"text", "kind": "header" / "eom", "fields": eng.same_fields or None, "bursts", "first",
+    "last"}) event returned by the push, and eas[s] keeps the station's messages so far; the logs are those of a receiver without it.  A window of
+    64 bits is decided 92 693 input samples after its first sample; there is no flush.
     carrier=True: the receiver also measures every station's analog carrier on the device (FmDemod(carrier=True); it creates the FmDemod if
     neither analog nor rds did).  carrier[s] is the station's snapshot after every push (FmDemod.carrier: the windowed and the running level_db,
     cnr_db, offset_hz and the sums behind them), and a ("carrier", {"level_db", "cnr_db", "offset_hz"}) event is returned by the push whenever the
@@ -95,7 +102,7 @@ class WidebandReceiver:
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
                  programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
                  lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None, rds: bool = False,
-                 carrier: bool = False, steer=False):
+                 carrier: bool = False, steer=False, eas: bool = False):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -134,9 +141,12 @@ class WidebandReceiver:
         self.on_audio = on_audio
         self.rds = bool(rds)
         self.carrier_enabled = bool(carrier)
+        self.eas_enabled = bool(eas)
+        self.eas = [[] for _ in range(self.k)]
         self.fm = None
-        if self.analog or self.rds or self.carrier_enabled:
+        if self.analog or self.rds or self.carrier_enabled or self.eas_enabled:
             self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path, **({"rds": True} if self.rds else {}),
+                                  **({"same": True, "same_burst_events": False} if self.eas_enabled else {}),
                                   **({"carrier": True} if self.carrier_enabled else {}), **({"steer": steer} if self.steer_enabled else {}))
         self.steer = [None] * self.k
         self._steer_side = [None] * self.k
@@ -270,6 +280,11 @@ class WidebandReceiver:
                 v = {"kind": e["kind"], **eng.rds_event_fields(e["kind"], e["v"], e["data"])}
                 self.logs[e["channel"]].append(("rds", v))
                 new[e["channel"]].append((e["channel"], "rds", v))
+        if self.eas_enabled:
+            for e in self.fm.same_read():                               # messages only: the bursts stay on the device
+                v = {**eng.same_event_fields(e["kind"], e["v"], e["data"]), "first": e["first"], "last": e["last"]}
+                self.eas[e["channel"]].append(v)
+                new[e["channel"]].append((e["channel"], "eas", v))
         if self.carrier_enabled:
             self._measure_carrier(new)
         if self.steer_enabled:
@@ -625,6 +640,8 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} carrier {v['level_db']:.1f} dBFS CNR {v['cnr_db']:.1f} dB offset {v['offset_hz'] / 1e3:+.2f} kHz"
     if kind == "steer":
         return f"{head} reception blend {v['blend']:.2f} high-cut {v['highcut']:.2f} mute {v['mute']:.2f}"
+    if kind == "eas":
+        return f"{head} " + eng.same_line(v["text"])
     if kind == "rds":
         if v["kind"] == "pi":
             return f"{head} RDS PI 0x{v['pi']:04X}" + (f" ({v['callsign']})" if v["callsign"] else "")
@@ -793,6 +810,7 @@ def main(argv=None) -> int:
                     help="write every station's analog FM programme as WAV (44.1 kHz, 16 bit, stereo): DIR/station<k>_<offset in Hz>_analog.wav")
     ap.add_argument("--deemphasis", type=float, default=75.0, choices=[75.0, 50.0, 0.0], help="de-emphasis of the analog audio in us (0: none)")
     ap.add_argument("--metadata", action="store_true", help="print what every program is playing (ID3 tags of the program service data)")
+    ap.add_argument("--eas", action="store_true", help="print the EAS alerts (SAME headers and end of message) in every station's analog audio, one line per message")
     ap.add_argument("--rds", action="store_true", help="print RDS / RBDS of every station's analog host: PI (and the call sign it encodes), name, RadioText, clock")
     ap.add_argument("--carrier", action="store_true", help="print level, CNR and centre error of every station's analog carrier whenever the CNR has moved by 1 dB")
     ap.add_argument("--steer", action="store_true", help="steer the analog audio by reception: stereo blend, high-cut and soft mute (with --dump-analog); prints "
@@ -851,7 +869,7 @@ def main(argv=None) -> int:
                 ap.error("a threshold pair is LO,HI")
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
                           data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis, rds=a.rds,
-                          carrier=a.carrier, steer=steer)
+                          carrier=a.carrier, steer=steer, eas=a.eas)
     wav = None
     if a.dump_analog is not None:
         wav = AnalogDump(a.dump_analog, offsets)
