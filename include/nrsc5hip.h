@@ -181,7 +181,7 @@ int nrsc5hip_stream_reset(nrsc5hip_engine *e, int stream);
 /* ABI NOTE (NRSC5HIP_ABI_VERSION >= 5): until round 4 nrsc5hip_stream_reset gave a FRESH session; since round 5 it is the reference's input_reset as described above (stale FIR
  * windows, samperr / angle / bc kept) and the fresh session is nrsc5hip_stream_fresh.  A caller that used reset to start an independent capture on a slot must call
  * nrsc5hip_stream_fresh now (on engines with batch_zero_copy both are the fresh form).  nrsc5hip_abi_version() lets a binding check what it was linked against. */
-#define NRSC5HIP_ABI_VERSION 23   /* 23: + EAS alerts (SAME) of the analog host (nrsc5hip_fm_same_enable, _same_read, _same_get, _same_stats, _same_info, _same_table, nrsc5hip_stage_same_tones, _stage_same_frames); 22: + reception steering of the analog FM audio (nrsc5hip_fm_steer_enable, nrsc5hip_fm_steer, nrsc5hip_fm_steer_taps, nrsc5hip_stage_fm_steer); 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
+#define NRSC5HIP_ABI_VERSION 24   /* 24: + reception impairments of the analog host (nrsc5hip_fm_impair_enable, nrsc5hip_fm_impair, nrsc5hip_fm_impair_taps, nrsc5hip_stage_fm_impair); 23: + EAS alerts (SAME) of the analog host (nrsc5hip_fm_same_enable, _same_read, _same_get, _same_stats, _same_info, _same_table, nrsc5hip_stage_same_tones, _stage_same_frames); 22: + reception steering of the analog FM audio (nrsc5hip_fm_steer_enable, nrsc5hip_fm_steer, nrsc5hip_fm_steer_taps, nrsc5hip_stage_fm_steer); 21: + carrier quality of the analog host (nrsc5hip_fm_carrier_enable, nrsc5hip_fm_carrier, nrsc5hip_stage_fm_carrier) and the analog-carrier detector (nrsc5hip_scan_detect_fm_psd, nrsc5hip_scan_detect_fm); 20: + nrsc5hip_stage_symbols; 19: + RDS of the analog host (nrsc5hip_fm_rds_*, nrsc5hip_stage_rds_mf, _stage_rds_groups), nrsc5hip_fm_debug_launches; 18: + nrsc5hip_stage_am_block, nrsc5hip_debug_fetch_am_sym; 17: + nrsc5hip_stage_nco_exact; 16: + analog FM audio (nrsc5hip_fm_*, nrsc5hip_stage_fm_mpx, nrsc5hip_chan_feed_fm); 15: + the data services (nrsc5hip_aas_*, nrsc5hip_stage_aas, _stage_aas_frames); 14: + SIS on the device (nrsc5hip_sis_*, nrsc5hip_stage_sis); 13: + the coarse-acquisition stage hooks (nrsc5hip_stage_acquire, _acquire_raw, _am_acquire); 12: + the PSD transport (nrsc5hip_psd_*, nrsc5hip_stage_psd); 11: + nrsc5hip_hdc_feed; 10: + nrsc5hip_batch_trim, NRSC5HIP_TRIM_RETAIN_MAX; 9: + the band scan (nrsc5hip_scan_*); 8: + the wideband channelizer (nrsc5hip_chan_*); 7: + NRSC5HIP_TUNE_HOST_CAPTURE / _FOLD_REPORT, nrsc5hip_debug_host_capture_stats; 6: + nrsc5hip_abi_version, nrsc5hip_debug_flow_stats, NRSC5HIP_TUNE_FLOW_MIN / _LOOP_EXACT, NRSC5HIP_PROF_FLOW; 5: the reset semantics above */
 int nrsc5hip_abi_version(void);
 /* nrsc5_close + nrsc5_open_pipe on this slot: a fresh session (calloc'd windows), what nrsc5hip_reset_all does for every stream */
 int nrsc5hip_stream_fresh(nrsc5hip_engine *e, int stream);
@@ -1326,6 +1326,98 @@ int  nrsc5hip_stage_same_tones(nrsc5hip_fm *fm, const int16_t *dev_in, long long
  * channel i's framer and vote are reset in front of that bit of the call (nbits[i]: behind the last; -1: never).  Events come with
  * nrsc5hip_fm_same_read */
 int  nrsc5hip_stage_same_frames(nrsc5hip_fm *fm, int n, const int *channels, const uint8_t *const *bits, const int *nbits, const int *reset_at);
+
+/* ---- reception impairments of the analog host (ABI 24): multipath and adjacent-channel detectors of every channel's FM carrier --------------
+ * Opt-in per analog FM object (nrsc5hip_fm_impair_enable; it enables the carrier measurement when that is off).  It then runs inside every
+ * nrsc5hip_fm_process / nrsc5hip_chan_feed_fm on the same stream, two launches per push that completes a block.  Notation of "carrier quality":
+ * blocks of 540 Fs1 samples, r[m] the envelope, d[m] the discriminator, win[w] the pilot's window as float32 (|w| <= 16).  Every quantity is a
+ * function of absolute sample indices, there is no recurrence and every sum has a stated order: any chunking of a session gives the same bits.
+ * With the measurement off nothing changes: not a byte of d, of the audio or of any report, not the launch count.
+ *   amplitude       e[m] = sqrtf(r[m] * r[m - 1]) in float32 (the product rounded to float32, then the square root), e[0] = 0: the modulus of
+ *                   z[m] conj z[m - 1], whose angle is d[m], so both signals sit at m - 1/2.  The square root is the correctly rounded one
+ *                   (IEEE 754 sqrt: the device's sqrtf under hipcc's default of correctly rounded float32 division and square root; the tests
+ *                   compare every e with the correctly rounded root of the library's own r, bit for bit)
+ *   multipath sums  for every complete block j, in double, with x = d[m], y = e[m], over m in [540 j, 540 j + 540): the eight sums of
+ *                   x, x2 = x x, x3 = x2 x, x4 = x2 x2, y, x y, x2 y, y y (x x, x y and y y are exact in double; the others round once per
+ *                   product); lane l of 64 takes m = 540 j + l + 64 i, i ascending, then an xor butterfly (32, 16, .. 1): the carrier triples' order
+ *   band-pass       hU: 63 taps, linear phase, hU[i] = (2 f2 sinc(2 f2 t) - 2 f1 sinc(2 f1 t)) kaiser(i; beta 8), t = i - 31, f1 = 100 kHz / Fs1,
+ *                   f2 = 170 kHz / Fs1, designed in double, stored as float32 (nrsc5hip_fm_impair_taps).  eu[m] = sum_i hU[i] e[m - i],
+ *                   du[m] = sum_i hU[i] d[m - i], each one float32 chain acc = fmaf(hU[i], e[m - i], acc) from acc = 0, i ascending; samples
+ *                   in front of the stream are zero
+ *   adjacent sums   per block, in double and in the order above: Cee = sum eu eu, Cdd = sum du du, Ced = sum eu du (every product exact)
+ *   windowed        of the last audio block delivered, ja: sum over |w| <= 16 of win[w] v[ja + w] for each of the eleven sums v, each product
+ *                   in double, blocks in front of the stream zero; lane w + 16 holds term w, then the butterfly.  count = the sum of the 33
+ *                   float32 window values in double, as in the carrier report
+ *   running         every complete block since create / reset, added one after the other in block order, in double; count = the blocks.  It
+ *                   includes block 0, where the channel filter turns on (x[n] = 0 for n < 0): a step of e and a jump of d that weigh on the
+ *                   running figures of a short session (an unmodulated carrier of 111 blocks reads a running explained of 0.56 at depth
+ *                   0.016 and a windowed one of exactly 0).  Judge reception by the windowed report; the verdict thresholds are set for it
+ *   figures         on the host, in double, from a set of sums and its count; every line is one statement, evaluated as written (no fused
+ *                   multiply-add), so that an implementation in IEEE double agrees bit for bit but for log10:
+ *                     n   = 540 count
+ *                     mx  = sx / n, m2 = sxx / n, m3 = sxxx / n, m4 = sxxxx / n, my = sy / n, mxy = sxy / n, mxxy = sxxy / n, myy = syy / n
+ *                     q   = mx mx
+ *                     u2  = m2 - q                                              the centred moments of x
+ *                     u3  = (m3 - (3 mx) m2) + (2 mx) q
+ *                     u4  = ((m4 - (4 mx) m3) + (6 q) m2) - (3 q) q
+ *                     cu  = mxy - mx my                                         cov(x - mx, y)
+ *                     cv  = ((mxxy - (2 mx) mxy) + q my) - u2 my                cov((x - mx)^2, y)
+ *                     k   = u4 - u2 u2
+ *                     det = u2 k - u3 u3                                        of the normal equations of y - my ~ b1 (x - mx) + b2 ((x - mx)^2 - u2)
+ *                     tot = myy - my my                                         total variance of y per sample
+ *                     b1  = (cu k - cv u3) / det,  b2 = (cv u2 - cu u3) / det
+ *                     res = tot - (b1 cu + b2 cv)                               residual variance per sample
+ *                     explained = min(1, max(0, 1 - res / tot))
+ *                     depth     = sqrt(max(0, tot - res)) / my                  rms of the fitted envelope variation over the mean envelope
+ *                     c2 = b2,  c1 = b1 - (2 b2) mx,  c0 = (my - b1 mx) + b2 (q - u2)      y ~ c0 + c1 x + c2 x^2
+ *                     slope     = c1 / c0  (per 75 kHz: x = 1 is 75 kHz),  curvature = c2 / c0;  both 0 unless c0 > 0
+ *                   no fit -- explained = depth = slope = curvature = 0 -- unless my > 0, tot > 0, u2 >= NRSC5HIP_FM_IMPAIR_MOD_MIN (an rms
+ *                   deviation of 75 Hz: an unmodulated carrier has no frequency to fit against) and det >= NRSC5HIP_FM_IMPAIR_MOD_MIN u2 u2 u2
+ *                   (a near-singular system; a Gaussian x has det = 2 u2^3, one tone 0.5 u2^3), and every intermediate is finite
+ *                     usn_db    = 10 log10(cdd / n)                             power of d in 100 .. 170 kHz ("ultrasonic noise"), 0 dB = 75 kHz rms
+ *                     ripple_db = 10 log10((cee / n) / (my my))                 power of e in that band over the squared mean amplitude
+ *                     rho       = ced / sqrt(cee cdd), clamped to [-1, 1]; 0 when cee or cdd is 0
+ *                   the dB figures are NRSC5HIP_FM_CARRIER_DB_MIN when their argument is not positive and are clamped to _MIN .. _MAX: never
+ *                   NaN, never infinite.  count = 0 (no block yet): every field 0
+ *   verdict         NRSC5HIP_FM_IMPAIR_MULTIPATH when explained >= explained_min and depth >= depth_min; NRSC5HIP_FM_IMPAIR_ADJACENT when
+ *                   |rho| >= rho_min, then side = +1 (rho > 0: the neighbour is above) or -1 (below), else side = 0.  Both can hold at once
+ * Why: multipath is frequency-selective fading, so the amplitude becomes a function of the instantaneous frequency; a neighbour on one side adds
+ * a beat that shows in the amplitude and in the frequency in phase (above) or in antiphase (below); white noise does neither.
+ * Limit: a neighbour's carrier, 200 kHz away, lies in the channel filter's stop band; what the detector sees is the part of the neighbour's spectrum
+ * that its own modulation swings below 129 kHz.  rho therefore grows with the neighbour's deviation as well as with its level: on the float64 model
+ * a neighbour 10 dB below the carrier reads |rho| 0.80 when modulated close to full deviation, 0.43 .. 0.50 -- under the default rho_min -- when
+ * modulated at about half of it, and 0.00 when silent, at any level.  A quiet or weak neighbour is missed; lower rho_min to trade this against
+ * false alarms (noise alone: |rho| <= 0.03 in the window of 33 blocks) */
+enum { NRSC5HIP_FM_IMPAIR_MULTIPATH = 1, NRSC5HIP_FM_IMPAIR_ADJACENT = 2 };
+#define NRSC5HIP_FM_IMPAIR_TAPS 63
+#define NRSC5HIP_FM_IMPAIR_NSUMS 11
+#define NRSC5HIP_FM_IMPAIR_MOD_MIN 1e-6
+typedef struct nrsc5hip_fm_impair_config {
+    double explained_min;                /* 0 .. 1; default 0.5 */
+    double depth_min;                    /* >= 0, finite; default 0.05 */
+    double rho_min;                      /* 0 .. 1; default 0.5 */
+} nrsc5hip_fm_impair_config;
+typedef struct nrsc5hip_fm_impair_report {
+    double sx, sxx, sxxx, sxxxx, sy, sxy, sxxy, syy, cee, cdd, ced, count;      /* the eleven sums and what they are divided by (in blocks) */
+    double explained, depth, slope, curvature, usn_db, ripple_db, rho;
+    int32_t verdict, side;               /* NRSC5HIP_FM_IMPAIR_* or'ed; +1, -1 or 0 */
+} nrsc5hip_fm_impair_report;
+typedef struct nrsc5hip_fm_impair_info {
+    nrsc5hip_fm_impair_report windowed, running;
+    long long blocks, audio_blocks;      /* complete blocks and audio blocks delivered since create / reset */
+} nrsc5hip_fm_impair_info;
+/* cfg NULL: the defaults.  Only before the first nrsc5hip_fm_process / nrsc5hip_chan_feed_fm of the object and only once; thresholds that are
+ * not finite or out of range are refused; nrsc5hip_fm_reset keeps it enabled and zeroes the totals */
+int  nrsc5hip_fm_impair_enable(nrsc5hip_fm *fm, const nrsc5hip_fm_impair_config *cfg);
+/* NRSC5HIP_EINVAL on an object without the measurement.  Only the two sets of sums per channel cross to the host */
+int  nrsc5hip_fm_impair(nrsc5hip_fm *fm, nrsc5hip_fm_impair_info *out /* [nchan] */);
+/* hU as stored; the measurement need not be enabled */
+int  nrsc5hip_fm_impair_taps(nrsc5hip_fm *fm, float *hu /* [NRSC5HIP_FM_IMPAIR_TAPS] */);
+/* stage hook: e, eu, du (host, each [nchan][540 blocks], blocks = ((n_in + 1) / 2) / 540: the samples of the complete blocks; any may be NULL)
+ * and the block sums (host, [nchan][blocks][11] in the order of nrsc5hip_fm_impair_report; may be NULL) of n_in samples taken as a whole session
+ * from n = 0; the object's own session is not touched, the measurement need not be enabled, and the launches are not counted */
+int  nrsc5hip_stage_fm_impair(nrsc5hip_fm *fm, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *e_out, float *eu_out,
+                              float *du_out, double *sums_out);
 
 #ifdef __cplusplus
 }

@@ -329,5 +329,42 @@ def bind_same(lib) -> None:
     lib.nrsc5hip_stage_same_frames.argtypes = [vp, ci, vp, vp, vp, vp]
 
 
+FM_IMPAIR_MULTIPATH, FM_IMPAIR_ADJACENT = 1, 2            # NRSC5HIP_FM_IMPAIR_*
+FM_IMPAIR_TAPS, FM_IMPAIR_NSUMS = 63, 11
+FM_IMPAIR_SUMS = ("sx", "sxx", "sxxx", "sxxxx", "sy", "sxy", "sxxy", "syy", "cee", "cdd", "ced")
+FM_IMPAIR_FIGURES = ("explained", "depth", "slope", "curvature", "usn_db", "ripple_db", "rho")
+FM_IMPAIR_DEFAULTS = dict(explained_min=0.5, depth_min=0.05, rho_min=0.5)
+
+
+class _FmImpairConfig(ctypes.Structure):
+    """nrsc5hip_fm_impair_config"""
+    _fields_ = [("explained_min", ctypes.c_double), ("depth_min", ctypes.c_double), ("rho_min", ctypes.c_double)]
+
+
+class FmImpairReport(ctypes.Structure):
+    """nrsc5hip_fm_impair_report"""
+    _fields_ = [(n, ctypes.c_double) for n in FM_IMPAIR_SUMS + ("count",) + FM_IMPAIR_FIGURES] + [("verdict", ctypes.c_int32), ("side", ctypes.c_int32)]
+
+
+class FmImpairInfo(ctypes.Structure):
+    """nrsc5hip_fm_impair_info"""
+    _fields_ = [("windowed", FmImpairReport), ("running", FmImpairReport), ("blocks", ctypes.c_longlong), ("audio_blocks", ctypes.c_longlong)]
+
+
+assert ctypes.sizeof(FmImpairInfo) == 336
+
+
+def bind_impair(lib) -> None:
+    """argument types of the reception impairments of the analog FM object (include/nrsc5hip.h, ABI 24)"""
+    vp, ll = ctypes.c_void_p, ctypes.c_longlong
+    lib.nrsc5hip_abi_version.restype = ctypes.c_int
+    if lib.nrsc5hip_abi_version() < 24:                    # an older library loaded for an A/B comparison: it has everything but these
+        return
+    lib.nrsc5hip_fm_impair_enable.argtypes = [vp, ctypes.POINTER(_FmImpairConfig)]
+    lib.nrsc5hip_fm_impair.argtypes = [vp, vp]
+    lib.nrsc5hip_fm_impair_taps.argtypes = [vp, vp]
+    lib.nrsc5hip_stage_fm_impair.argtypes = [vp, vp, ll, ll, vp, vp, vp, vp]
+
+
 class Nrsc5HipError(RuntimeError):
     pass

@@ -12,7 +12,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nrsc5_amd", "csrc")
-HIP_SOURCES = ["engine.hip", "engine_steps.hip", "engine_seam.hip", "engine_batch.hip", "engine_stage.hip", "k_decimate.hip", "k_acquire.hip", "k_mixfft.hip", "k_sync.hip", "k_pids_px.hip", "k_decode.hip", "k_replay.hip", "k_trim.hip", "k_am_decimate.hip", "k_am.hip", "k_am_decode.hip", "k_l2.hip", "hdc_consumer.hip", "k_psd.hip", "psd_consumer.hip", "k_sis.hip", "sis_consumer.hip", "k_aas.hip", "aas_consumer.hip", "k_channelize.hip", "k_scan.hip", "k_fm_audio.hip", "fm_audio.hip", "k_fm_carrier.hip", "fm_carrier.hip", "k_rds.hip", "rds.hip", "k_same.hip", "same.hip"]
+HIP_SOURCES = ["engine.hip", "engine_steps.hip", "engine_seam.hip", "engine_batch.hip", "engine_stage.hip", "k_decimate.hip", "k_acquire.hip", "k_mixfft.hip", "k_sync.hip", "k_pids_px.hip", "k_decode.hip", "k_replay.hip", "k_trim.hip", "k_am_decimate.hip", "k_am.hip", "k_am_decode.hip", "k_l2.hip", "hdc_consumer.hip", "k_psd.hip", "psd_consumer.hip", "k_sis.hip", "sis_consumer.hip", "k_aas.hip", "aas_consumer.hip", "k_channelize.hip", "k_scan.hip", "k_fm_audio.hip", "fm_audio.hip", "k_fm_carrier.hip", "fm_carrier.hip", "k_fm_impair.hip", "fm_impair.hip", "k_rds.hip", "rds.hip", "k_same.hip", "same.hip"]
 LIB = os.path.join(ROOT, "nrsc5_amd", "libnrsc5hip.so")
 EMU_LIB = os.path.join(ROOT, "tests", "simt", "libnrsc5hip_emu.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

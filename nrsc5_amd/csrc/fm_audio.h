@@ -8,6 +8,7 @@
 #include "rds.h"
 #include "same.h"
 #include "fm_carrier.h"
+#include "fm_impair.h"
 
 namespace nrsc5 {
 namespace fm {
@@ -75,7 +76,7 @@ struct KeepArgs {
     const int *hist_old; int *hist_new;
 };
 
-// Where the launch_* functions of k_fm_audio.hip, k_fm_carrier.hip, k_rds.hip and k_same.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
+// Where the launch_* functions of k_fm_audio.hip, k_fm_carrier.hip, k_fm_impair.hip, k_rds.hip and k_same.hip count themselves, one per kernel launch: fm_launch points it at its object's counter
 // for the length of a push (nrsc5hip_fm_debug_launches); nullptr anywhere else (the stage hooks are not counted)
 extern thread_local long long *launch_count;
 inline void count_launch() { if (launch_count) ++*launch_count; }
@@ -83,6 +84,9 @@ struct CountLaunches {
     explicit CountLaunches(long long *to) { launch_count = to; }
     ~CountLaunches() { launch_count = nullptr; }
 };
+
+double bessel_i0(double x);                   // the filter designs' Kaiser window and sinc, in double (fm_audio.hip)
+double sinc(double x);
 
 void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a);
 void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a);
@@ -112,6 +116,7 @@ struct nrsc5hip_fm {
     nrsc5::RdsHost *rds = nullptr;                           // RDS (rds.hip), once enabled
     nrsc5::SameHost *same = nullptr;                         // EAS alerts (same.hip), once enabled
     nrsc5::CarrierHost *carrier = nullptr;                   // carrier quality (fm_carrier.hip), once enabled
+    nrsc5::ImpairHost *impair = nullptr;                     // reception impairments (fm_impair.hip), once enabled: needs carrier
     bool steer = false;                                      // reception steering, once enabled: needs carrier
     nrsc5::fm::SteerRamps ramps = {};
     std::vector<float> tab_n;                                // the narrow table, host copy [PHASES][tb]

@@ -21,19 +21,6 @@ constexpr double EQ_F0 = 28000.0, EQ_F1 = 48000.0;                    // the dro
 constexpr int MAX_CHANNELS = 512;
 constexpr long long KEEP_MAX_BLOCKS = 2 * W + 3;
 
-double bessel_i0(double x)
-{
-    double s = 1.0, t = 1.0;
-    for (int k = 1; k < 500; k++) {
-        t *= (x / (2.0 * k)) * (x / (2.0 * k));
-        s += t;
-        if (t < 1e-18 * s) break;
-    }
-    return s;
-}
-
-double sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
-
 // Kaiser-windowed sinc, fc in cycles per sample, symmetric about (taps - 1) / 2
 std::vector<double> kaiser_lowpass(int taps, double fc, double att_db)
 {
@@ -90,6 +77,7 @@ void free_fm(nrsc5hip_fm *f)
     nrsc5::rds_free(f->rds);
     nrsc5::same_free(f->same);
     nrsc5::carrier_free(f->carrier);
+    nrsc5::impair_free(f->impair);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -104,6 +92,7 @@ int fm_zero_state(nrsc5hip_fm *f)
     HIPCHK(hipStreamSynchronize(f->stream));
     f->cur = 0; f->n_total = 0; f->m_total = 0; f->blocks = 0; f->audio_blocks = 0; f->d_base = 0; f->p_base = 0; f->launches = 0;
     if (f->carrier) { const int rc = nrsc5::carrier_reset(f); if (rc) return rc; }
+    if (f->impair) { const int rc = nrsc5::impair_reset(f); if (rc) return rc; }
     if (f->same) { const int rc = nrsc5::same_reset(f); if (rc) return rc; }
     return f->rds ? nrsc5::rds_reset(f) : 0;
 }
@@ -153,6 +142,19 @@ int fm_reserve(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1)
 
 thread_local long long *nrsc5::fm::launch_count = nullptr;
 
+double nrsc5::fm::bessel_i0(double x)
+{
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < 500; k++) {
+        t *= (x / (2.0 * k)) * (x / (2.0 * k));
+        s += t;
+        if (t < 1e-18 * s) break;
+    }
+    return s;
+}
+
+double nrsc5::fm::sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
+
 int nrsc5::fm_nchan(const nrsc5hip_fm *f) { return f->nchan; }
 int nrsc5::fm_device(const nrsc5hip_fm *f) { return f->device; }
 
@@ -179,8 +181,8 @@ int nrsc5::fm_check(nrsc5hip_fm *f, long long n_in, const int16_t *dev_out, long
     return 0;
 }
 
-// front, pilot sums, audio, the carrier sums and report (when enabled; steered, the sums in front of the audio) and the kept tails on `stream`; no
-// host wait (but for a buffer that has to grow)
+// front, pilot sums, audio, the carrier sums and report (when enabled; steered, the sums in front of the audio; the impairment sums and report
+// between the two) and the kept tails on `stream`; no host wait (but for a buffer that has to grow)
 int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long long in_stride, long long n_in, int16_t *out, long long out_stride)
 {
     if (n_in <= 0) return 0;
@@ -190,6 +192,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     int rc = fm_reserve(f, s, c.m1, c.b1);
     if (rc) return rc;
     if (f->carrier && (rc = nrsc5::carrier_reserve(f, s, c.m1, c.b1))) return rc;
+    if (f->impair && (rc = nrsc5::impair_reserve(f, s, c.b1))) return rc;
     float *d = f->d_d[f->cur]; float2 *p = f->d_p[f->cur];
     if (c.m1 > f->m_total) {
         FrontArgs a;
@@ -222,6 +225,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
         HIPCHK(hipGetLastError());
     }
     if (!f->steer && new_blocks && (rc = nrsc5::carrier_launch_sums(f, s, d, c.b1))) return rc;
+    if (f->impair && new_blocks && (rc = nrsc5::impair_launch(f, s, d, c.b1, c.a1))) return rc;       // reads this push's r: in front of its hand-over
     if (new_blocks && (rc = nrsc5::carrier_launch_report(f, s, c.m1, c.b1, c.a1))) return rc;
     // what the next call needs: d from the first tap of audio block a1, the block sums from a1 - W, the last HIST input samples
     long long d_base = (long long)BLOCK * c.a1 - f->tb - 1, p_base = c.a1 - W;

@@ -19,7 +19,7 @@ if _AB_LIB:
 
 from . import abi
 from .abi import *                                             # noqa: F401,F403  (every name of the ABI stays reachable as engine.<name>)
-from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig, _FmSteerConfig, _SameConfig
+from .abi import _Config, _ChanConfig, _ScanConfig, _FmConfig, _RdsConfig, _FmSteerConfig, _SameConfig, _FmImpairConfig
 from .consumers import (HdcConsumer, PsdConsumer, SisConsumer, feed_hdc, feed_hdc_batch, feed_psd_batch, feed_sis_batch,   # noqa: F401
                         sis_utf8, sis_text, _sis_device_info, sis_event_fields, rds_text, rds_callsign, rds_event_fields, same_fields, same_event_fields, same_line, AasConsumer, feed_aas_batch, aas_event_fields, aas_sig_table, aas_packets)
 
@@ -190,6 +190,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     abi.bind_carrier(lib)
     abi.bind_steer(lib)
     abi.bind_same(lib)
+    abi.bind_impair(lib)
     lib.nrsc5hip_scan_create.argtypes = [ctypes.POINTER(_ScanConfig), ctypes.POINTER(vp)]
     lib.nrsc5hip_scan_destroy.argtypes = [vp]
     lib.nrsc5hip_scan_destroy.restype = None
@@ -231,7 +232,8 @@ EXPORTED_SYMBOLS = [
     "nrsc5hip_fm_carrier_enable", "nrsc5hip_fm_carrier", "nrsc5hip_stage_fm_carrier", "nrsc5hip_scan_detect_fm_psd", "nrsc5hip_scan_detect_fm",
     "nrsc5hip_fm_steer_enable", "nrsc5hip_fm_steer", "nrsc5hip_fm_steer_taps", "nrsc5hip_stage_fm_steer",
     "nrsc5hip_fm_same_enable", "nrsc5hip_fm_same_read", "nrsc5hip_fm_same_get", "nrsc5hip_fm_same_stats", "nrsc5hip_fm_same_info", "nrsc5hip_fm_same_table",
-    "nrsc5hip_stage_same_tones", "nrsc5hip_stage_same_frames"]
+    "nrsc5hip_stage_same_tones", "nrsc5hip_stage_same_frames",
+    "nrsc5hip_fm_impair_enable", "nrsc5hip_fm_impair", "nrsc5hip_fm_impair_taps", "nrsc5hip_stage_fm_impair"]
 
 
 def library_sha(path: str | None = None) -> str:
@@ -956,7 +958,7 @@ class FmDemod:
 
     def __init__(self, nchan: int, deemphasis_us: float = 75.0, pilot_min: float = 0.0, gains=None, device: int = 0, lib_path: str | None = None,
                  rds: bool = False, rds_raw_groups: bool = False, rds_correct_burst: int = 2, carrier: bool = False, steer=False,
-                 same: bool = False, same_burst_events: bool = True):
+                 same: bool = False, same_burst_events: bool = True, impair=False):
         self.lib = load_library(lib_path)
         self.nchan, self.device, self.deemphasis_us = int(nchan), device, float(deemphasis_us)
         self.gains = None if gains is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gains, dtype=np.float32), (self.nchan,)))
@@ -970,7 +972,8 @@ class FmDemod:
         self.carrier_enabled = False
         self.steer_config = None
         self.same = False
-        if rds or carrier or steer or same:
+        self.impair_config = None
+        if rds or carrier or steer or same or impair:
             try:
                 if rds:
                     self.rds_enable(rds_raw_groups, rds_correct_burst)
@@ -980,6 +983,8 @@ class FmDemod:
                     self.steer_enable(**({} if steer is True else dict(steer)))
                 if same:
                     self.same_enable(same_burst_events)
+                if impair:
+                    self.impair_enable(**({} if impair is True else dict(impair)))
             except Nrsc5HipError:
                 self.close()                                       # the demodulator that was created goes with the failed constructor
                 raise
@@ -1165,6 +1170,48 @@ class FmDemod:
         out = np.zeros((self.nchan, max(0, ((n_in + 1) // 2) // 540 - 16), 4), dtype=np.float32)
         self._check(self.lib.nrsc5hip_stage_fm_steer(self._h, dev_in, in_stride_elems, n_in, out.ctypes.data))
         return out
+
+    # ---- reception impairments: multipath and adjacent-channel detectors (nrsc5hip_fm_impair*) ---------------------------------------------
+    def impair_enable(self, explained_min=None, depth_min=None, rho_min=None):
+        """only before the first push, and once; enables the carrier measurement when it is off.  No argument: the defaults (FM_IMPAIR_DEFAULTS)"""
+        cfg = dict(FM_IMPAIR_DEFAULTS)
+        for k, v in (("explained_min", explained_min), ("depth_min", depth_min), ("rho_min", rho_min)):
+            if v is not None:
+                cfg[k] = float(v)
+        c = _FmImpairConfig(cfg["explained_min"], cfg["depth_min"], cfg["rho_min"])
+        self._check(self.lib.nrsc5hip_fm_impair_enable(self._h, ctypes.byref(c)))
+        self.impair_config = cfg
+        self.carrier_enabled = True
+
+    def impair(self) -> list:
+        """one dict per channel: {"windowed": {...}, "running": {...}, "blocks", "audio_blocks"}; a report holds the figures "explained", "depth",
+        "slope", "curvature", "usn_db", "ripple_db", "rho", the verdict "multipath", "adjacent" (bool) and "side" (+1: the neighbour is above,
+        -1: below, 0: none), and the sums behind them, FM_IMPAIR_SUMS and "count" (windowed: of the last audio block delivered; running: since
+        create / reset)"""
+        out = (FmImpairInfo * self.nchan)()
+        self._check(self.lib.nrsc5hip_fm_impair(self._h, ctypes.addressof(out)))
+
+        def report(r):
+            v = {n: float(getattr(r, n)) for n in FM_IMPAIR_SUMS + ("count",) + FM_IMPAIR_FIGURES}
+            v.update(multipath=bool(r.verdict & FM_IMPAIR_MULTIPATH), adjacent=bool(r.verdict & FM_IMPAIR_ADJACENT), side=int(r.side))
+            return v
+
+        return [{"windowed": report(o.windowed), "running": report(o.running), "blocks": int(o.blocks), "audio_blocks": int(o.audio_blocks)} for o in out]
+
+    def impair_taps(self) -> np.ndarray:
+        """float32 [63]: the 100 .. 170 kHz band-pass hU as stored"""
+        hu = np.zeros(FM_IMPAIR_TAPS, dtype=np.float32)
+        self._check(self.lib.nrsc5hip_fm_impair_taps(self._h, hu.ctypes.data))
+        return hu
+
+    def stage_impair(self, dev_in: int, in_stride_elems: int, n_in: int) -> dict:
+        """nrsc5hip_stage_fm_impair -> {"e", "eu", "du" float32 [nchan][540 blocks], "sums" float64 [nchan][blocks][11] (FM_IMPAIR_SUMS)} of the
+        input taken as a whole session"""
+        nb = ((n_in + 1) // 2) // 540
+        e, eu, du = (np.zeros((self.nchan, 540 * nb), dtype=np.float32) for _ in range(3))
+        sums = np.zeros((self.nchan, nb, FM_IMPAIR_NSUMS), dtype=np.float64)
+        self._check(self.lib.nrsc5hip_stage_fm_impair(self._h, dev_in, in_stride_elems, n_in, e.ctypes.data, eu.ctypes.data, du.ctypes.data, sums.ctypes.data))
+        return {"e": e, "eu": eu, "du": du, "sums": sums}
 
     def close(self):
         if self._h:

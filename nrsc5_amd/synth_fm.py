@@ -256,9 +256,13 @@ def mpx(n: int, terms, fs: float = FS) -> np.ndarray:
     return out
 
 
-def fm_phase(n: int, terms, fs: float = FS, dev_hz: float = DEV_HZ) -> np.ndarray:
-    """2 pi dev * integral from 0 to t of the MPX, float64, closed form"""
+def fm_phase(n: int, terms, fs: float = FS, dev_hz: float = DEV_HZ, delay_s: float = 0.0) -> np.ndarray:
+    """2 pi dev * integral from 0 to t of the MPX, float64, closed form; delay_s: evaluated at t - delay_s (a delayed ray of a host of tones)"""
     t = np.arange(n, dtype=np.float64) / fs
+    if delay_s:
+        if getattr(terms, "rds", None) is not None or getattr(terms, "same", None) is not None:
+            raise ValueError("a delayed ray is available for hosts of tones only: not with rds or same")
+        t = t - delay_s
     out = np.zeros(n)
     for a, f, ph in terms:
         out += a * dev_hz / f * (np.cos(ph) - np.cos(2 * np.pi * f * t + ph))
@@ -271,10 +275,23 @@ def fm_phase(n: int, terms, fs: float = FS, dev_hz: float = DEV_HZ) -> np.ndarra
     return out
 
 
-def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, amp=8000.0, cnr_db=None, seed=0, rds=None, same=None) -> np.ndarray:
-    """int16 [n, 2]: the host as cs16 at 744 187.5 S/s.  cnr_db: white noise over the whole sampled band, carrier power / noise power"""
+def _with_rays(n: int, terms, fs: float, rays) -> np.ndarray:
+    """the unit-amplitude carrier plus a * exp(j (phase(t - tau) + phi)) per ray (a, tau_s, phi): the phase integral in closed form at the shifted
+    time; the rotation of the carrier itself over tau is part of phi"""
+    x = np.exp(1j * fm_phase(n, terms, fs))
+    for a, tau, phi in rays or ():
+        x = x + float(a) * np.exp(1j * (fm_phase(n, terms, fs, delay_s=float(tau)) + float(phi)))
+    return x
+
+
+def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, amp=8000.0, cnr_db=None, seed=0, rds=None, same=None,
+            rays=None) -> np.ndarray:
+    """int16 [n, 2]: the host as cs16 at 744 187.5 S/s.  cnr_db: white noise over the whole sampled band, power of the direct carrier / noise power.
+    rays: [(a, tau_s, phi), ...], delayed copies of relative amplitude a (multipath); hosts of tones only, refused together with rds / same"""
+    if rays and (rds is not None or same is not None):
+        raise ValueError("rays: hosts of tones only, not together with rds or same")
     terms = mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds, same)
-    x = amp * np.exp(1j * fm_phase(n, terms))
+    x = amp * _with_rays(n, terms, FS, rays)
     if cnr_db is not None:
         rng = np.random.default_rng(seed)
         s = amp * 10 ** (-cnr_db / 20) / np.sqrt(2)
@@ -285,6 +302,9 @@ def fm_host(n: int, left=(), right=(), pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3
     return out
 
 
-def fm_carrier(n: int, left=(), right=(), fs: float = FS, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, rds=None, same=None) -> np.ndarray:
-    """complex128 [n]: the unit-amplitude host at any sample rate (for a wideband scene: scale, shift and add it)"""
-    return np.exp(1j * fm_phase(n, mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds, same), fs))
+def fm_carrier(n: int, left=(), right=(), fs: float = FS, pilot=0.1, pilot_ppm=0.0, pilot_phase=0.3, preemph_us=None, rds=None, same=None, rays=None) -> np.ndarray:
+    """complex128 [n]: the unit-amplitude host at any sample rate (for a wideband scene: scale, shift and add it); rays as in fm_host (the direct
+    carrier keeps amplitude 1)"""
+    if rays and (rds is not None or same is not None):
+        raise ValueError("rays: hosts of tones only, not together with rds or same")
+    return _with_rays(n, mpx_terms(left, right, pilot, pilot_ppm, pilot_phase, preemph_us, rds, same), fs, rays)

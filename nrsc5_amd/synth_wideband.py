@@ -27,7 +27,7 @@ class Station:
     chan: object = None                  # channel.Impairments or None
     psd: bytes | None = None             # program 0's PSD byte stream (synth_torch.payload_stream), None: flag bytes only
     pids: object = None                  # the PIDS frames to transmit, cycled ([n, 80] bits, synth.sis_frame), None: reserved-id frames only
-    host: dict | None = None             # analog FM host in the middle of the station: synth_fm.fm_carrier's programme (left, right, pilot, preemph_us, rds, same, ...)
+    host: dict | None = None             # analog FM host in the middle of the station: synth_fm.fm_carrier's programme (left, right, pilot, preemph_us, rds, same, rays, ...)
     host_db: float = 20.0                # ... its carrier power over the total digital power, dB
     digital: bool = True                 # False: an analog-only station, the host alone at `level` (host_db has nothing to refer to)
 

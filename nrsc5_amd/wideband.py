@@ -19,6 +19,8 @@ DIR/station<k>_<offset in Hz>_p<program>.aac and prints one `program ... packets
 `station 1 (+0.0 kHz): EAS WXR TOR 029095,029097 +0030 day 123 14:05 KXYZ/FM`, `... EAS end of message`.
 --steer steers the analog audio by the reception of its own block -- stereo blend, high-cut, soft mute; --blend-db / --highcut-db / --mute-db LO,HI
 set the CNR thresholds and imply it -- and prints `station 1 (+0.0 kHz): reception blend 0.42 high-cut 1.00 mute 1.00`.
+--impair looks for the two impairments the CNR cannot tell apart and prints `station 1 (+0.0 kHz): reception multipath depth 0.30 (explained 0.88);
+adjacent upper rho +0.91 usn -42.5 dB`, or `reception clear`, with a station's first audio and whenever a verdict changes.
 --carrier measures every station's analog carrier on the device and prints `station 1 (+0.0 kHz): carrier -21.3 dBFS CNR 31.2 dB offset +0.41 kHz`
 whenever the CNR has moved by 1 dB; --scan-analog makes the scan find analog-only FM stations as well (the spectrum nominates carriers, a measurement
 of each one's CNR and centre error confirms them) and receives both kinds: `found +400.3 kHz analog score 18.8 dB carrier -54.7 dBFS CNR 15.3 dB ...`.
@@ -97,12 +99,17 @@ class WidebandReceiver:
     the reception of its own block -- stereo blend, high-cut and soft mute on the device (FmDemod(steer=...)); it implies analog=True.  steer[s] is
     the station's snapshot after every push (FmDemod.steer: q, blend, highcut, mute at the end of the last audio block), and a ("steer", {...})
     event is returned by the push with the station's first audio and whenever its blend crosses 0.5 or its mute crosses the midpoint of its range:
-    rare by design.  The logs are those of a receiver without steering."""
+    rare by design.  The logs are those of a receiver without steering.
+    impair=True (or a dict of FmDemod.impair_enable's thresholds: explained_min, depth_min, rho_min): the receiver also looks for the two impairments
+    that spoil an FM programme and that the CNR cannot tell apart -- multipath and a neighbour on one side -- on the device (FmDemod(impair=...)); it
+    implies analog=True.  impair[s] is the station's snapshot after every push (FmDemod.impair: the windowed and the running figures, verdicts and
+    sums), and an ("impair", {"multipath", "adjacent", "side", "explained", "depth", "rho", "usn_db", ...}) event of the windowed report is returned by
+    the push with the station's first audio and whenever a verdict bit changes.  The logs are those of a receiver without it."""
 
     def __init__(self, rate, fmt: str, offsets_hz, device: int = 0, gains=None, q15_capacity: int = 1 << 24, lib_path: str | None = None,
                  programs: bool = False, on_packet=None, metadata: bool = False, on_aas=None, sis: bool = False, data_services: bool = False,
                  lot_files: int = 16, on_file=None, analog: bool = False, deemphasis_us: float = 75.0, on_audio=None, rds: bool = False,
-                 carrier: bool = False, steer=False, eas: bool = False):
+                 carrier: bool = False, steer=False, eas: bool = False, impair=False):
         import torch
         self.fmt = eng.IQ_FORMATS[fmt]
         self.dtype = eng.IQ_DTYPES[self.fmt]
@@ -137,7 +144,8 @@ class WidebandReceiver:
         self.aas = [[] for _ in range(self.k)]
         self.sis = eng.SisConsumer(self.engine, self.k) if sis else None
         self.steer_enabled = bool(steer)
-        self.analog = bool(analog) or self.steer_enabled
+        self.impair_enabled = bool(impair)
+        self.analog = bool(analog) or self.steer_enabled or self.impair_enabled
         self.on_audio = on_audio
         self.rds = bool(rds)
         self.carrier_enabled = bool(carrier)
@@ -147,7 +155,10 @@ class WidebandReceiver:
         if self.analog or self.rds or self.carrier_enabled or self.eas_enabled:
             self.fm = eng.FmDemod(self.k, deemphasis_us=deemphasis_us, device=device, lib_path=lib_path, **({"rds": True} if self.rds else {}),
                                   **({"same": True, "same_burst_events": False} if self.eas_enabled else {}),
-                                  **({"carrier": True} if self.carrier_enabled else {}), **({"steer": steer} if self.steer_enabled else {}))
+                                  **({"carrier": True} if self.carrier_enabled else {}), **({"steer": steer} if self.steer_enabled else {}),
+                                  **({"impair": impair} if self.impair_enabled else {}))
+        self.impair = [None] * self.k
+        self._impair_said = [None] * self.k
         self.steer = [None] * self.k
         self._steer_side = [None] * self.k
         self.carrier = [None] * self.k
@@ -289,7 +300,22 @@ class WidebandReceiver:
             self._measure_carrier(new)
         if self.steer_enabled:
             self._measure_steer(new)
+        if self.impair_enabled:
+            self._measure_impair(new)
         return [ev for per in new for ev in per]
+
+    def _measure_impair(self, events):
+        """impair[s]: the snapshot after this push; an ("impair", {...}) event of the windowed report with the first audio and whenever a verdict bit
+        (multipath, adjacent, side) differs from the last one said (an event of the push only, as "carrier" is)"""
+        self.impair = self.fm.impair()
+        if not self._audio_seen:
+            return
+        for s, snap in enumerate(self.impair):
+            w = snap["windowed"]
+            said = (w["multipath"], w["adjacent"], w["side"])
+            if said != self._impair_said[s]:
+                self._impair_said[s] = said
+                events[s].append((s, "impair", {k: w[k] for k in ("multipath", "adjacent", "side") + eng.FM_IMPAIR_FIGURES}))
 
     def _measure_steer(self, events):
         """steer[s]: the snapshot after this push; a ("steer", {...}) event with the first audio and whenever the blend has crossed 0.5 or the mute
@@ -414,6 +440,13 @@ class FoundStation:
     carrier_offset_hz: float | None = None   # ... the carrier sits at offset_hz + carrier_offset_hz
     stereo: bool | None = None           # ... the pilot flag and level of the last audio block
     pilot: float | None = None
+    multipath: bool | None = None        # ... the two reception verdicts and their figures (FmDemod.impair), of the last audio block's window
+    adjacent: bool | None = None
+    adjacent_side: int | None = None     # +1: the neighbour is above, -1: below, 0: none
+    explained: float | None = None
+    depth: float | None = None
+    rho: float | None = None
+    usn_db: float | None = None
 
 
 def _device_samples(raw, fmt: int, device: int):
@@ -521,19 +554,24 @@ def survey_fm(raw, rate, fmt: str, *, seconds: float | None = None, nfft: int = 
 
 
 def measure_carriers(x, n: int, rate, code: int, centres, *, chunk: int = 1 << 22, device: int = 0, lib_path: str | None = None, rds: bool = False,
-                     seconds_rds: float | None = None):
+                     seconds_rds: float | None = None, impair: bool = False):
     """the first n samples of the device tensor x through a Channelizer at `centres` and an FmDemod(carrier=True) behind it, no engine
-    -> (FmDemod.carrier() snapshots, pilot levels, stereo flags, rds snapshots or None)"""
+    -> (FmDemod.carrier() snapshots, pilot levels, stereo flags, rds snapshots or None); impair=True: the same pass also runs the impairment
+    detectors, and every carrier snapshot carries FmDemod.impair()'s under the key "impair" """
     import torch
     ch = eng.Channelizer(rate, code, centres, device=device, lib_path=lib_path)
-    fm = eng.FmDemod(len(centres), device=device, lib_path=lib_path, carrier=True, rds=rds)
+    fm = eng.FmDemod(len(centres), device=device, lib_path=lib_path, carrier=True, rds=rds, impair=impair)
     try:
         for p in range(0, n, chunk):
             y = ch.process_tensor(x[2 * p:2 * min(n, p + chunk)])
             if y.shape[1]:
                 fm.process_tensor(y)
         level, flag = fm.pilot()
-        return fm.carrier(), level, flag, ([fm.rds_get(k) for k in range(len(centres))] if rds else None)
+        snaps = fm.carrier()
+        if impair:
+            for snap, v in zip(snaps, fm.impair()):
+                snap["impair"] = v
+        return snaps, level, flag, ([fm.rds_get(k) for k in range(len(centres))] if rds else None)
     finally:
         fm.close()
         ch.close()
@@ -560,12 +598,15 @@ def confirm_analog(raw, rate, fmt: str, found, *, confirm_seconds: float = CONFI
         first, _, _, _ = measure_carriers(x, n, rate, code, centres, chunk=chunk, device=device, lib_path=lib_path)
         centres = [c + v["running"]["offset_hz"] for c, v in zip(centres, first)]
     n2 = max(n, min(x.numel() // 2, int((NAME_SECONDS if name_seconds is None else name_seconds) * fs))) if names else n
-    snaps, level, flag, rds = measure_carriers(x, n2, rate, code, centres, chunk=chunk, device=device, lib_path=lib_path, rds=names)
+    snaps, level, flag, rds = measure_carriers(x, n2, rate, code, centres, chunk=chunk, device=device, lib_path=lib_path, rds=names, impair=True)
     kept = []
     for k, s in enumerate(cands):
         r = snaps[k]["running"]
         s.offset_hz = centres[k]
         s.cnr_db, s.level_db, s.carrier_offset_hz, s.stereo, s.pilot = r["cnr_db"], r["level_db"], r["offset_hz"], bool(flag[k]), float(level[k])
+        w = snaps[k]["impair"]["windowed"]
+        s.multipath, s.adjacent, s.adjacent_side = w["multipath"], w["adjacent"], w["side"]
+        s.explained, s.depth, s.rho, s.usn_db = w["explained"], w["depth"], w["rho"], w["usn_db"]
         if names and s.name is None and rds[k]["pi"] >= 0:
             s.name = eng.rds_callsign(rds[k]["pi"]) or (rds[k]["ps"].decode("latin-1").strip() if rds[k]["ps"] else None)
         if keep_all or (r["cnr_db"] >= min_cnr_db and abs(r["offset_hz"]) <= max_offset_hz):
@@ -612,6 +653,9 @@ def format_found(s: FoundStation) -> str:
     line += f" psmi {s.psmi}" if s.psmi is not None else ""
     if s.cnr_db is not None:
         line += f" carrier {s.level_db:.1f} dBFS CNR {s.cnr_db:.1f} dB offset {s.carrier_offset_hz / 1e3:+.2f} kHz {'stereo' if s.stereo else 'mono'}"
+    if s.multipath or s.adjacent:
+        line += " reception " + _impair_words(dict(multipath=s.multipath, adjacent=s.adjacent, side=s.adjacent_side, explained=s.explained, depth=s.depth,
+                                                   rho=s.rho, usn_db=s.usn_db))
     return line + (f" name {s.name}" if s.name is not None else "")
 
 
@@ -620,6 +664,16 @@ def write_spectrum_csv(path: str, freqs, psd):
         f.write("freq_hz,power_db\n")
         for fr, p in zip(freqs, psd):
             f.write(f"{fr:.3f},{10 * np.log10(max(p, 1e-30)):.3f}\n")
+
+
+def _impair_words(v: dict) -> str:
+    """`multipath depth 0.30 (explained 0.88); adjacent upper rho +0.91 usn -42.5 dB`, or `clear`"""
+    words = []
+    if v["multipath"]:
+        words.append(f"multipath depth {v['depth']:.2f} (explained {v['explained']:.2f})")
+    if v["adjacent"]:
+        words.append(f"adjacent {'upper' if v['side'] > 0 else 'lower'} rho {v['rho']:+.2f} usn {v['usn_db']:.1f} dB")
+    return "; ".join(words) or "clear"
 
 
 def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None:
@@ -640,6 +694,8 @@ def format_event(rx: WidebandReceiver, s: int, kind: str, v: dict) -> str | None
         return f"{head} carrier {v['level_db']:.1f} dBFS CNR {v['cnr_db']:.1f} dB offset {v['offset_hz'] / 1e3:+.2f} kHz"
     if kind == "steer":
         return f"{head} reception blend {v['blend']:.2f} high-cut {v['highcut']:.2f} mute {v['mute']:.2f}"
+    if kind == "impair":
+        return f"{head} reception " + _impair_words(v)
     if kind == "eas":
         return f"{head} " + eng.same_line(v["text"])
     if kind == "rds":
@@ -819,6 +875,8 @@ def main(argv=None) -> int:
     ap.add_argument("--blend-db", type=pair, metavar="LO,HI", default=None, help="CNR in dB where the stereo blend starts and where it is complete (18,30); implies --steer")
     ap.add_argument("--highcut-db", type=pair, metavar="LO,HI", default=None, help="CNR in dB where the high-cut is full and where it ends (10,20); implies --steer")
     ap.add_argument("--mute-db", type=pair, metavar="LO,HI", default=None, help="CNR in dB where the soft mute is at its floor and where it ends (2,8); implies --steer")
+    ap.add_argument("--impair", action="store_true", help="look for multipath and for a neighbour on one side in every station's analog carrier: prints "
+                    "`reception multipath depth D (explained E); adjacent upper rho R usn U dB` or `reception clear` with a station's first audio and when a verdict changes")
     ap.add_argument("--scan-analog", action="store_true", help="scan for analog-only FM stations as well as HD stations, and receive both")
     ap.add_argument("--sis", action="store_true", help="print who every station is: id, name, slogan, message, location, services, alerts; a scan then prints the call sign on every `found` line")
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -869,7 +927,7 @@ def main(argv=None) -> int:
                 ap.error("a threshold pair is LO,HI")
     rx = WidebandReceiver(rate, a.format, offsets, device=a.device, q15_capacity=a.q15_capacity, programs=a.dump_hdc is not None, metadata=a.metadata, sis=a.sis,
                           data_services=a.dump_aas_files is not None, analog=a.dump_analog is not None, deemphasis_us=a.deemphasis, rds=a.rds,
-                          carrier=a.carrier, steer=steer, eas=a.eas)
+                          carrier=a.carrier, steer=steer, eas=a.eas, impair=a.impair)
     wav = None
     if a.dump_analog is not None:
         wav = AnalogDump(a.dump_analog, offsets)
@@ -891,7 +949,7 @@ def main(argv=None) -> int:
                 line = format_event(rx, s, kind, v)
                 if line:
                     print(line, flush=True)
-            if wav is not None or steer:
+            if wav is not None or steer or a.impair:
                 for kept in rx.audio:                          # written and flushed by on_audio (or, steered without a dump, not wanted)
                     kept.clear()
             if dump is not None:
