@@ -1,5 +1,5 @@
-// Analog FM audio (include/nrsc5hip.h, "analog FM audio"): what the host unit (fm_audio.hip), the kernels (k_fm_audio.hip) and
-// the channelizer's feed (k_channelize.hip) share.
+// Analog FM audio (include/nrsc5hip.h, "analog FM audio"): what the host units (through fm_host.h, which holds the object itself),
+// the kernels (k_fm_audio.hip) and the channelizer's feed (k_channelize.hip) share: constants, the kernels' arguments and their launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,8 +85,7 @@ struct CountLaunches {
     ~CountLaunches() { launch_count = nullptr; }
 };
 
-double bessel_i0(double x);                   // the filter designs' Kaiser window and sinc, in double (fm_audio.hip)
-double sinc(double x);
+double bessel_i0(double x);                   // the filter designs' Kaiser window, in double (fm_audio.hip)
 
 void launch_front(hipStream_t s, int tiles, int nchan, const FrontArgs &a);
 void launch_pilot(hipStream_t s, int blocks, int nchan, const PilotArgs &a);
@@ -96,33 +95,6 @@ void launch_keep(hipStream_t s, int nchan, const KeepArgs &a);
 
 }  // namespace fm
 }  // namespace nrsc5
-
-struct nrsc5hip_fm {
-    int device = 0, nchan = 0, tb = 0;
-    double deemphasis_us = 75.0;
-    float pilot_min = 0.03f, aq = 0, bq = 0, wsum = 0;
-    std::vector<float> ha, tab, scale;                       // tab: host copy [PHASES][tb]
-    hipStream_t stream = nullptr;
-    float *d_ha = nullptr, *d_tab = nullptr, *d_win = nullptr, *d_scale = nullptr, *d_pilot = nullptr;
-    float2 *d_cs = nullptr;
-    int *d_hist[2] = {nullptr, nullptr};
-    float *d_d[2] = {nullptr, nullptr}; long long d_cap = 0, d_base = 0;     // d[m], m in [d_base, m_total), of channel c at d_d[cur][c * d_cap + m - d_base]
-    float2 *d_p[2] = {nullptr, nullptr}; long long p_cap = 0, p_base = 0;    // block sums [p_base, blocks)
-    int cur = 0;
-    unsigned long long *d_clips = nullptr;
-    long long n_total = 0, m_total = 0, blocks = 0, audio_blocks = 0;        // input samples, d samples, complete pilot blocks, audio blocks delivered
-    long long launches = 0;                                  // kernel launches of the pushes since create / reset
-    bool processed = false;                                  // a push has been launched since create
-    nrsc5::RdsHost *rds = nullptr;                           // RDS (rds.hip), once enabled
-    nrsc5::SameHost *same = nullptr;                         // EAS alerts (same.hip), once enabled
-    nrsc5::CarrierHost *carrier = nullptr;                   // carrier quality (fm_carrier.hip), once enabled
-    nrsc5::ImpairHost *impair = nullptr;                     // reception impairments (fm_impair.hip), once enabled: needs carrier
-    bool steer = false;                                      // reception steering, once enabled: needs carrier
-    nrsc5::fm::SteerRamps ramps = {};
-    std::vector<float> tab_n;                                // the narrow table, host copy [PHASES][tb]
-    float *d_tab_n = nullptr;
-    float4 *d_steer = nullptr;                               // [nchan]: (q, b, h, g) of the last audio block delivered
-};
 
 namespace nrsc5 {
 // for nrsc5hip_chan_feed_fm: the checks of nrsc5hip_fm_process without its launch, and the launch without a wait, on the caller's stream

@@ -1,5 +1,6 @@
-// Analog FM audio, host side (include/nrsc5hip.h, "analog FM audio"): the filter design in double, the object's buffers and the C ABI.
-// The kernels are in k_fm_audio.hip; the definition is DESIGN.md (o).
+// Analog FM audio, host side (include/nrsc5hip.h, "analog FM audio"): the filter design in double, the object's buffers, the push (fm_launch) and
+// the C ABI, reception steering included.  The kernels are in k_fm_audio.hip; the object and the plumbing the analog units share are in fm_host.h;
+// the definition is DESIGN.md (o).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -7,7 +8,7 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "host_util.h"
-#include "fm_audio.h"
+#include "fm_host.h"
 
 using namespace nrsc5::fm;
 
@@ -72,7 +73,7 @@ void free_fm(nrsc5hip_fm *f)
 {
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     (void)hipFree(f->d_ha); (void)hipFree(f->d_tab); (void)hipFree(f->d_win); (void)hipFree(f->d_scale); (void)hipFree(f->d_pilot); (void)hipFree(f->d_cs);
-    for (int i = 0; i < 2; i++) { (void)hipFree(f->d_hist[i]); (void)hipFree(f->d_d[i]); (void)hipFree(f->d_p[i]); }
+    (void)hipFree(f->d_hist[0]); (void)hipFree(f->d_hist[1]);
     (void)hipFree(f->d_clips); (void)hipFree(f->d_tab_n); (void)hipFree(f->d_steer);
     nrsc5::rds_free(f->rds);
     nrsc5::same_free(f->same);
@@ -105,37 +106,11 @@ Counts counts_after(const nrsc5hip_fm *f, long long n_in)
     return c;
 }
 
-// room for d[d_base, m1) and p[p_base, b1): grown once the work queued on `s` has finished; what is kept moves over
+// room for d[d_base, m1) and p[p_base, b1)
 int fm_reserve(nrsc5hip_fm *f, hipStream_t s, long long m1, long long b1)
 {
-    const long long need_d = m1 - f->d_base, need_p = b1 - f->p_base;
-    if (need_d > f->d_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        const long long cap = need_d + need_d / 4 + 4096;
-        float *nd[2] = {nullptr, nullptr};
-        HIPCHK(hipMalloc(&nd[0], sizeof(float) * (size_t)cap * f->nchan));
-        if (hipMalloc(&nd[1], sizeof(float) * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(nd[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (d, %lld per channel)", cap); }
-        const long long have = f->m_total - f->d_base;
-        if (have > 0)
-            HIPCHK(hipMemcpy2DAsync(nd[f->cur], sizeof(float) * cap, f->d_d[f->cur], sizeof(float) * f->d_cap, sizeof(float) * have, f->nchan, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        (void)hipFree(f->d_d[0]); (void)hipFree(f->d_d[1]);
-        f->d_d[0] = nd[0]; f->d_d[1] = nd[1]; f->d_cap = cap;
-    }
-    if (need_p > f->p_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        const long long cap = need_p + need_p / 4 + 64;
-        float2 *np[2] = {nullptr, nullptr};
-        HIPCHK(hipMalloc(&np[0], sizeof(float2) * (size_t)cap * f->nchan));
-        if (hipMalloc(&np[1], sizeof(float2) * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(np[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (pilot sums)"); }
-        const long long have = f->blocks - f->p_base;
-        if (have > 0)
-            HIPCHK(hipMemcpy2DAsync(np[f->cur], sizeof(float2) * cap, f->d_p[f->cur], sizeof(float2) * f->p_cap, sizeof(float2) * have, f->nchan, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        (void)hipFree(f->d_p[0]); (void)hipFree(f->d_p[1]);
-        f->d_p[0] = np[0]; f->d_p[1] = np[1]; f->p_cap = cap;
-    }
-    return 0;
+    const int rc = f->d.reserve(s, m1 - f->d_base, f->m_total - f->d_base, f->nchan, 1, 4096, f->cur, "d");
+    return rc ? rc : f->p.reserve(s, b1 - f->p_base, f->blocks - f->p_base, f->nchan, 1, 64, f->cur, "pilot sums");
 }
 
 }  // namespace
@@ -153,20 +128,16 @@ double nrsc5::fm::bessel_i0(double x)
     return s;
 }
 
-double nrsc5::fm::sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
-
 int nrsc5::fm_nchan(const nrsc5hip_fm *f) { return f->nchan; }
 int nrsc5::fm_device(const nrsc5hip_fm *f) { return f->device; }
 
-namespace {
-int fm_check_input(const nrsc5hip_fm *f, const void *dev_in, long long in_stride_elems, long long n_in)
+int nrsc5::fm_check_input(const nrsc5hip_fm *f, const void *dev_in, long long in_stride_elems, long long n_in)
 {
     if (n_in < 0 || (n_in > 0 && !dev_in)) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
     if (((uintptr_t)dev_in & 3) || (in_stride_elems & 1)) FAIL(NRSC5HIP_EINVAL, "input not aligned to 4 bytes (in_stride_elems %lld)", in_stride_elems);
     if (f->nchan > 1 && in_stride_elems < 2 * n_in) FAIL(NRSC5HIP_EINVAL, "in_stride_elems %lld < 2 * n_in %lld", in_stride_elems, n_in);
     return 0;
 }
-}  // namespace
 
 int nrsc5::fm_check(nrsc5hip_fm *f, long long n_in, const int16_t *dev_out, long long out_stride_elems, long long out_capacity, long long *n_out)
 {
@@ -193,11 +164,11 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     if (rc) return rc;
     if (f->carrier && (rc = nrsc5::carrier_reserve(f, s, c.m1, c.b1))) return rc;
     if (f->impair && (rc = nrsc5::impair_reserve(f, s, c.b1))) return rc;
-    float *d = f->d_d[f->cur]; float2 *p = f->d_p[f->cur];
+    float *d = f->d.p[f->cur]; float2 *p = f->p.p[f->cur];
     if (c.m1 > f->m_total) {
         FrontArgs a;
         a.in = dev_in; a.in_stride = in_stride; a.n0 = f->n_total; a.n_in = n_in; a.hist = f->d_hist[f->cur]; a.ha = f->d_ha;
-        a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.m0 = f->m_total; a.m_count = c.m1 - f->m_total;
+        a.d = d; a.d_stride = f->d.cap; a.d_base = f->d_base; a.m0 = f->m_total; a.m_count = c.m1 - f->m_total;
         if (f->carrier) { const nrsc5::FrontTarget t = nrsc5::carrier_front(f); a.r = t.r; a.r_stride = t.r_stride; a.r_base = t.r_base; }
         launch_front(s, (int)((a.m_count + FT - 1) / FT), f->nchan, a);
         HIPCHK(hipGetLastError());
@@ -206,7 +177,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     if (f->same && (rc = nrsc5::same_launch(f, s, d, c.m1))) return rc;
     if (c.b1 > f->blocks) {
         PilotArgs a;
-        a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.cs = f->d_cs; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.j0 = f->blocks;
+        a.d = d; a.d_stride = f->d.cap; a.d_base = f->d_base; a.cs = f->d_cs; a.p = p; a.p_stride = f->p.cap; a.p_base = f->p_base; a.j0 = f->blocks;
         launch_pilot(s, (int)(c.b1 - f->blocks), f->nchan, a);
         HIPCHK(hipGetLastError());
     }
@@ -214,7 +185,7 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     if (f->steer && new_blocks && (rc = nrsc5::carrier_launch_sums(f, s, d, c.b1))) return rc;      // steered: the audio reads the new blocks' triples
     if (c.a1 > f->audio_blocks) {
         SteeredAudioArgs a;
-        a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.p = p; a.p_stride = f->p_cap; a.p_base = f->p_base; a.cs = f->d_cs;
+        a.d = d; a.d_stride = f->d.cap; a.d_base = f->d_base; a.p = p; a.p_stride = f->p.cap; a.p_base = f->p_base; a.cs = f->d_cs;
         a.tab = f->d_tab; a.tb = f->tb; a.win = f->d_win; a.wsum = f->wsum; a.aq = f->aq; a.bq = f->bq; a.pilot_min = f->pilot_min; a.scale = f->d_scale;
         a.j0 = f->audio_blocks; a.k0 = BLOCK_OUT * f->audio_blocks; a.out = out; a.out_stride = out_stride; a.clips = f->d_clips; a.pilot = f->d_pilot;
         if (f->steer) {
@@ -234,8 +205,8 @@ int nrsc5::fm_launch(nrsc5hip_fm *f, hipStream_t s, const int16_t *dev_in, long 
     if (f->rds && nrsc5::rds_d_need(f) < d_base) d_base = nrsc5::rds_d_need(f);     // ... and d from the first tap of the first grid point not yet summed
     if (f->same && nrsc5::same_d_need(f) < d_base) d_base = nrsc5::same_d_need(f);  // ... and from the first SAME segment not yet summed
     KeepArgs k;
-    k.d_old = d; k.d_new = f->d_d[f->cur ^ 1]; k.d_stride = f->d_cap; k.d_shift = d_base - f->d_base; k.d_count = c.m1 - d_base;
-    k.p_old = p; k.p_new = f->d_p[f->cur ^ 1]; k.p_stride = f->p_cap; k.p_shift = p_base - f->p_base; k.p_count = c.b1 - p_base;
+    k.d_old = d; k.d_new = f->d.p[f->cur ^ 1]; k.d_stride = f->d.cap; k.d_shift = d_base - f->d_base; k.d_count = c.m1 - d_base;
+    k.p_old = p; k.p_new = f->p.p[f->cur ^ 1]; k.p_stride = f->p.cap; k.p_shift = p_base - f->p_base; k.p_count = c.b1 - p_base;
     k.in = dev_in; k.in_stride = in_stride; k.n0 = f->n_total; k.n_in = n_in; k.hist_old = f->d_hist[f->cur]; k.hist_new = f->d_hist[f->cur ^ 1];
     launch_keep(s, f->nchan, k);
     HIPCHK(hipGetLastError());
@@ -273,9 +244,9 @@ extern "C" int nrsc5hip_fm_create(const nrsc5hip_fm_config *cfg, nrsc5hip_fm **o
     }
     f->tab = audio_prototype(PASS_B, STOP_B, cfg->deemphasis_us, &f->tb);
     const std::vector<float> dev_tab = device_layout(f->tab, f->tb);
-    std::vector<float> win(2 * W + 1);
+    const std::vector<float> win = hann_window();
     double wsum = 0;
-    for (int w = -W; w <= W; w++) { const double v = 0.5 * (1 + cos(M_PI * w / (W + 1))); win[w + W] = (float)v; wsum += v; }
+    for (int w = -W; w <= W; w++) wsum += hann(w);           // of the window in double: what the audio kernel divides by
     f->wsum = (float)wsum;
     std::vector<float2> cs(PILOT_DEN);
     for (int k = 0; k < PILOT_DEN; k++) { const double t = 2 * M_PI * k / PILOT_DEN; cs[k] = make_float2((float)cos(t), (float)sin(t)); }
@@ -292,12 +263,8 @@ extern "C" int nrsc5hip_fm_create(const nrsc5hip_fm_config *cfg, nrsc5hip_fm **o
     CREATE_CHK(hipMalloc(&f->d_hist[0], sizeof(int) * HIST * f->nchan));
     CREATE_CHK(hipMalloc(&f->d_hist[1], sizeof(int) * HIST * f->nchan));
     CREATE_CHK(hipMalloc(&f->d_clips, sizeof(unsigned long long) * 2 * f->nchan));
-    f->d_cap = KEEP_MAX_BLOCKS * BLOCK + f->tb + 65536;
-    f->p_cap = KEEP_MAX_BLOCKS + 256;
-    for (int i = 0; i < 2; i++) {
-        CREATE_CHK(hipMalloc(&f->d_d[i], sizeof(float) * (size_t)f->d_cap * f->nchan));
-        CREATE_CHK(hipMalloc(&f->d_p[i], sizeof(float2) * (size_t)f->p_cap * f->nchan));
-    }
+    CREATE_CHK(f->d.alloc(KEEP_MAX_BLOCKS * BLOCK + f->tb + 65536, f->nchan));
+    CREATE_CHK(f->p.alloc(KEEP_MAX_BLOCKS + 256, f->nchan));
     CREATE_CHK(hipMemcpy(f->d_ha, f->ha.data(), sizeof(float) * TA, hipMemcpyHostToDevice));
     CREATE_CHK(hipMemcpy(f->d_tab, dev_tab.data(), sizeof(float) * dev_tab.size(), hipMemcpyHostToDevice));
     CREATE_CHK(hipMemcpy(f->d_win, win.data(), sizeof(float) * win.size(), hipMemcpyHostToDevice));
@@ -355,7 +322,7 @@ extern "C" int nrsc5hip_fm_process(nrsc5hip_fm *f, const int16_t *dev_in, long l
 {
     if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
     long long nout = 0;
-    int rc = fm_check_input(f, dev_in, in_stride_elems, n_in);
+    int rc = nrsc5::fm_check_input(f, dev_in, in_stride_elems, n_in);
     if (rc) return rc;
     rc = nrsc5::fm_check(f, n_in, dev_out, out_stride_elems, out_capacity, &nout);
     if (rc) return rc;
@@ -400,30 +367,21 @@ extern "C" int nrsc5hip_fm_pilot(nrsc5hip_fm *f, float *level, int *stereo)
 extern "C" int nrsc5hip_stage_fm_mpx(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *d_out, float *psum_out)
 {
     if (!f || !d_out) FAIL(NRSC5HIP_EINVAL, "null argument");
-    if (n_in <= 0) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
-    int rc = fm_check_input(f, dev_in, in_stride_elems, n_in);
-    if (rc) return rc;
-    const long long m1 = (n_in + 1) >> 1, b1 = m1 / BLOCK;
-    if ((m1 + FT - 1) / FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
     nrsc5::DeviceGuard guard(f->device);
-    nrsc5::DevTmp d, p, hist;
-    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * f->nchan));
+    StageFront sf;
+    const int rc = sf.open(f, dev_in, in_stride_elems, n_in, false);
+    if (rc) return rc;
+    const long long m1 = sf.m1, b1 = sf.b1;
+    nrsc5::DevTmp p;
     HIPCHK(hipMalloc(&p.p, sizeof(float2) * (size_t)(b1 + 1) * f->nchan));
-    HIPCHK(hipMalloc(&hist.p, sizeof(int) * HIST * f->nchan));
-    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * HIST * f->nchan, f->stream));
-    FrontArgs a;
-    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
-    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
-    launch_front(f->stream, (int)((m1 + FT - 1) / FT), f->nchan, a);
-    HIPCHK(hipGetLastError());
     if (b1 > 0) {
         PilotArgs q;
-        q.d = (const float *)d.p; q.d_stride = m1; q.d_base = 0; q.cs = f->d_cs; q.p = (float2 *)p.p; q.p_stride = b1; q.p_base = 0; q.j0 = 0;
+        q.d = sf.df(); q.d_stride = m1; q.d_base = 0; q.cs = f->d_cs; q.p = (float2 *)p.p; q.p_stride = b1; q.p_base = 0; q.j0 = 0;
         launch_pilot(f->stream, (int)b1, f->nchan, q);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(f->stream));
-    HIPCHK(hipMemcpy(d_out, d.p, sizeof(float) * (size_t)m1 * f->nchan, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(d_out, sf.d.p, sizeof(float) * (size_t)m1 * f->nchan, hipMemcpyDeviceToHost));
     if (psum_out && b1 > 0) HIPCHK(hipMemcpy(psum_out, p.p, sizeof(float2) * (size_t)b1 * f->nchan, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -451,9 +409,7 @@ bool steer_ramp_of(const double db[2], float *lo, float *inv)
 
 extern "C" int nrsc5hip_fm_steer_enable(nrsc5hip_fm *f, const nrsc5hip_fm_steer_config *cfg)
 {
-    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
-    if (f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is enabled already");
-    if (f->processed) FAIL(NRSC5HIP_EINVAL, "reception steering can be enabled only before the first push");
+    FM_ENABLE_CHECK(f, f->steer, "reception steering");
     nrsc5hip_fm_steer_config c = {NRSC5HIP_FM_STEER_ALL, {18.0, 30.0}, {10.0, 20.0}, {2.0, 8.0}, -20.0};
     if (cfg) c = *cfg;
     if (c.controls & ~(unsigned)NRSC5HIP_FM_STEER_ALL) FAIL(NRSC5HIP_EINVAL, "controls 0x%x: unknown bits", c.controls);
@@ -484,9 +440,8 @@ extern "C" int nrsc5hip_fm_steer_enable(nrsc5hip_fm *f, const nrsc5hip_fm_steer_
 extern "C" int nrsc5hip_fm_steer(nrsc5hip_fm *f, nrsc5hip_fm_steer_info *out)
 {
     if (!f || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
-    if (!f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is not enabled on this object");
+    FM_FEATURE_ENTER(f, steer, "reception steering");
     static_assert(sizeof(nrsc5hip_fm_steer_info) == sizeof(float4), "the device writes (q, b, h, g) as one float4");
-    nrsc5::DeviceGuard guard(f->device);
     HIPCHK(hipStreamSynchronize(f->stream));
     HIPCHK(hipMemcpy(out, f->d_steer, sizeof(float4) * f->nchan, hipMemcpyDeviceToHost));
     return 0;
@@ -495,7 +450,7 @@ extern "C" int nrsc5hip_fm_steer(nrsc5hip_fm *f, nrsc5hip_fm_steer_info *out)
 extern "C" int nrsc5hip_fm_steer_taps(nrsc5hip_fm *f, float *audio_narrow)
 {
     if (!f || !audio_narrow) FAIL(NRSC5HIP_EINVAL, "null argument");
-    if (!f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is not enabled on this object");
+    FM_FEATURE_ENTER(f, steer, "reception steering");
     memcpy(audio_narrow, f->tab_n.data(), sizeof(float) * f->tab_n.size());
     return 0;
 }
@@ -503,44 +458,32 @@ extern "C" int nrsc5hip_fm_steer_taps(nrsc5hip_fm *f, float *audio_narrow)
 extern "C" int nrsc5hip_stage_fm_steer(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *out)
 {
     if (!f || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
-    if (!f->steer) FAIL(NRSC5HIP_EINVAL, "reception steering is not enabled on this object");
-    if (n_in <= 0) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
-    int rc = fm_check_input(f, dev_in, in_stride_elems, n_in);
+    FM_FEATURE_ENTER(f, steer, "reception steering");
+    StageFront sf;
+    const int rc = sf.open(f, dev_in, in_stride_elems, n_in, true, W + 1);
     if (rc) return rc;
-    const long long m1 = (n_in + 1) >> 1, b1 = m1 / BLOCK, a1 = b1 > W ? b1 - W : 0;
-    if ((m1 + FT - 1) / FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
-    if (a1 == 0) return 0;
+    const long long m1 = sf.m1, b1 = sf.b1, a1 = b1 > W ? b1 - W : 0;
+    if (a1 == 0) return 0;                                   // no audio block
     const size_t K = (size_t)f->nchan;
-    nrsc5::DeviceGuard guard(f->device);
-    nrsc5::DevTmp d, r, p, t, hist, pcm, fac, clips, pilot;
-    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * K));
-    HIPCHK(hipMalloc(&r.p, sizeof(float) * (size_t)m1 * K));
+    nrsc5::DevTmp p, t, pcm, fac, clips, pilot;
     HIPCHK(hipMalloc(&p.p, sizeof(float2) * (size_t)b1 * K));
     HIPCHK(hipMalloc(&t.p, sizeof(double) * 3 * (size_t)b1 * K));
-    HIPCHK(hipMalloc(&hist.p, sizeof(int) * HIST * K));
     HIPCHK(hipMalloc(&pcm.p, sizeof(int16_t) * 2 * BLOCK_OUT * (size_t)a1 * K));
     HIPCHK(hipMalloc(&fac.p, sizeof(float4) * (size_t)a1 * K));
     HIPCHK(hipMalloc(&clips.p, sizeof(unsigned long long) * 2 * K));
     HIPCHK(hipMalloc(&pilot.p, sizeof(float) * 2 * K));
-    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * HIST * K, f->stream));
     HIPCHK(hipMemsetAsync(clips.p, 0, sizeof(unsigned long long) * 2 * K, f->stream));
-    FrontArgs a;
-    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
-    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
-    a.r = (float *)r.p; a.r_stride = m1; a.r_base = 0;
-    launch_front(f->stream, (int)((m1 + FT - 1) / FT), f->nchan, a);
-    HIPCHK(hipGetLastError());
     PilotArgs q;
-    q.d = (const float *)d.p; q.d_stride = m1; q.d_base = 0; q.cs = f->d_cs; q.p = (float2 *)p.p; q.p_stride = b1; q.p_base = 0; q.j0 = 0;
+    q.d = sf.df(); q.d_stride = m1; q.d_base = 0; q.cs = f->d_cs; q.p = (float2 *)p.p; q.p_stride = b1; q.p_base = 0; q.j0 = 0;
     launch_pilot(f->stream, (int)b1, f->nchan, q);
     HIPCHK(hipGetLastError());
     CarrierArgs c;
-    c.r = (const float *)r.p; c.r_stride = m1; c.r_base = 0; c.d = (const float *)d.p; c.d_stride = m1; c.d_base = 0;
+    c.r = sf.rf(); c.r_stride = m1; c.r_base = 0; c.d = sf.df(); c.d_stride = m1; c.d_base = 0;
     c.t = (double *)t.p; c.t_stride = b1; c.t_base = 0; c.j0 = 0;
     launch_carrier(f->stream, (int)b1, f->nchan, c);
     HIPCHK(hipGetLastError());
     SteeredAudioArgs u;
-    u.d = (const float *)d.p; u.d_stride = m1; u.d_base = 0; u.p = (const float2 *)p.p; u.p_stride = b1; u.p_base = 0; u.cs = f->d_cs;
+    u.d = sf.df(); u.d_stride = m1; u.d_base = 0; u.p = (const float2 *)p.p; u.p_stride = b1; u.p_base = 0; u.cs = f->d_cs;
     u.tab = f->d_tab; u.tb = f->tb; u.win = f->d_win; u.wsum = f->wsum; u.aq = f->aq; u.bq = f->bq; u.pilot_min = f->pilot_min; u.scale = f->d_scale;
     u.j0 = 0; u.k0 = 0; u.out = (int16_t *)pcm.p; u.out_stride = 2 * BLOCK_OUT * a1; u.clips = (unsigned long long *)clips.p; u.pilot = (float *)pilot.p;
     u.t = (const double *)t.p; u.t_stride = b1; u.t_base = 0; u.tab_n = f->d_tab_n; u.ramps = f->ramps;

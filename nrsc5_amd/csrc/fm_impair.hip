@@ -1,6 +1,7 @@
 // Reception impairments of the analog host, host side (include/nrsc5hip.h, "reception impairments"): the band-pass design in
 // double, the buffers an analog FM object gains with nrsc5hip_fm_impair_enable, the two launches fm_launch chains behind the carrier sums, the
-// figures and the verdict formed from the sums, and the stage hook.  The kernels are in k_fm_impair.hip.
+// figures and the verdict formed from the sums, and the stage hook.  The kernels are in k_fm_impair.hip; the records' buffer that grows, the hook's
+// opening and the dB clamp are fm_host.h's.
 //   per push, host -> device: nothing (the launches carry their arguments)
 //   per nrsc5hip_fm_impair, device -> host: 176 bytes per channel (the two sets of eleven sums)
 #include <hip/hip_runtime.h>
@@ -10,20 +11,20 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "host_util.h"
-#include "fm_audio.h"
+#include "fm_host.h"
 
 using namespace nrsc5;
 using namespace nrsc5::fm;
 
 struct nrsc5::ImpairHost {
-    double *d_t[2] = {nullptr, nullptr}; long long t_cap = 0, t_base = 0;   // block records [t_base, blocks) at d_t[cur][NS * (c * t_cap + j - t_base)]
+    PingPong<double> t; long long t_base = 0;                     // block records [t_base, blocks) at t.p[cur][NS * (c * t.cap + j - t_base)]
     int cur = 0;
     double *d_report = nullptr;                                   // [nchan][2 NS]
     float *d_tail = nullptr;                                      // [nchan][R_TAIL]: r[540 blocks - R_TAIL, 540 blocks)
     float *d_hu = nullptr;                                        // [UT]
     nrsc5hip_fm_impair_config cfg = {0.5, 0.05, 0.5};
     double wsum = 0;                                              // sum of the window as the device reads it: the windowed report's count
-    ~ImpairHost() { for (int i = 0; i < 2; i++) (void)hipFree(d_t[i]); (void)hipFree(d_report); (void)hipFree(d_tail); (void)hipFree(d_hu); }
+    ~ImpairHost() { (void)hipFree(d_report); (void)hipFree(d_tail); (void)hipFree(d_hu); }
 };
 
 namespace {
@@ -33,7 +34,7 @@ constexpr double FS1 = 744187.5 / 2, EDGE_LO = 100e3, EDGE_HI = 170e3, BETA = 8.
 // hU as stored: designed once; the getter, the enabled object's device table and the stage hook all read this one table
 const std::vector<float> &hu_table();
 
-// Kaiser-windowed difference of two sincs, symmetric about tap 31
+// Kaiser-windowed difference of two sincs, symmetric about tap 31 (the window's end taps are 1 / I0(beta), not fm_audio.hip's design)
 std::vector<float> design_hu()
 {
     const double f1 = EDGE_LO / FS1, f2 = EDGE_HI / FS1, i0b = bessel_i0(BETA);
@@ -50,12 +51,6 @@ const std::vector<float> &hu_table()
 {
     static const std::vector<float> h = design_hu();
     return h;
-}
-
-double clamp_db(double v)
-{
-    const double lo = NRSC5HIP_FM_CARRIER_DB_MIN, hi = NRSC5HIP_FM_CARRIER_DB_MAX;
-    return !(v >= lo) ? lo : v > hi ? hi : v;
 }
 
 // the figures and the verdict of one set of sums, line by line as include/nrsc5hip.h states them
@@ -121,21 +116,7 @@ int nrsc5::impair_reset(nrsc5hip_fm *f)
 int nrsc5::impair_reserve(nrsc5hip_fm *f, hipStream_t s, long long b1)
 {
     ImpairHost *P = f->impair;
-    const long long need_t = b1 - P->t_base;
-    if (need_t > P->t_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        const long long cap = need_t + need_t / 4 + 64;
-        double *nt[2] = {nullptr, nullptr};
-        HIPCHK(hipMalloc(&nt[0], sizeof(double) * NS * (size_t)cap * f->nchan));
-        if (hipMalloc(&nt[1], sizeof(double) * NS * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(nt[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (impairment sums)"); }
-        const long long have = f->blocks - P->t_base;
-        if (have > 0)
-            HIPCHK(hipMemcpy2DAsync(nt[P->cur], sizeof(double) * NS * cap, P->d_t[P->cur], sizeof(double) * NS * P->t_cap, sizeof(double) * NS * have, f->nchan, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        (void)hipFree(P->d_t[0]); (void)hipFree(P->d_t[1]);
-        P->d_t[0] = nt[0]; P->d_t[1] = nt[1]; P->t_cap = cap;
-    }
-    return 0;
+    return P->t.reserve(s, b1 - P->t_base, f->blocks - P->t_base, f->nchan, NS, 64, P->cur, "impairment sums");
 }
 
 int nrsc5::impair_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long b1, long long a1)
@@ -146,13 +127,13 @@ int nrsc5::impair_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long lon
     if (f->d_base > (first > 0 ? first : 0)) FAIL(NRSC5HIP_EHIP, "internal: d is kept from %lld, the impairment sums read from %lld", f->d_base, first);
     ImpairArgs a;
     a.r = r.r; a.r_stride = r.r_stride; a.r_base = r.r_base; a.r_tail = P->d_tail;
-    a.d = d; a.d_stride = f->d_cap; a.d_base = f->d_base; a.hu = P->d_hu;
-    a.t = P->d_t[P->cur]; a.t_stride = P->t_cap; a.t_base = P->t_base; a.j0 = f->blocks;
+    a.d = d; a.d_stride = f->d.cap; a.d_base = f->d_base; a.hu = P->d_hu;
+    a.t = P->t.p[P->cur]; a.t_stride = P->t.cap; a.t_base = P->t_base; a.j0 = f->blocks;
     a.e_out = a.eu_out = a.du_out = nullptr; a.out_stride = 0;
     launch_impair(s, (int)(b1 - f->blocks), f->nchan, a);
     HIPCHK(hipGetLastError());
     ImpairReportArgs q;
-    q.t = P->d_t[P->cur]; q.t_new = P->d_t[P->cur ^ 1]; q.t_stride = P->t_cap; q.t_base = P->t_base;
+    q.t = P->t.p[P->cur]; q.t_new = P->t.p[P->cur ^ 1]; q.t_stride = P->t.cap; q.t_base = P->t_base;
     q.t_base_new = b1 > RECORDS_KEPT ? b1 - RECORDS_KEPT : 0;
     q.j0 = f->blocks; q.j1 = b1; q.ja = a1 - 1; q.win = f->d_win; q.report = P->d_report;
     q.r = r.r; q.r_stride = r.r_stride; q.r_at = (long long)BLOCK * b1 - R_TAIL - r.r_base; q.r_tail = P->d_tail;
@@ -165,9 +146,7 @@ int nrsc5::impair_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long lon
 extern "C" int nrsc5hip_fm_impair_enable(nrsc5hip_fm *f, const nrsc5hip_fm_impair_config *cfg)
 {
     static_assert(RECORDS_KEPT == 2 * W + 1, "the windowed report reads 2 W + 1 block records");
-    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
-    if (f->impair) FAIL(NRSC5HIP_EINVAL, "the impairment measurement is enabled already");
-    if (f->processed) FAIL(NRSC5HIP_EINVAL, "the impairment measurement can be enabled only before the first push");
+    FM_ENABLE_CHECK(f, f->impair, "the impairment measurement");
     nrsc5hip_fm_impair_config c = {0.5, 0.05, 0.5};
     if (cfg) c = *cfg;
     if (!(c.explained_min >= 0.0 && c.explained_min <= 1.0)) FAIL(NRSC5HIP_EINVAL, "explained_min %g outside 0..1", c.explained_min);
@@ -177,12 +156,11 @@ extern "C" int nrsc5hip_fm_impair_enable(nrsc5hip_fm *f, const nrsc5hip_fm_impai
     ImpairHost *P = new (std::nothrow) ImpairHost;
     if (!P) FAIL(NRSC5HIP_ENOMEM, "out of host memory");
     P->cfg = c;
-    for (int w = -W; w <= W; w++) P->wsum += (double)(float)(0.5 * (1 + cos(M_PI * w / (W + 1))));
+    for (float v : hann_window()) P->wsum += (double)v;
     const std::vector<float> &hu = hu_table();
     const size_t K = (size_t)f->nchan;
-    P->t_cap = RECORDS_KEPT + 256;
 #define ENABLE_CHK(expr) HIPCHK_OR(expr, delete P)
-    for (int i = 0; i < 2; i++) ENABLE_CHK(hipMalloc(&P->d_t[i], sizeof(double) * NS * (size_t)P->t_cap * K));
+    ENABLE_CHK(P->t.alloc(RECORDS_KEPT + 256, f->nchan, NS));
     ENABLE_CHK(hipMalloc(&P->d_report, sizeof(double) * 2 * NS * K));
     ENABLE_CHK(hipMalloc(&P->d_tail, sizeof(float) * R_TAIL * K));
     ENABLE_CHK(hipMalloc(&P->d_hu, sizeof(float) * UT));
@@ -198,8 +176,7 @@ extern "C" int nrsc5hip_fm_impair_enable(nrsc5hip_fm *f, const nrsc5hip_fm_impai
 extern "C" int nrsc5hip_fm_impair(nrsc5hip_fm *f, nrsc5hip_fm_impair_info *out)
 {
     if (!f || !out) FAIL(NRSC5HIP_EINVAL, "null argument");
-    if (!f->impair) FAIL(NRSC5HIP_EINVAL, "the impairment measurement is not enabled on this object");
-    nrsc5::DeviceGuard guard(f->device);
+    FM_FEATURE_ENTER(f, impair, "the impairment measurement");
     ImpairHost *P = f->impair;
     std::vector<double> v(2 * NS * (size_t)f->nchan);
     HIPCHK(hipStreamSynchronize(f->stream));
@@ -226,35 +203,24 @@ extern "C" int nrsc5hip_stage_fm_impair(nrsc5hip_fm *f, const int16_t *dev_in, l
                                         float *du_out, double *sums_out)
 {
     if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
-    if (n_in <= 0 || !dev_in) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
-    if (((uintptr_t)dev_in & 3) || (in_stride_elems & 1)) FAIL(NRSC5HIP_EINVAL, "input not aligned to 4 bytes (in_stride_elems %lld)", in_stride_elems);
-    if (f->nchan > 1 && in_stride_elems < 2 * n_in) FAIL(NRSC5HIP_EINVAL, "in_stride_elems %lld < 2 * n_in %lld", in_stride_elems, n_in);
-    const long long m1 = (n_in + 1) >> 1, b1 = m1 / BLOCK, mb = (long long)BLOCK * b1;
-    if ((m1 + FT - 1) / FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
-    if (b1 == 0) return 0;
+    nrsc5::DeviceGuard guard(f->device);
+    StageFront sf;
+    const int rc = sf.open(f, dev_in, in_stride_elems, n_in, true, 1);
+    if (rc) return rc;
+    const long long m1 = sf.m1, b1 = sf.b1, mb = (long long)BLOCK * b1;
+    if (b1 == 0) return 0;                                   // no complete block
     const size_t K = (size_t)f->nchan;
     const std::vector<float> &hu = hu_table();
-    nrsc5::DeviceGuard guard(f->device);
-    nrsc5::DevTmp d, r, e, eu, du, t, hist, taps;
-    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * K));
-    HIPCHK(hipMalloc(&r.p, sizeof(float) * (size_t)m1 * K));
+    nrsc5::DevTmp e, eu, du, t, taps;
     HIPCHK(hipMalloc(&e.p, sizeof(float) * (size_t)mb * K));
     HIPCHK(hipMalloc(&eu.p, sizeof(float) * (size_t)mb * K));
     HIPCHK(hipMalloc(&du.p, sizeof(float) * (size_t)mb * K));
     HIPCHK(hipMalloc(&t.p, sizeof(double) * NS * (size_t)b1 * K));
-    HIPCHK(hipMalloc(&hist.p, sizeof(int) * HIST * K));
     HIPCHK(hipMalloc(&taps.p, sizeof(float) * UT));
-    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * HIST * K, f->stream));
     HIPCHK(hipMemcpyAsync(taps.p, hu.data(), sizeof(float) * UT, hipMemcpyHostToDevice, f->stream));
-    FrontArgs a;
-    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
-    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
-    a.r = (float *)r.p; a.r_stride = m1; a.r_base = 0;
-    launch_front(f->stream, (int)((m1 + FT - 1) / FT), f->nchan, a);
-    HIPCHK(hipGetLastError());
     ImpairArgs q;
-    q.r = (const float *)r.p; q.r_stride = m1; q.r_base = 0; q.r_tail = (const float *)r.p;      // the tail is not read: every m >= 0 is in r
-    q.d = (const float *)d.p; q.d_stride = m1; q.d_base = 0; q.hu = (const float *)taps.p;
+    q.r = sf.rf(); q.r_stride = m1; q.r_base = 0; q.r_tail = sf.rf();                            // the tail is not read: every m >= 0 is in r
+    q.d = sf.df(); q.d_stride = m1; q.d_base = 0; q.hu = (const float *)taps.p;
     q.t = (double *)t.p; q.t_stride = b1; q.t_base = 0; q.j0 = 0;
     q.e_out = (float *)e.p; q.eu_out = (float *)eu.p; q.du_out = (float *)du.p; q.out_stride = mb;
     launch_impair(f->stream, (int)b1, f->nchan, q);

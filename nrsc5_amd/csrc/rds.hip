@@ -1,6 +1,6 @@
 // RDS / RBDS of the analog host, host side (include/nrsc5hip.h, "RDS"): the tap table in double, the buffers an analog FM object
 // gains with nrsc5hip_fm_rds_enable, the launches fm_launch chains behind its front end, the event read-back and the two stage hooks.  The
-// kernels are in k_rds.hip.
+// kernels are in k_rds.hip; y's buffer that grows, the event arena and the hooks' opening are fm_host.h's.
 //   per push, host -> device: nothing (the launches carry their arguments)
 //   per read, device -> host: 4 bytes per channel (the used part of its arena) and the used parts themselves (64 bytes + the text per event)
 #include <hip/hip_runtime.h>
@@ -11,8 +11,7 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "host_util.h"
-#include "arena_consumer.h"
-#include "fm_audio.h"
+#include "fm_host.h"
 
 using namespace nrsc5;
 using namespace nrsc5::rds;
@@ -21,19 +20,17 @@ struct nrsc5::RdsHost {
     int raw = 0, burst = 2;
     std::vector<float> tab;                                  // host copy [GRID][NT]
     DevFixed<float> d_tab;                                   // [NT][GRID], indexed by r mod GRID
-    float2 *d_y[2] = {nullptr, nullptr}; long long y_cap = 0, y_base = 0; int cur = 0;   // y[r], r in [y_base, r_total), of channel c at d_y[cur][c * y_cap + r - y_base]
+    fm::PingPong<float2> y; long long y_base = 0; int cur = 0;   // y[r], r in [y_base, r_total), of channel c at y.p[cur][c * y.cap + r - y_base]
     long long r_total = 0, windows = 0;                      // grid points summed, windows decided
     DevFixed<int> d_s[2]; int s_cur = 0;                     // [nchan]: s of the last window decided (-1: none)
     DevFixed<State> d_state; DevFixed<unsigned long long> d_stats;
     DevGrow bits, counts;                                    // one launch's decisions
-    uint8_t *d_arena = nullptr; DevFixed<unsigned> d_used;   // [nchan][arena_cap]; d_used: [nchan] bytes used, then the overflow flag
-    unsigned arena_cap = 0; size_t pending = 0;              // pending: what a channel's arena may hold at most since the last look
-    ~RdsHost() { (void)hipFree(d_y[0]); (void)hipFree(d_y[1]); (void)hipFree(d_arena); }
+    fm::EventArena events;                                   // what k_rds_groups reports, until the next read
 };
 
 namespace {
 
-double sinc(double x) { return x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x); }
+using fm::sinc;
 double shape_h(double t, double T) { return sinc(4 * t / T + 0.5) + sinc(4 * t / T - 0.5); }
 
 // tab[ph][j]: the biphase symbol, centred on the grid point, tau = j - HALF - ph / GRID samples from it, under the Hann window over |tau| <= 2 T
@@ -53,56 +50,15 @@ std::vector<float> design_taps()
 
 size_t events_bound(long long nbits) { return (size_t)(nbits / 104 + 2) * EVENTS_PER_GROUP * EVENT_MAX; }
 
-int y_reserve(nrsc5hip_fm *f, hipStream_t s, long long r1)
-{
-    RdsHost *R = f->rds;
-    const long long need = r1 - R->y_base;
-    if (need <= R->y_cap) return 0;
-    HIPCHK(hipStreamSynchronize(s));
-    const long long cap = need + need / 4 + 2048;
-    float2 *ny[2] = {nullptr, nullptr};
-    HIPCHK(hipMalloc(&ny[0], sizeof(float2) * (size_t)cap * f->nchan));
-    if (hipMalloc(&ny[1], sizeof(float2) * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(ny[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (y, %lld per channel)", cap); }
-    const long long have = R->r_total - R->y_base;
-    if (have > 0)
-        HIPCHK(hipMemcpy2DAsync(ny[R->cur], sizeof(float2) * cap, R->d_y[R->cur], sizeof(float2) * R->y_cap, sizeof(float2) * have, f->nchan, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    (void)hipFree(R->d_y[0]); (void)hipFree(R->d_y[1]);
-    R->d_y[0] = ny[0]; R->d_y[1] = ny[1]; R->y_cap = cap;
-    return 0;
-}
-
-// room in every channel's arena for the events of nbits more bits; what the arenas hold moves over when they grow
-int arena_reserve_bits(nrsc5hip_fm *f, hipStream_t s, long long nbits)
-{
-    RdsHost *R = f->rds;
-    const size_t more = events_bound(nbits);
-    if (R->pending + more <= R->arena_cap) { R->pending += more; return 0; }
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<unsigned> used((size_t)f->nchan);
-    HIPCHK(hipMemcpy(used.data(), R->d_used.p, sizeof(unsigned) * f->nchan, hipMemcpyDeviceToHost));
-    const size_t top = *std::max_element(used.begin(), used.end());
-    R->pending = top;
-    if (R->pending + more > R->arena_cap) {
-        const size_t cap = 2 * (R->pending + more);
-        if (cap * (size_t)f->nchan > 0xfffffff0u) FAIL(NRSC5HIP_EOVERFLOW, "RDS events of %d channels unread: %zu bytes per channel", f->nchan, cap);
-        uint8_t *na = nullptr;
-        if (hipMalloc(&na, cap * f->nchan) != hipSuccess) FAIL(NRSC5HIP_ENOMEM, "out of device memory (RDS events, %zu per channel)", cap);
-        if (top > 0) HIPCHK(hipMemcpy2DAsync(na, cap, R->d_arena, R->arena_cap, top, f->nchan, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        (void)hipFree(R->d_arena);
-        R->d_arena = na; R->arena_cap = (unsigned)cap;
-    }
-    R->pending += more;
-    return 0;
-}
+// room in every channel's arena for the events of nbits more bits
+int arena_reserve_bits(nrsc5hip_fm *f, hipStream_t s, long long nbits) { return f->rds->events.reserve(s, events_bound(nbits), f->nchan, "RDS"); }
 
 void groups_args(nrsc5hip_fm *f, GroupsArgs &g)
 {
     RdsHost *R = f->rds;
     g.targets = nullptr; g.reset_at = nullptr;
     g.state = R->d_state.p; g.stats = R->d_stats.p;
-    g.arena = R->d_arena; g.used = R->d_used.p; g.overflow = R->d_used.p + f->nchan; g.arena_cap = R->arena_cap;
+    g.arena = R->events.d_arena; g.used = R->events.d_used.p; g.overflow = R->events.d_used.p + f->nchan; g.arena_cap = R->events.arena_cap;
     g.raw = R->raw; g.burst = R->burst;
 }
 
@@ -127,9 +83,10 @@ int nrsc5::rds_reset(nrsc5hip_fm *f)
     HIPCHK(hipMemcpy(R->d_s[0].p, none.data(), sizeof(int) * f->nchan, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R->d_s[1].p, none.data(), sizeof(int) * f->nchan, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(R->d_stats.p, 0, sizeof(unsigned long long) * NSTATS * f->nchan, f->stream));
-    HIPCHK(hipMemsetAsync(R->d_used.p, 0, sizeof(unsigned) * (f->nchan + 1), f->stream));
+    const int rc = R->events.reset(f->stream, f->nchan);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(f->stream));
-    R->cur = 0; R->s_cur = 0; R->y_base = 0; R->r_total = 0; R->windows = 0; R->pending = 0;
+    R->cur = 0; R->s_cur = 0; R->y_base = 0; R->r_total = 0; R->windows = 0;
     return 0;
 }
 
@@ -140,20 +97,20 @@ int nrsc5::rds_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long m
     if (r1 <= R->r_total) return 0;
     const long long w1 = r1 / WIN_PTS, nwin = w1 - R->windows;
     int rc;
-    if ((rc = y_reserve(f, s, r1))) return rc;
+    if ((rc = R->y.reserve(s, r1 - R->y_base, R->r_total - R->y_base, f->nchan, 1, 2048, R->cur, "y"))) return rc;
     if (nwin > 0) {
         if (nwin > 0x7fffffLL) FAIL(NRSC5HIP_EINVAL, "push too large (%lld RDS windows)", nwin);
         if ((rc = R->bits.need((size_t)f->nchan * nwin * BITS_STRIDE)) || (rc = R->counts.need(sizeof(int) * (size_t)f->nchan * nwin))) return rc;
         if ((rc = arena_reserve_bits(f, s, nwin * WIN_MAX_BITS))) return rc;
     }
     MfArgs m;
-    m.d = d; m.d_stride = f->d_cap; m.d_base = f->d_base; m.cs = f->d_cs; m.tab = R->d_tab.p;
-    m.y = R->d_y[R->cur]; m.y_stride = R->y_cap; m.y_base = R->y_base; m.r0 = R->r_total; m.r_count = r1 - R->r_total;
+    m.d = d; m.d_stride = f->d.cap; m.d_base = f->d_base; m.cs = f->d_cs; m.tab = R->d_tab.p;
+    m.y = R->y.p[R->cur]; m.y_stride = R->y.cap; m.y_base = R->y_base; m.r0 = R->r_total; m.r_count = r1 - R->r_total;
     launch_mf(s, (int)((m.r_count + MT - 1) / MT), f->nchan, m);
     HIPCHK(hipGetLastError());
     if (nwin > 0) {
         BitsArgs b;
-        b.y = R->d_y[R->cur]; b.y_stride = R->y_cap; b.y_base = R->y_base; b.w0 = R->windows; b.nwin = (int)nwin;
+        b.y = R->y.p[R->cur]; b.y_stride = R->y.cap; b.y_base = R->y_base; b.w0 = R->windows; b.nwin = (int)nwin;
         b.s_in = R->d_s[R->s_cur].p; b.s_out = R->d_s[R->s_cur ^ 1].p;
         b.bits = (uint8_t *)R->bits.p; b.counts = (int *)R->counts.p; b.energy = nullptr; b.s_w = nullptr; b.stats = R->d_stats.p;
         launch_bits(s, f->nchan, b);
@@ -166,7 +123,7 @@ int nrsc5::rds_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long m
         // what the next call needs of y: the incomplete window and, for its first decision, the 8 points in front of it
         const long long y_base = w1 * WIN_PTS - S;
         rds::KeepArgs k;
-        k.y_old = R->d_y[R->cur]; k.y_new = R->d_y[R->cur ^ 1]; k.y_stride = R->y_cap; k.shift = y_base - R->y_base; k.count = r1 - y_base;
+        k.y_old = R->y.p[R->cur]; k.y_new = R->y.p[R->cur ^ 1]; k.y_stride = R->y.cap; k.shift = y_base - R->y_base; k.count = r1 - y_base;
         rds::launch_keep(s, f->nchan, k);
         HIPCHK(hipGetLastError());
         R->cur ^= 1; R->s_cur ^= 1; R->y_base = y_base; R->windows = w1;
@@ -175,17 +132,13 @@ int nrsc5::rds_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long m
     return 0;
 }
 
-#define RDS_ENTER(f)                                                         \
-    if (!(f)) FAIL(NRSC5HIP_EINVAL, "null demodulator");                     \
-    if (!(f)->rds) FAIL(NRSC5HIP_EINVAL, "RDS is not enabled on this object"); \
-    nrsc5::DeviceGuard guard((f)->device);                                   \
+#define RDS_ENTER(f)                   \
+    FM_FEATURE_ENTER(f, rds, "RDS"); \
     RdsHost *R = (f)->rds
 
 extern "C" int nrsc5hip_fm_rds_enable(nrsc5hip_fm *f, const nrsc5hip_rds_config *cfg)
 {
-    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
-    if (f->rds) FAIL(NRSC5HIP_EINVAL, "RDS is enabled already");
-    if (f->processed) FAIL(NRSC5HIP_EINVAL, "RDS can be enabled only before the first push");
+    FM_ENABLE_CHECK(f, f->rds, "RDS");
     if (cfg && (cfg->correct_burst < 0 || cfg->correct_burst > 2)) FAIL(NRSC5HIP_EINVAL, "correct_burst %d: 0 .. 2", cfg->correct_burst);
     nrsc5::DeviceGuard guard(f->device);
     RdsHost *R = new (std::nothrow) RdsHost;
@@ -198,18 +151,14 @@ extern "C" int nrsc5hip_fm_rds_enable(nrsc5hip_fm *f, const nrsc5hip_rds_config 
         for (int j = 0; j < NT; j++) dev[(size_t)j * GRID + q] = R->tab[(size_t)ph * NT + j];
     }
     const size_t K = (size_t)f->nchan;
-    R->y_cap = 2 * WIN_PTS + 8192;
-    R->arena_cap = (unsigned)events_bound(4 * WIN_MAX_BITS * 8);
 #define ENABLE_CHK(expr) HIPCHK_OR(expr, delete R)
     ENABLE_CHK(hipMalloc(&R->d_tab.p, sizeof(float) * dev.size()));
-    ENABLE_CHK(hipMalloc(&R->d_y[0], sizeof(float2) * (size_t)R->y_cap * K));
-    ENABLE_CHK(hipMalloc(&R->d_y[1], sizeof(float2) * (size_t)R->y_cap * K));
+    ENABLE_CHK(R->y.alloc(2 * WIN_PTS + 8192, f->nchan));
     ENABLE_CHK(hipMalloc(&R->d_s[0].p, sizeof(int) * K));
     ENABLE_CHK(hipMalloc(&R->d_s[1].p, sizeof(int) * K));
     ENABLE_CHK(hipMalloc(&R->d_state.p, sizeof(State) * K));
     ENABLE_CHK(hipMalloc(&R->d_stats.p, sizeof(unsigned long long) * NSTATS * K));
-    ENABLE_CHK(hipMalloc(&R->d_used.p, sizeof(unsigned) * (K + 1)));
-    ENABLE_CHK(hipMalloc(&R->d_arena, (size_t)R->arena_cap * K));
+    ENABLE_CHK(R->events.alloc(events_bound(4 * WIN_MAX_BITS * 8), f->nchan));
     ENABLE_CHK(hipMemcpy(R->d_tab.p, dev.data(), sizeof(float) * dev.size(), hipMemcpyHostToDevice));
 #undef ENABLE_CHK
     f->rds = R;
@@ -240,34 +189,9 @@ extern "C" int nrsc5hip_fm_rds_taps(nrsc5hip_fm *f, float *taps)
 extern "C" int nrsc5hip_fm_rds_read(nrsc5hip_fm *f, nrsc5hip_rds_cb cb, void *opaque)
 {
     RDS_ENTER(f);
-    const size_t K = (size_t)f->nchan;
-    HIPCHK(hipStreamSynchronize(f->stream));
-    std::vector<unsigned> used(K + 1);
-    HIPCHK(hipMemcpy(used.data(), R->d_used.p, sizeof(unsigned) * (K + 1), hipMemcpyDeviceToHost));
-    if (used[K]) FAIL(NRSC5HIP_EOVERFLOW, "RDS event arena of %u bytes per channel too small: events are lost", R->arena_cap);
-    const size_t top = *std::max_element(used.begin(), used.begin() + K);
-    if (top == 0) { R->pending = 0; return 0; }
-    if (top > R->arena_cap) FAIL(NRSC5HIP_EHIP, "RDS event arena is not what k_rds_groups writes (%zu bytes used of %u)", top, R->arena_cap);
-    std::vector<uint8_t> got(top * K);
-    HIPCHK(hipMemcpy2DAsync(got.data(), top, R->d_arena, R->arena_cap, top, K, hipMemcpyDeviceToHost, f->stream));
-    HIPCHK(hipMemsetAsync(R->d_used.p, 0, sizeof(unsigned) * K, f->stream));
-    HIPCHK(hipStreamSynchronize(f->stream));
-    R->pending = 0;
-    int delivered = 0;
-    for (size_t c = 0; c < K; c++) {
-        std::vector<std::vector<size_t>> per;
-        size_t bad = 0;
-        const uint8_t *base = got.data() + c * top;
-        if (!arena_walk<Event>(base, used[c], K, [&](const Event &ev) { return ev.pos == c && ev.kind >= NRSC5HIP_RDS_PI && ev.kind <= NRSC5HIP_RDS_GROUP && ev.len <= 64; }, per, &bad))
-            FAIL(NRSC5HIP_EHIP, "RDS event arena of channel %zu is not what k_rds_groups writes (offset %zu)", c, bad);
-        for (size_t at : per[c]) {
-            Event ev;
-            memcpy(&ev, base + at, sizeof(ev));
-            if (cb) cb(opaque, (int)c, ev.kind, ev.group, ev.bit, ev.v, base + at + sizeof(Event), ev.len);
-            delivered++;
-        }
-    }
-    return delivered;
+    return R->events.read<Event>(f->stream, f->nchan, "RDS", "k_rds_groups",
+        [](const Event &ev) { return ev.kind >= NRSC5HIP_RDS_PI && ev.kind <= NRSC5HIP_RDS_GROUP && ev.len <= 64; },
+        [&](int c, const Event &ev, const uint8_t *text) { if (cb) cb(opaque, c, ev.kind, ev.group, ev.bit, ev.v, text, ev.len); });
 }
 
 extern "C" int nrsc5hip_fm_rds_get(nrsc5hip_fm *f, int channel, nrsc5hip_rds_info *out)
@@ -290,43 +214,29 @@ extern "C" int nrsc5hip_fm_rds_get(nrsc5hip_fm *f, int channel, nrsc5hip_rds_inf
 extern "C" int nrsc5hip_fm_rds_stats(nrsc5hip_fm *f, int channel, long long stats[NRSC5HIP_RDS_NSTATS])
 {
     RDS_ENTER(f);
-    if (!stats || channel < 0 || channel >= f->nchan) FAIL(NRSC5HIP_EINVAL, "bad channel %d", channel);
-    HIPCHK(hipStreamSynchronize(f->stream));
-    unsigned long long v[NSTATS];
-    HIPCHK(hipMemcpy(v, R->d_stats.p + (size_t)channel * NSTATS, sizeof(v), hipMemcpyDeviceToHost));
-    for (int k = 0; k < NSTATS; k++) stats[k] = (long long)v[k];
-    return 0;
+    return fm::read_channel_stats<NSTATS>(f, R->d_stats.p, channel, stats);
 }
 
 extern "C" int nrsc5hip_stage_rds_mf(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *y_out, float *energy_out,
                                      int32_t *s_out, uint8_t *bits_out, int32_t *counts_out)
 {
     RDS_ENTER(f);
-    if (n_in <= 0 || !dev_in) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
-    if (((uintptr_t)dev_in & 3) || (in_stride_elems & 1)) FAIL(NRSC5HIP_EINVAL, "input not aligned to 4 bytes (in_stride_elems %lld)", in_stride_elems);
-    if (f->nchan > 1 && in_stride_elems < 2 * n_in) FAIL(NRSC5HIP_EINVAL, "in_stride_elems %lld < 2 * n_in %lld", in_stride_elems, n_in);
-    const long long m1 = (n_in + 1) >> 1, r1 = points_total(m1), nwin = r1 / WIN_PTS;
-    if ((m1 + fm::FT - 1) / fm::FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
+    fm::StageFront sf;
+    const int rc = sf.open(f, dev_in, in_stride_elems, n_in, false);
+    if (rc) return rc;
+    const long long m1 = sf.m1, r1 = points_total(m1), nwin = r1 / WIN_PTS;
     const size_t K = (size_t)f->nchan;
-    nrsc5::DevTmp d, hist, y, sk, bits, counts, en, sw;
-    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * K));
-    HIPCHK(hipMalloc(&hist.p, sizeof(int) * fm::HIST * K));
+    nrsc5::DevTmp y, sk, bits, counts, en, sw;
     HIPCHK(hipMalloc(&y.p, sizeof(float2) * (size_t)(r1 + 1) * K));
     HIPCHK(hipMalloc(&sk.p, sizeof(int) * 2 * K));
     HIPCHK(hipMalloc(&bits.p, (size_t)(nwin + 1) * BITS_STRIDE * K));
     HIPCHK(hipMalloc(&counts.p, sizeof(int) * (size_t)(nwin + 1) * K));
     HIPCHK(hipMalloc(&en.p, sizeof(float) * (size_t)(nwin + 1) * S * K));
     HIPCHK(hipMalloc(&sw.p, sizeof(int) * (size_t)(nwin + 1) * K));
-    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * fm::HIST * K, f->stream));
     HIPCHK(hipMemsetAsync(sk.p, 0xff, sizeof(int) * 2 * K, f->stream));
-    fm::FrontArgs a;
-    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
-    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
-    fm::launch_front(f->stream, (int)((m1 + fm::FT - 1) / fm::FT), f->nchan, a);
-    HIPCHK(hipGetLastError());
     if (r1 > 0) {
         MfArgs m;
-        m.d = (const float *)d.p; m.d_stride = m1; m.d_base = 0; m.cs = f->d_cs; m.tab = R->d_tab.p;
+        m.d = sf.df(); m.d_stride = m1; m.d_base = 0; m.cs = f->d_cs; m.tab = R->d_tab.p;
         m.y = (float2 *)y.p; m.y_stride = r1; m.y_base = 0; m.r0 = 0; m.r_count = r1;
         launch_mf(f->stream, (int)((r1 + MT - 1) / MT), f->nchan, m);
         HIPCHK(hipGetLastError());

@@ -1,6 +1,6 @@
 // EAS alerts (SAME) of the analog host, host side (include/nrsc5hip.h, "SAME"): the phasor table in double, the buffers an analog
 // FM object gains with nrsc5hip_fm_same_enable, the launches fm_launch chains behind its front end, the event read-back and the two stage hooks.
-// The kernels are in k_same.hip.
+// The kernels are in k_same.hip; c's buffer that grows, the event arena and the hooks' opening are fm_host.h's.
 //   per push, host -> device: nothing (the launches carry their arguments)
 //   per read, device -> host: 4 bytes per channel (the used part of its arena) and the used parts themselves (64 bytes + the text per event)
 #include <hip/hip_runtime.h>
@@ -11,9 +11,7 @@
 #include <vector>
 #include "nrsc5hip.h"
 #include "host_util.h"
-#include "arena_consumer.h"
-#include "fm_audio.h"
-#include "same.h"
+#include "fm_host.h"
 
 using namespace nrsc5;
 using namespace nrsc5::same;
@@ -22,70 +20,27 @@ struct nrsc5::SameHost {
     int burst_events = 1;
     std::vector<float2> cs;                                  // host copy of the table
     DevFixed<float2> d_cs;                                   // [DEN] (cos, sin) of 2 pi k / DEN
-    float4 *d_c[2] = {nullptr, nullptr}; long long c_cap = 0, c_base = 0; int cur = 0;   // c[r], r in [c_base, r_total), of channel k at d_c[cur][k * c_cap + r - c_base]
+    fm::PingPong<float4> c; long long c_base = 0; int cur = 0;   // c[r], r in [c_base, r_total), of channel k at c.p[cur][k * c.cap + r - c_base]
     long long r_total = 0, windows = 0;                      // segments summed, windows decided
     DevFixed<int> d_s[2]; int s_cur = 0;                     // [nchan]: s of the last window decided (-1: none)
     DevFixed<State> d_state; DevFixed<unsigned long long> d_stats;
     DevGrow bits, counts;                                    // one launch's decisions
-    uint8_t *d_arena = nullptr; DevFixed<unsigned> d_used;   // [nchan][arena_cap]; d_used: [nchan] bytes used, then the overflow flag
-    unsigned arena_cap = 0; size_t pending = 0;              // pending: what a channel's arena may hold at most since the last look
-    ~SameHost() { (void)hipFree(d_c[0]); (void)hipFree(d_c[1]); (void)hipFree(d_arena); }
+    fm::EventArena events;                                   // what k_same_frames reports, until the next read
 };
 
 namespace {
 
 size_t events_bound(long long nbits) { return (size_t)(nbits / BURST_MIN_BITS + 2) * 2 * EVENT_MAX; }
 
-int c_reserve(nrsc5hip_fm *f, hipStream_t s, long long r1)
-{
-    SameHost *R = f->same;
-    const long long need = r1 - R->c_base;
-    if (need <= R->c_cap) return 0;
-    HIPCHK(hipStreamSynchronize(s));
-    const long long cap = need + need / 4 + 2048;
-    float4 *nc[2] = {nullptr, nullptr};
-    HIPCHK(hipMalloc(&nc[0], sizeof(float4) * (size_t)cap * f->nchan));
-    if (hipMalloc(&nc[1], sizeof(float4) * (size_t)cap * f->nchan) != hipSuccess) { (void)hipFree(nc[0]); FAIL(NRSC5HIP_ENOMEM, "out of device memory (c, %lld per channel)", cap); }
-    const long long have = R->r_total - R->c_base;
-    if (have > 0)
-        HIPCHK(hipMemcpy2DAsync(nc[R->cur], sizeof(float4) * cap, R->d_c[R->cur], sizeof(float4) * R->c_cap, sizeof(float4) * have, f->nchan, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    (void)hipFree(R->d_c[0]); (void)hipFree(R->d_c[1]);
-    R->d_c[0] = nc[0]; R->d_c[1] = nc[1]; R->c_cap = cap;
-    return 0;
-}
-
-// room in every channel's arena for the events of nbits more bits; what the arenas hold moves over when they grow
-int arena_reserve_bits(nrsc5hip_fm *f, hipStream_t s, long long nbits)
-{
-    SameHost *R = f->same;
-    const size_t more = events_bound(nbits);
-    if (R->pending + more <= R->arena_cap) { R->pending += more; return 0; }
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<unsigned> used((size_t)f->nchan);
-    HIPCHK(hipMemcpy(used.data(), R->d_used.p, sizeof(unsigned) * f->nchan, hipMemcpyDeviceToHost));
-    const size_t top = *std::max_element(used.begin(), used.end());
-    R->pending = top;
-    if (R->pending + more > R->arena_cap) {
-        const size_t cap = 2 * (R->pending + more);
-        if (cap * (size_t)f->nchan > 0xfffffff0u) FAIL(NRSC5HIP_EOVERFLOW, "SAME events of %d channels unread: %zu bytes per channel", f->nchan, cap);
-        uint8_t *na = nullptr;
-        if (hipMalloc(&na, cap * f->nchan) != hipSuccess) FAIL(NRSC5HIP_ENOMEM, "out of device memory (SAME events, %zu per channel)", cap);
-        if (top > 0) HIPCHK(hipMemcpy2DAsync(na, cap, R->d_arena, R->arena_cap, top, f->nchan, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        (void)hipFree(R->d_arena);
-        R->d_arena = na; R->arena_cap = (unsigned)cap;
-    }
-    R->pending += more;
-    return 0;
-}
+// room in every channel's arena for the events of nbits more bits
+int arena_reserve_bits(nrsc5hip_fm *f, hipStream_t s, long long nbits) { return f->same->events.reserve(s, events_bound(nbits), f->nchan, "SAME"); }
 
 void frames_args(nrsc5hip_fm *f, FramesArgs &g)
 {
     SameHost *R = f->same;
     g.targets = nullptr; g.reset_at = nullptr;
     g.state = R->d_state.p; g.stats = R->d_stats.p;
-    g.arena = R->d_arena; g.used = R->d_used.p; g.overflow = R->d_used.p + f->nchan; g.arena_cap = R->arena_cap;
+    g.arena = R->events.d_arena; g.used = R->events.d_used.p; g.overflow = R->events.d_used.p + f->nchan; g.arena_cap = R->events.arena_cap;
     g.burst_events = R->burst_events;
 }
 
@@ -106,9 +61,10 @@ int nrsc5::same_reset(nrsc5hip_fm *f)
     HIPCHK(hipMemcpy(R->d_s[0].p, none.data(), sizeof(int) * f->nchan, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(R->d_s[1].p, none.data(), sizeof(int) * f->nchan, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(R->d_stats.p, 0, sizeof(unsigned long long) * NSTATS * f->nchan, f->stream));
-    HIPCHK(hipMemsetAsync(R->d_used.p, 0, sizeof(unsigned) * (f->nchan + 1), f->stream));
+    const int rc = R->events.reset(f->stream, f->nchan);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(f->stream));
-    R->cur = 0; R->s_cur = 0; R->c_base = 0; R->r_total = 0; R->windows = 0; R->pending = 0;
+    R->cur = 0; R->s_cur = 0; R->c_base = 0; R->r_total = 0; R->windows = 0;
     return 0;
 }
 
@@ -120,20 +76,20 @@ int nrsc5::same_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long 
     const long long w1 = windows_total(r1), nwin = w1 - R->windows;
     int rc;
     if ((r1 - R->r_total + TT - 1) / TT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "push too large (%lld SAME segments)", r1 - R->r_total);
-    if ((rc = c_reserve(f, s, r1))) return rc;
+    if ((rc = R->c.reserve(s, r1 - R->c_base, R->r_total - R->c_base, f->nchan, 1, 2048, R->cur, "c"))) return rc;
     if (nwin > 0) {
         if (nwin > 0x7fffffLL) FAIL(NRSC5HIP_EINVAL, "push too large (%lld SAME windows)", nwin);
         if ((rc = R->bits.need((size_t)f->nchan * nwin * BITS_STRIDE)) || (rc = R->counts.need(sizeof(int) * (size_t)f->nchan * nwin))) return rc;
         if ((rc = arena_reserve_bits(f, s, nwin * WIN_MAX_BITS))) return rc;
     }
     TonesArgs t;
-    t.d = d; t.d_stride = f->d_cap; t.d_base = f->d_base; t.cs = R->d_cs.p;
-    t.c = R->d_c[R->cur]; t.c_stride = R->c_cap; t.c_base = R->c_base; t.r0 = R->r_total; t.r_count = r1 - R->r_total;
+    t.d = d; t.d_stride = f->d.cap; t.d_base = f->d_base; t.cs = R->d_cs.p;
+    t.c = R->c.p[R->cur]; t.c_stride = R->c.cap; t.c_base = R->c_base; t.r0 = R->r_total; t.r_count = r1 - R->r_total;
     launch_tones(s, (int)((t.r_count + TT - 1) / TT), f->nchan, t);
     HIPCHK(hipGetLastError());
     if (nwin > 0) {
         BitsArgs b;
-        b.c = R->d_c[R->cur]; b.c_stride = R->c_cap; b.c_base = R->c_base; b.w0 = R->windows; b.nwin = (int)nwin;
+        b.c = R->c.p[R->cur]; b.c_stride = R->c.cap; b.c_base = R->c_base; b.w0 = R->windows; b.nwin = (int)nwin;
         b.s_in = R->d_s[R->s_cur].p; b.s_out = R->d_s[R->s_cur ^ 1].p;
         b.bits = (uint8_t *)R->bits.p; b.counts = (int *)R->counts.p; b.q = nullptr; b.metric = nullptr; b.s_w = nullptr; b.stats = R->d_stats.p;
         launch_bits(s, f->nchan, b);
@@ -146,7 +102,7 @@ int nrsc5::same_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long 
         // what the next call needs of c: the incomplete window
         const long long c_base = w1 * WIN_PTS;
         same::KeepArgs k;
-        k.c_old = R->d_c[R->cur]; k.c_new = R->d_c[R->cur ^ 1]; k.c_stride = R->c_cap; k.shift = c_base - R->c_base; k.count = r1 - c_base;
+        k.c_old = R->c.p[R->cur]; k.c_new = R->c.p[R->cur ^ 1]; k.c_stride = R->c.cap; k.shift = c_base - R->c_base; k.count = r1 - c_base;
         same::launch_keep(s, f->nchan, k);
         HIPCHK(hipGetLastError());
         R->cur ^= 1; R->s_cur ^= 1; R->c_base = c_base; R->windows = w1;
@@ -155,17 +111,13 @@ int nrsc5::same_launch(nrsc5hip_fm *f, hipStream_t s, const float *d, long long 
     return 0;
 }
 
-#define SAME_ENTER(f)                                                         \
-    if (!(f)) FAIL(NRSC5HIP_EINVAL, "null demodulator");                      \
-    if (!(f)->same) FAIL(NRSC5HIP_EINVAL, "SAME is not enabled on this object"); \
-    nrsc5::DeviceGuard guard((f)->device);                                    \
+#define SAME_ENTER(f)                    \
+    FM_FEATURE_ENTER(f, same, "SAME"); \
     SameHost *R = (f)->same
 
 extern "C" int nrsc5hip_fm_same_enable(nrsc5hip_fm *f, const nrsc5hip_same_config *cfg)
 {
-    if (!f) FAIL(NRSC5HIP_EINVAL, "null demodulator");
-    if (f->same) FAIL(NRSC5HIP_EINVAL, "SAME is enabled already");
-    if (f->processed) FAIL(NRSC5HIP_EINVAL, "SAME can be enabled only before the first push");
+    FM_ENABLE_CHECK(f, f->same, "SAME");
     if (cfg && (cfg->burst_events < 0 || cfg->burst_events > 1)) FAIL(NRSC5HIP_EINVAL, "burst_events %d: 0 or 1", cfg->burst_events);
     nrsc5::DeviceGuard guard(f->device);
     SameHost *R = new (std::nothrow) SameHost;
@@ -174,18 +126,14 @@ extern "C" int nrsc5hip_fm_same_enable(nrsc5hip_fm *f, const nrsc5hip_same_confi
     R->cs.resize(DEN);
     for (int k = 0; k < DEN; k++) { const double t = 2 * M_PI * k / DEN; R->cs[k] = make_float2((float)cos(t), (float)sin(t)); }
     const size_t K = (size_t)f->nchan;
-    R->c_cap = 2 * WIN_PTS + 8192;
-    R->arena_cap = (unsigned)events_bound(8 * WIN_MAX_BITS * 8);
 #define ENABLE_CHK(expr) HIPCHK_OR(expr, delete R)
     ENABLE_CHK(hipMalloc(&R->d_cs.p, sizeof(float2) * DEN));
-    ENABLE_CHK(hipMalloc(&R->d_c[0], sizeof(float4) * (size_t)R->c_cap * K));
-    ENABLE_CHK(hipMalloc(&R->d_c[1], sizeof(float4) * (size_t)R->c_cap * K));
+    ENABLE_CHK(R->c.alloc(2 * WIN_PTS + 8192, f->nchan));
     ENABLE_CHK(hipMalloc(&R->d_s[0].p, sizeof(int) * K));
     ENABLE_CHK(hipMalloc(&R->d_s[1].p, sizeof(int) * K));
     ENABLE_CHK(hipMalloc(&R->d_state.p, sizeof(State) * K));
     ENABLE_CHK(hipMalloc(&R->d_stats.p, sizeof(unsigned long long) * NSTATS * K));
-    ENABLE_CHK(hipMalloc(&R->d_used.p, sizeof(unsigned) * (K + 1)));
-    ENABLE_CHK(hipMalloc(&R->d_arena, (size_t)R->arena_cap * K));
+    ENABLE_CHK(R->events.alloc(events_bound(8 * WIN_MAX_BITS * 8), f->nchan));
     ENABLE_CHK(hipMemcpy(R->d_cs.p, R->cs.data(), sizeof(float2) * DEN, hipMemcpyHostToDevice));
 #undef ENABLE_CHK
     f->same = R;
@@ -215,34 +163,9 @@ extern "C" int nrsc5hip_fm_same_table(nrsc5hip_fm *f, float *cs)
 extern "C" int nrsc5hip_fm_same_read(nrsc5hip_fm *f, nrsc5hip_same_cb cb, void *opaque)
 {
     SAME_ENTER(f);
-    const size_t K = (size_t)f->nchan;
-    HIPCHK(hipStreamSynchronize(f->stream));
-    std::vector<unsigned> used(K + 1);
-    HIPCHK(hipMemcpy(used.data(), R->d_used.p, sizeof(unsigned) * (K + 1), hipMemcpyDeviceToHost));
-    if (used[K]) FAIL(NRSC5HIP_EOVERFLOW, "SAME event arena of %u bytes per channel too small: events are lost", R->arena_cap);
-    const size_t top = *std::max_element(used.begin(), used.begin() + K);
-    if (top == 0) { R->pending = 0; return 0; }
-    if (top > R->arena_cap) FAIL(NRSC5HIP_EHIP, "SAME event arena is not what k_same_frames writes (%zu bytes used of %u)", top, R->arena_cap);
-    std::vector<uint8_t> got(top * K);
-    HIPCHK(hipMemcpy2DAsync(got.data(), top, R->d_arena, R->arena_cap, top, K, hipMemcpyDeviceToHost, f->stream));
-    HIPCHK(hipMemsetAsync(R->d_used.p, 0, sizeof(unsigned) * K, f->stream));
-    HIPCHK(hipStreamSynchronize(f->stream));
-    R->pending = 0;
-    int delivered = 0;
-    for (size_t c = 0; c < K; c++) {
-        std::vector<std::vector<size_t>> per;
-        size_t bad = 0;
-        const uint8_t *base = got.data() + c * top;
-        if (!arena_walk<Event>(base, used[c], K, [&](const Event &ev) { return ev.pos == c && ev.kind >= NRSC5HIP_SAME_BURST && ev.kind <= NRSC5HIP_SAME_MESSAGE && ev.len <= (unsigned)TEXT_MAX; }, per, &bad))
-            FAIL(NRSC5HIP_EHIP, "SAME event arena of channel %zu is not what k_same_frames writes (offset %zu)", c, bad);
-        for (size_t at : per[c]) {
-            Event ev;
-            memcpy(&ev, base + at, sizeof(ev));
-            if (cb) cb(opaque, (int)c, ev.kind, ev.first, ev.last, ev.v, base + at + sizeof(Event), ev.len);
-            delivered++;
-        }
-    }
-    return delivered;
+    return R->events.read<Event>(f->stream, f->nchan, "SAME", "k_same_frames",
+        [](const Event &ev) { return ev.kind >= NRSC5HIP_SAME_BURST && ev.kind <= NRSC5HIP_SAME_MESSAGE && ev.len <= (unsigned)TEXT_MAX; },
+        [&](int c, const Event &ev, const uint8_t *text) { if (cb) cb(opaque, c, ev.kind, ev.first, ev.last, ev.v, text, ev.len); });
 }
 
 extern "C" int nrsc5hip_fm_same_get(nrsc5hip_fm *f, int channel, nrsc5hip_same_info *out)
@@ -264,27 +187,19 @@ extern "C" int nrsc5hip_fm_same_get(nrsc5hip_fm *f, int channel, nrsc5hip_same_i
 extern "C" int nrsc5hip_fm_same_stats(nrsc5hip_fm *f, int channel, long long stats[NRSC5HIP_SAME_NSTATS])
 {
     SAME_ENTER(f);
-    if (!stats || channel < 0 || channel >= f->nchan) FAIL(NRSC5HIP_EINVAL, "bad channel %d", channel);
-    HIPCHK(hipStreamSynchronize(f->stream));
-    unsigned long long v[NSTATS];
-    HIPCHK(hipMemcpy(v, R->d_stats.p + (size_t)channel * NSTATS, sizeof(v), hipMemcpyDeviceToHost));
-    for (int k = 0; k < NSTATS; k++) stats[k] = (long long)v[k];
-    return 0;
+    return fm::read_channel_stats<NSTATS>(f, R->d_stats.p, channel, stats);
 }
 
 extern "C" int nrsc5hip_stage_same_tones(nrsc5hip_fm *f, const int16_t *dev_in, long long in_stride_elems, long long n_in, float *c_out, float *q_out,
                                          float *metric_out, int32_t *s_out, uint8_t *bits_out, int32_t *counts_out)
 {
     SAME_ENTER(f);
-    if (n_in <= 0 || !dev_in) FAIL(NRSC5HIP_EINVAL, "bad input (n_in %lld)", n_in);
-    if (((uintptr_t)dev_in & 3) || (in_stride_elems & 1)) FAIL(NRSC5HIP_EINVAL, "input not aligned to 4 bytes (in_stride_elems %lld)", in_stride_elems);
-    if (f->nchan > 1 && in_stride_elems < 2 * n_in) FAIL(NRSC5HIP_EINVAL, "in_stride_elems %lld < 2 * n_in %lld", in_stride_elems, n_in);
-    const long long m1 = (n_in + 1) >> 1, r1 = segments_total(m1), nwin = windows_total(r1);
-    if ((m1 + fm::FT - 1) / fm::FT > 0x7fffffffLL) FAIL(NRSC5HIP_EINVAL, "input too large (%lld samples)", n_in);
+    fm::StageFront sf;
+    const int rc = sf.open(f, dev_in, in_stride_elems, n_in, false);
+    if (rc) return rc;
+    const long long m1 = sf.m1, r1 = segments_total(m1), nwin = windows_total(r1);
     const size_t K = (size_t)f->nchan;
-    nrsc5::DevTmp d, hist, c, sk, bits, counts, q, mt, sw;
-    HIPCHK(hipMalloc(&d.p, sizeof(float) * (size_t)m1 * K));
-    HIPCHK(hipMalloc(&hist.p, sizeof(int) * fm::HIST * K));
+    nrsc5::DevTmp c, sk, bits, counts, q, mt, sw;
     HIPCHK(hipMalloc(&c.p, sizeof(float4) * (size_t)(r1 + 1) * K));
     HIPCHK(hipMalloc(&sk.p, sizeof(int) * 2 * K));
     HIPCHK(hipMalloc(&bits.p, (size_t)(nwin + 1) * BITS_STRIDE * K));
@@ -292,16 +207,10 @@ extern "C" int nrsc5hip_stage_same_tones(nrsc5hip_fm *f, const int16_t *dev_in, 
     HIPCHK(hipMalloc(&q.p, sizeof(float) * (size_t)(nwin + 1) * WIN_PTS * K));
     HIPCHK(hipMalloc(&mt.p, sizeof(float) * (size_t)(nwin + 1) * S * K));
     HIPCHK(hipMalloc(&sw.p, sizeof(int) * (size_t)(nwin + 1) * K));
-    HIPCHK(hipMemsetAsync(hist.p, 0, sizeof(int) * fm::HIST * K, f->stream));
     HIPCHK(hipMemsetAsync(sk.p, 0xff, sizeof(int) * 2 * K, f->stream));
-    fm::FrontArgs a;
-    a.in = dev_in; a.in_stride = in_stride_elems; a.n0 = 0; a.n_in = n_in; a.hist = (const int *)hist.p; a.ha = f->d_ha;
-    a.d = (float *)d.p; a.d_stride = m1; a.d_base = 0; a.m0 = 0; a.m_count = m1;
-    fm::launch_front(f->stream, (int)((m1 + fm::FT - 1) / fm::FT), f->nchan, a);
-    HIPCHK(hipGetLastError());
     if (r1 > 0) {
         TonesArgs t;
-        t.d = (const float *)d.p; t.d_stride = m1; t.d_base = 0; t.cs = R->d_cs.p;
+        t.d = sf.df(); t.d_stride = m1; t.d_base = 0; t.cs = R->d_cs.p;
         t.c = (float4 *)c.p; t.c_stride = r1; t.c_base = 0; t.r0 = 0; t.r_count = r1;
         launch_tones(f->stream, (int)((r1 + TT - 1) / TT), f->nchan, t);
         HIPCHK(hipGetLastError());
